@@ -17,6 +17,9 @@ step (streams a clip's keys and encoder outputs once per decode step); `loss_par
 reference's own CPU numbers in this very run; `cpu_baseline` is the oracle's as-written CPU restatement of the same training step timed
 on this box's host cores on a bounded sample (a reported baseline, not the target); with N > 1 `data_parallel` lists each rank's decode
 steps and all-reduce wait (the straggler terms of SURVEY 8e).
+
+--dump-outputs DIR writes what the last timed step computed -- loss terms, log-probabilities, updated parameters; fixed seeded samples of the
+large ones -- as DIR/<name>.npy (dump_outputs), so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -37,6 +40,8 @@ MFMA_BF16_PEAK_TFS = 2500.0    # dense bf16 MFMA peak (same guide, "Peak BF16/FP
 MFMA_F32_PEAK_TFS = 157.3      # dense fp32-input MFMA peak (same guide: v_mfma_f32_16x16x4_f32, 64 FLOP/clk/SIMD)
 TF_RATIO = 0.7                 # hparams/pretrain.yaml teacher_forcing_ratio at epoch 0
 N_MINIBATCHES = 8              # distinct synthetic minibatches the timed steps cycle over
+DUMP_MAX_BYTES = 64 * 2 ** 20  # --dump-outputs: all files together
+DUMP_SEED = 1234               # --dump-outputs: the fixed sample of the staff rows and of the parameters
 # Teacher-forcing coin stream across data-parallel ranks: "rank_offset" = random.seed(1234 + rank) (the reference's
 # processes draw independently), "shared" = every rank seeds Python's random alike.  dp_straggler_simulation measures
 # both: the spread between ranks comes from the data, not from the coins (0.90 either way), so the reference's behaviour stays.
@@ -61,13 +66,23 @@ def parse(argv=None):
     ap.add_argument("--master-port", type=int, default=int(os.environ.get("MASTER_PORT", "29533")))
     ap.add_argument("--no-straggler-sim", action="store_true", help="skip the 1-GPU data-parallel straggler simulation (predicted_dp_efficiency)")
     ap.add_argument("--no-inference", action="store_true", help="skip the greedy-decode (config 5) block")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launcher_command(args, argv):
     """The command a bare `python bench.py --gpus N` (N > 1, no RANK in the environment) starts as a CHILD process: one rank per GPU
     under torch.distributed.run, the reference's own launch shape (reference README.md:119-122, pretrain.py:257)."""
     rest = [a for a in argv if a not in ("--dry-launch", "--launcher")]
+    for i, a in enumerate(rest):                # the ranks run from ROOT: a relative --dump-outputs DIR stays the caller's
+        if a == "--dump-outputs" and i + 1 < len(rest):
+            rest[i + 1] = os.path.abspath(rest[i + 1])
+        elif a.startswith("--dump-outputs="):
+            rest[i] = "--dump-outputs=" + os.path.abspath(a.split("=", 1)[1])
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
             "--master-port", str(args.master_port), os.path.abspath(__file__)] + rest
 
@@ -618,6 +633,51 @@ def inference_block(cfg, dev, batches=(256, 8)):
     return out
 
 
+def dump_outputs(outdir, step, model, batch, staff_rows=16384, param_samples=1 << 21):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 arrays in outdir/<name>.npy (at most DUMP_MAX_BYTES
+    in all), so that two builds can be compared output for output:
+      loss_terms (4,): time-signature, key, upper, lower NLL (what TrainStep returns); loss_total (1,);
+      clip_adadelta_ctl (3,): total gradient norm, clip coefficient, update-applied flag;
+      time_sig_logp, key_logp (B, bars, classes): TrainStep.last_outputs in full;
+      upper_logp_rows, lower_logp_rows (n, 173): a fixed sample (DUMP_SEED) of the staff log-probability rows whose target is not <pad> --
+        the only rows the step defines (TrainStep) -- and *_index (n, 3): their (clip, bar, position);
+      param_norms (83,): the L2 norm of every updated parameter tensor, named_parameters() order; batchnorm_buffers: every BatchNorm
+        buffer, named_buffers() order, concatenated;
+      params_sample (m,): a fixed sample (DUMP_SEED) of the updated flat parameter buffer (models.flatten_) and params_sample_index (m,).
+    Minibatches, initial weights, dropout masks and teacher-forcing coins are seeded, so two runs with the same arguments take the same
+    inputs.  The backward sums some weight gradients (embeddings, note-decoder GRU and output layer) with float atomics, so the updated
+    parameters of two runs differ in the last bits, and over many steps that grows into different fed-back tokens: at --steps 1
+    --warmup 0 everything but the updated parameters is bit-identical between runs; at more steps, compare against the spread between
+    two runs of one build."""
+    import numpy as np
+    from piano_a2s_amd.spec import PAD
+    rng = np.random.default_rng(DUMP_SEED)
+    ts, key, up, lo = step.last_outputs
+    out = {"loss_terms": step.objective.losses[:, 0], "loss_total": step.total, "clip_adadelta_ctl": step.opt.ctl,
+           "time_sig_logp": ts, "key_logp": key}
+    for name, o, tgt in (("upper", up, batch[3]), ("lower", lo, batch[5])):
+        live = np.argwhere((tgt != PAD).cpu().numpy())                          # (clip, bar, position), row-major
+        live = live[np.sort(rng.choice(len(live), size=min(staff_rows, len(live)), replace=False))]
+        at = torch.from_numpy(live).to(o.device)
+        out[f"{name}_logp_rows"] = o[at[:, 0], at[:, 1], at[:, 2]]
+        out[f"{name}_logp_rows_index"] = live.astype(np.float64)
+    with torch.no_grad():
+        out["param_norms"] = torch.stack([p.detach().double().norm() for p in model.parameters()])
+        out["batchnorm_buffers"] = torch.cat([b.detach().double().reshape(-1) for b in model.buffers()])
+    flat = step.flat
+    at = np.sort(rng.choice(flat.numel(), size=min(param_samples, flat.numel()), replace=False))
+    out["params_sample"] = flat[torch.from_numpy(at).to(flat.device)]
+    out["params_sample_index"] = at.astype(np.float64)
+    arrays = {name: (a.detach().cpu().numpy() if torch.is_tensor(a) else a) for name, a in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return total
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -723,6 +783,8 @@ def main():
     clip_steps_per_step = sum(timed.clip_steps) / max(len(timed.clip_steps), 1)
     main_step_ms = list(timed.step_ms)
     main_new_segments = list(timed.new_segments)
+    if args.dump_outputs and rank == 0:                   # before anything else steps the model again
+        dump_outputs(args.dump_outputs, step, model, batches[(args.steps - 1) % len(batches)])
     phases = phase_roofline(step, batches, B, 1201, cfg["freq_bins"], cfg["hidden_size"]) if (rank == 0 and world == 1 and not args.no_secondary) else None
     loss = float(step.total)
     groups = step._last[2] if step._last else None
