@@ -9,14 +9,20 @@ backward, (gradient all-reduce,) clip_grad_norm_(5.0) + Adadelta -- piano_a2s_am
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (one rank per GPU, RCCL)
 
 Rank 0 prints ONE JSON line.  Workload (config.workload): BASELINE.json configs[1], the pretrain.yaml model on synthetic clips as
-SURVEY.md 8(d) specifies them -- including the 1 % tail of full-length (398 / 189 token, no <eos>) bars; `tail_off` repeats the
-measurement without that tail (round 1's default workload).  `roofline` describes the 40-channel 3x3 convolution (two-term fp16 MFMA), measured
-live on conv4's forward launch; `roofline_phases` (round 5) EVERY phase of the step -- ConvStack forward / backward, encoder forward / backward,
-decoder -- against both roofs, from HIP events in this very run; `roofline_attention` the HBM-bound additive-attention
-step (streams a clip's keys and encoder outputs once per decode step); `loss_parity` checks the full-size model's loss against the
-reference's own CPU numbers in this very run; `cpu_baseline` is the oracle's as-written CPU restatement of the same training step timed
-on this box's host cores on a bounded sample (a reported baseline, not the target); with N > 1 `data_parallel` lists each rank's decode
-steps and all-reduce wait (the straggler terms of SURVEY 8e).
+SURVEY.md 8(d) specifies them -- including the 1 % tail of full-length (398 / 189 token, no <eos>) bars.  A plain run sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line: the headline `value` / `ms_per_step`, the `config` of the timed steps,
+`roofline_step` (arithmetic on the timed steps) and, with N > 1, `data_parallel` (each rank's decode steps and all-reduce wait: the
+straggler terms of SURVEY 8e).
+
+--full adds what takes runs of its own, after the timed steps: `tail_off` repeats the measurement without the 1 % tail (round 1's
+default workload); `roofline` describes the 40-channel 3x3 convolution (two-term fp16 MFMA), measured live on conv4's forward launch;
+`roofline_phases` (round 5) EVERY phase of the step -- ConvStack forward / backward, encoder forward / backward, decoder -- against both
+roofs, from HIP events over extra steps; `roofline_linear` the three products of the 19200 -> 256 Linear; `roofline_attention` the
+HBM-bound additive-attention step (streams a clip's keys and encoder outputs once per decode step); `loss_parity` checks the full-size
+model's loss against the reference's own CPU numbers; `inference` and `vqt` time greedy decoding and the VQT front end;
+`data_parallel_settings` and `dp_straggler_simulation` the data-parallel settings and straggler term on one GPU; `cpu_baseline` is the
+oracle's as-written CPU restatement of the same training step timed on this box's host cores on a bounded sample (a reported baseline,
+not the target).  The --no-* switches leave single --full blocks out.
 
 --dump-outputs DIR writes what the last timed step computed -- loss terms, log-probabilities, updated parameters; fixed seeded samples of the
 large ones -- as DIR/<name>.npy (dump_outputs), so that two builds run with the same arguments can be compared output for output.
@@ -56,16 +62,19 @@ def parse(argv=None):
     ap.add_argument("--no-reserve", action="store_true", help="do not reserve the caching allocator's per-stream pools before the first step")
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU per step")
     ap.add_argument("--full-tail", type=float, default=0.01, help="probability of a full-length (no <eos>) row per (clip,bar,staff); SURVEY 8d: 1 %%")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the tail-off secondary measurement and the loss-parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every measurement and check beyond the headline (rooflines, tail-off, loss parity, "
+                         "inference, VQT, data-parallel settings and straggler simulation, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the per-phase roofline, the tail-off secondary measurement and the loss-parity check")
     ap.add_argument("--cpu-clips", type=int, default=4)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no torchrun environment: print the launcher command as JSON and exit")
     ap.add_argument("--launcher", action="store_true", help="start the ranks through torch.distributed.run even for --gpus 1 (RCCL world of one)")
     ap.add_argument("--master-port", type=int, default=int(os.environ.get("MASTER_PORT", "29533")))
-    ap.add_argument("--no-straggler-sim", action="store_true", help="skip the 1-GPU data-parallel straggler simulation (predicted_dp_efficiency)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the greedy-decode (config 5) block")
+    ap.add_argument("--no-straggler-sim", action="store_true", help="with --full: skip the data-parallel settings and the 1-GPU straggler simulation (predicted_dp_efficiency)")
+    ap.add_argument("--no-inference", action="store_true", help="with --full: skip the greedy-decode (config 5) and VQT blocks")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args(argv)
@@ -779,15 +788,14 @@ def main():
             pool_gib = round(train.reserve_pools(dev, B), 1)
     reserve_pool()
     elapsed, decode_steps = timed(batches, args.warmup, args.steps)
+    # everything the result line says about the timed steps is read here, before --full steps the model again
     launches_per_step = round((a2s_hip.lib().a2s_launch_count() - timed.launches0) / args.steps)
     clip_steps_per_step = sum(timed.clip_steps) / max(len(timed.clip_steps), 1)
-    main_step_ms = list(timed.step_ms)
-    main_new_segments = list(timed.new_segments)
-    if args.dump_outputs and rank == 0:                   # before anything else steps the model again
-        dump_outputs(args.dump_outputs, step, model, batches[(args.steps - 1) % len(batches)])
-    phases = phase_roofline(step, batches, B, 1201, cfg["freq_bins"], cfg["hidden_size"]) if (rank == 0 and world == 1 and not args.no_secondary) else None
+    shared_steps_per_step = sum(timed.shared_steps) / max(len(timed.shared_steps), 1)
     loss = float(step.total)
     groups = step._last[2] if step._last else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, model, batches[(args.steps - 1) % len(batches)])
     # data-parallel straggler terms: decode steps each rank executed per optimizer step, and how long each rank's stream
     # sat waiting for the gradient all-reduce (the wait of a fast rank IS the imbalance)
     dp = None
@@ -798,16 +806,7 @@ def main():
         dist.all_gather(allr, mine)
         dp = {"decode_steps_per_step_by_rank": [round(float(t[0]), 1) for t in allr],
               "allreduce_wait_ms_per_step_by_rank": [round(float(t[1]), 2) for t in allr]}
-    secondary = None
-    if not args.no_secondary and args.full_tail > 0:
-        batches = None
-        step._last = None
-        torch.cuda.empty_cache()
-        reserve_pool()
-        e2, _ = timed(make_batches(0.0), 1, max(2, min(args.steps, 4)))
-        k2 = max(2, min(args.steps, 4))
-        secondary = {"value": round(B * world * k2 / e2, 3), "unit": "clips/s", "ms_per_step": round(e2 / k2 * 1e3, 2), "steps": k2, "warmup": 1,
-                     "what": "the same step on minibatches WITHOUT the 1 % full-length tail (round 1's default workload)"}
+    out = None
     if rank == 0:
         clips = B * world * args.steps
         out = {"metric": "training clips/sec (12 s, 5-bar)", "value": round(clips / elapsed, 3), "unit": "clips/s", "n_gpus": world,
@@ -826,7 +825,7 @@ def main():
                                      "holding full-length bars decoded as a concurrent clip group (loss, gradients and update identical "
                                      "to the per-bar loop over the whole minibatch)",
                           "clip_groups": groups, "decode_steps_per_step": round(sum(decode_steps) / max(len(decode_steps), 1), 1),
-                          "step_ms": main_step_ms, "hipMalloc_segments_per_step": main_new_segments, "allocator_pool_reserved_GiB": pool_gib,
+                          "step_ms": list(timed.step_ms), "hipMalloc_segments_per_step": list(timed.new_segments), "allocator_pool_reserved_GiB": pool_gib,
                           "allocator": {"hipMalloc_calls": torch.cuda.memory_stats().get("segment.all.allocated", 0),
                                         "alloc_retries": torch.cuda.memory_stats().get("num_alloc_retries", 0),
                                         "reserved_peak_GiB": round(torch.cuda.memory_stats().get("reserved_bytes.all.peak", 0) / 2 ** 30, 1)},
@@ -838,37 +837,47 @@ def main():
                                         "A2S_CONV_ROWS=0 selects round 2's tiled convolutions, A2S_ARITH=bf16x3 the three-term "
                                         "kernels, A2S_ARITH=f32 the fp32-input ones",
                           "final_loss": round(loss, 4), "peak_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}}
-        if secondary is not None:
-            out["tail_off"] = secondary
         if dp is not None:
             out["data_parallel"] = dp
-        step._last = None
-        batches = None
-        torch.cuda.empty_cache()
-        out["roofline"] = conv_roofline(B, 1201, cfg["freq_bins"])
-        out["roofline_step"] = step_roofline(B, 1201, cfg["freq_bins"], cfg["hidden_size"], clip_steps_per_step, out["ms_per_step"],
-                                             sum(timed.shared_steps) / max(len(timed.shared_steps), 1))
-        if phases is not None:
-            out["roofline_phases"] = phases
-        out["roofline_linear"] = linear_roofline(B, 1201, cfg["freq_bins"])
-        out["roofline_attention"] = attention_roofline(step, None, B, 1201, cfg["hidden_size"])
-        if not args.no_secondary and not use_dist:
-            # (single-process runs only: with a process group every TrainStep call takes part in the gradient all-reduce, and rank 0 is
-            # alone here -- the N = 1 line of the same commit carries the check)
-            out["loss_parity"] = loss_parity(dev)
-        if world == 1 and not args.no_inference:
-            out["inference"] = inference_block(cfg, dev)
-            out["inference"]["attention_roofline_frac"] = out["roofline_attention"]["frac"]
-        if world == 1 and not args.no_inference:
-            out["vqt"] = vqt_block(cfg, dev)
-        if world == 1 and not use_dist and not args.no_straggler_sim:
-            out["data_parallel_settings"] = dp_settings_block(model, cfg, B, dev, args.full_tail)
-        if world == 1 and not args.no_straggler_sim:
-            out["dp_straggler_simulation"] = straggler_simulation(step, cfg, B, dev, args.full_tail)
-            out["predicted_dp_efficiency"] = out["dp_straggler_simulation"][COIN_POLICY + "_coins"]["predicted_dp_efficiency"]
+        out["roofline_step"] = step_roofline(B, 1201, cfg["freq_bins"], cfg["hidden_size"], clip_steps_per_step, out["ms_per_step"], shared_steps_per_step)
         out["build"] = build_info
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.full_tail)
+    if args.full:
+        phases = phase_roofline(step, batches, B, 1201, cfg["freq_bins"], cfg["hidden_size"]) if (rank == 0 and world == 1 and not args.no_secondary) else None
+        if not args.no_secondary and args.full_tail > 0:
+            batches = None
+            step._last = None
+            torch.cuda.empty_cache()
+            reserve_pool()
+            k2 = max(2, min(args.steps, 4))
+            e2, _ = timed(make_batches(0.0), 1, k2)
+            if rank == 0:
+                out["tail_off"] = {"value": round(B * world * k2 / e2, 3), "unit": "clips/s", "ms_per_step": round(e2 / k2 * 1e3, 2), "steps": k2, "warmup": 1,
+                                   "what": "the same step on minibatches WITHOUT the 1 % full-length tail (round 1's default workload)"}
+        if rank == 0:
+            step._last = None
+            batches = None
+            torch.cuda.empty_cache()
+            out["roofline"] = conv_roofline(B, 1201, cfg["freq_bins"])
+            if phases is not None:
+                out["roofline_phases"] = phases
+            out["roofline_linear"] = linear_roofline(B, 1201, cfg["freq_bins"])
+            out["roofline_attention"] = attention_roofline(step, None, B, 1201, cfg["hidden_size"])
+            if not args.no_secondary and not use_dist:
+                # (single-process runs only: with a process group every TrainStep call takes part in the gradient all-reduce, and rank 0 is
+                # alone here -- the N = 1 line of the same commit carries the check)
+                out["loss_parity"] = loss_parity(dev)
+            if world == 1 and not args.no_inference:
+                out["inference"] = inference_block(cfg, dev)
+                out["inference"]["attention_roofline_frac"] = out["roofline_attention"]["frac"]
+                out["vqt"] = vqt_block(cfg, dev)
+            if world == 1 and not use_dist and not args.no_straggler_sim:
+                out["data_parallel_settings"] = dp_settings_block(model, cfg, B, dev, args.full_tail)
+            if world == 1 and not args.no_straggler_sim:
+                out["dp_straggler_simulation"] = straggler_simulation(step, cfg, B, dev, args.full_tail)
+                out["predicted_dp_efficiency"] = out["dp_straggler_simulation"][COIN_POLICY + "_coins"]["predicted_dp_efficiency"]
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.full_tail)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -1,5 +1,6 @@
 """bench.py --gpus N without a launcher environment starts its own ranks (reference README.md:119-122: `torchrun --nproc_per_node=N`).
 CPU box: the launcher command it would start (--dry-launch), nothing touches a GPU."""
+import importlib.util
 import json
 import os
 import subprocess
@@ -29,3 +30,13 @@ def test_single_gpu_and_ranks_do_not_relaunch():
     assert _run("--dry-launch", env=env)["launch"] is None                         # --gpus 1: runs in this process
     assert _run("--gpus", "2", "--dry-launch", env=dict(env, RANK="1", WORLD_SIZE="2", LOCAL_RANK="1"))["launch"] is None      # already a rank
     assert _run("--launcher", "--dry-launch", env=env)["launch"] is not None       # forced: one rank through torch.distributed.run
+
+
+def test_full_is_off_by_default_and_reaches_the_ranks():
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    cmd = _run("--gpus", "2", "--steps", "3", "--full", "--no-cpu-baseline", "--dry-launch", env=env)["launch"]
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == ["--gpus", "2", "--steps", "3", "--full", "--no-cpu-baseline"]
+    s = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(s)
+    s.loader.exec_module(bench)
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True

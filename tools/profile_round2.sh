@@ -4,8 +4,8 @@
 # counters of the dominant convolution kernel (own passes, no trace domains), phase times, two-term fp16 convolution accuracy / timing.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r2; mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/bench_kt.log 2>&1
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/bench_kt.log 2>&1
 python tools/kernel_stats.py $O/kt 60 > $O/kernel_stats.txt 2>&1
 python tools/trace_overlap.py $O/kt > $O/trace_overlap.txt 2>&1
 rm -rf $O/kt

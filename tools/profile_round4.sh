@@ -5,7 +5,7 @@
 # row-streaming convolutions and of the Linear GEMMs AT B = 256; phase times; the microbenchmarks the DESIGN tables quote.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r4p; mkdir -p $O
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
 python tools/kernel_stats.py $O/kt 70 > $O/kernel_stats.txt 2>&1
 python tools/trace_overlap.py $O/kt > $O/trace_overlap.txt 2>&1
 rm -rf $O/kt

@@ -16,7 +16,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc_t
 done > $O/conv_traffic_b256.txt 2>&1
 # kernel-trace summary of the bench command (5 steps under the profiler)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
 python tools/kernel_stats.py $O/kt 70 > $O/kernel_stats.txt 2>&1
 python tools/trace_overlap.py $O/kt > $O/trace_overlap.txt 2>&1
 rm -rf $O/kt

@@ -7,9 +7,9 @@ rm -f gpurun_out/g4_parity_report.txt
 (timeout 1500 python -m pytest tests -q -m gpu 2>&1 | grep -v Warn | tail -6) > $O/gpu_tests.txt 2>&1
 cp gpurun_out/g4_parity_report.txt $O/g4_parity_report.txt 2>/dev/null
 # the bench at the driver's flags
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err | grep '^{"metric' | tail -1 > $O/bench_driver_flags_b256.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | grep '^{"metric' | tail -1 > $O/bench_driver_flags_b256.json
 # kernel statistics + queue timelines of the bench command (4 steps under the profiler)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-inference --no-straggler-sim > $O/bench_kt.log 2>&1
 python tools/kernel_stats.py $O/kt 70 > $O/kernel_stats.txt 2>&1
 python tools/trace_overlap.py $O/kt > $O/trace_overlap.txt 2>&1
 rm -rf $O/kt
