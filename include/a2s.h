@@ -112,6 +112,10 @@ void a2s_gemm_debug_tile(int cfg);
 int a2s_debug_set(const char* key, int value);
 int a2s_debug_get(const char* key);   /* current value of "conv_bf16x3" / "gemm_bf16x3" / "wgrad_bf16x3" / "gru_fused"; -1 for an unknown key;
                                         * also "device_cus" / "device_xccs": compute units and XCDs the runtime reports for the current device */
+/* The library reads the environment variables that override a switch's default (A2S_CONV_ROWS, A2S_WGRAD_ROWS: decimal bit masks; A2S_GRU_PERSIST,
+ * A2S_DEC_PERSIST, A2S_DEC_FUSED: off when the text starts with 0) once, when it is loaded.  0, or A2S_ERR_ARG with the variable it could not
+ * parse in a2s_last_error() (that switch keeps its default). */
+int a2s_env_check(void);
 /* Persistent kernels (encoder recurrences, few-clip note decoder: one launch whose workgroups wait for each other, replacing the per-step
  * launches of nn.GRU / NoteDecoder.decode_notes, models.py:63-67,388-419).  Their waits are bounded; a launch that gives up poisons its outputs
  * with NaN (the loss becomes non-finite, the update is skipped) and ORs a bit into *device_word (a 4-byte device word the caller owns, zeroed by

@@ -1,162 +1,11 @@
 // extern "C" surface of liba2s_hip.so (declared in include/a2s.h): thin, exception-free trampolines onto the
-// *_impl launchers of a2s_gemm.hip / a2s_conv.hip / a2s_seq.hip.
-#include "a2s_common.h"
-#include "../../include/a2s.h"
+// *_impl launchers of the kernel translation units (a2s_internal.h), and the storage of the switch table (a2s_switches.h).
+#define A2S_SWITCHES_IMPL
+#include "a2s_internal.h"
 
 thread_local char a2s_err_msg[512] = {0};
 long long a2s_launch_counter = 0;
 
-// ---- launchers implemented in the kernel translation units
-int a2s_gemm_impl(hipStream_t, int, int, int, float, const float*, long, long, const float*, long, long, float, float*, long,
-                  const float*, int, int, long, long, long, int, float*, size_t);
-size_t a2s_gemm_workspace_bytes_impl(int, int, int, int);
-int a2s_gemm_affine_impl(hipStream_t, int, int, int, float, const float*, long, long, const float*, long, long, float, float*, long, const float*,
-                         int, int, long, long, long, int, float*, size_t, const float*, const float*, int, const float*, const float*, int,
-                         const float*, const float*, const float*, const float*, const float*, float*, int, int, const float*, const float*);
-int a2s_absmax_impl(hipStream_t, const float*, long, float*);
-void a2s_gemm_f16x2_set(int);
-int a2s_gemm_f16x2_enabled(void);
-int a2s_gemm_bnstats_slots(int);
-int a2s_conv3x3_impl(hipStream_t, const float*, const float*, float*, const float*, const float*, float*, int, int, int, int, int, int, float*,
-                     const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*);
-void a2s_conv_rows_set(int);
-void a2s_conv_c1_fast_set(int);
-int a2s_conv_c1_fast_enabled(void);
-int a2s_conv_rows_enabled(void);
-void a2s_wgrad_rows_set(int);
-int a2s_wgrad_rows_enabled(void);
-void a2s_staff_emb_fast_set(int);
-int a2s_staff_emb_fast_enabled(void);
-void a2s_conv_f16x2_set(int);
-int a2s_conv_f16x2_enabled(void);
-size_t a2s_conv3x3_workspace_floats_impl(int);
-void a2s_conv_bf16x3_set(int);
-void a2s_gemm_split_set(int);
-void a2s_wgrad_split_set(int);
-int a2s_wgrad_split_enabled(void);
-int a2s_gemm_split_enabled(void);
-int a2s_conv_bf16x3_enabled(void);
-int a2s_conv3x3_stat_blocks_impl(int, int, int, int);
-int a2s_bn_finalize_impl(hipStream_t, const float*, int, int, double, const float*, const float*, float*, float*, long long*,
-                         float*, float*, float*, float*, float, float, int);
-int a2s_bn_relu_apply_impl(hipStream_t, const float*, float*, const float*, const float*, long, int, int);
-int a2s_col_stats_impl(hipStream_t, const float*, float*, long, int, int);
-int a2s_bn1d_relu_dropout_impl(hipStream_t, const float*, float*, const float*, const float*, const uint8_t*, float, long, int);
-int a2s_gru_gates_fwd_impl(hipStream_t, const float*, long, const float*, long, const float*, long, float*, long, float*, long, float*, int, int);
-int a2s_gru_seq_fwd_impl(hipStream_t, const float*, long, long, const float*, const float*, float*, long, long, float*, float*,
-                         float*, float*, int, int, int, int, float*, size_t);
-int a2s_attn_step_fwd_impl(hipStream_t, const float*, const float*, const float*, long, const float*, float*, long, float*, long,
-                           float*, int, int, int, const int*, int, float*, const a2s_attn_rows*, a2s_attn_deferred* = nullptr);
-size_t a2s_attn_workspace_floats_impl(int, int, int, int);
-int a2s_log_softmax_rows_impl(hipStream_t, const float*, long, float*, long, int*, int, int);
-int a2s_embed_rows_impl(hipStream_t, const float*, const long long*, const int*, long, int, float*, long, int, int, int, const uint8_t*, float);
-int a2s_staff_emb_fwd_impl(hipStream_t, const float*, const float* const*, const long long*, const int*, long, const long long*, long,
-                           float*, long, int, float*, int, int, int, int);
-int a2s_gemm_pick_splitk_impl(int M, int N, int K, int batch);
-void a2s_gemm_debug_tile_impl(int);
-void a2s_gru_step_fused_set(int);
-void a2s_gru_persist_set(int);
-int a2s_gru_persist_enabled(void);
-void a2s_dec_persist_set(int);
-void a2s_gru_persist_alone_set(int);
-int a2s_gru_persist_alone(void);
-void a2s_attn_deep_set(int);
-void a2s_attn_defer_combine_set(int);
-void a2s_dec_mid_set(int);
-int a2s_dec_mid_enabled(void);
-int a2s_dec_mid_launches(void);
-int a2s_attn_defer_combine_enabled(void);
-int a2s_attn_deep_max_clips(void);
-int a2s_dec_persist_launches(void);
-int a2s_dec_persist_enabled(void);
-size_t a2s_note_decoder_persist_ws_bytes(int n_clips, int R, int steps);
-size_t a2s_note_decoder_bwd_persist_ws_bytes(int n_clips);
-int a2s_nll_grad_impl(hipStream_t st, float* dlogp, const long long* target, const float* loss_out, float gscale, long rows, int V, long long ignore_index);
-void a2s_attn_fused_combine_set(int v);
-int a2s_attn_fused_combine_enabled(void);
-void a2s_dec_fused_set(int v);
-void a2s_dec_fused_max_rows_set(int v);
-int a2s_dec_fused_enabled(void);
-int a2s_dec_fused_max_rows(void);
-size_t a2s_note_step_workspace_floats_impl(int H, int E);
-
-bool a2s_gru_step_fused_enabled(void);
-int a2s_note_decoder_fwd_impl(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
-int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_args& au, const a2s_note_dec_args& al, const int* pair_order,
-                                   const int* pair_rank, const int* pair_n_active, int* done_u, int* done_l);
-void a2s_attn_pair_set(int);
-int a2s_attn_pair_enabled(void);
-long a2s_attn_pair_launches(void);
-long a2s_attn_pair_bwd_launches(void);
-void a2s_attn_pair_fused_rows_set(int);
-int a2s_attn_pair_fused_rows(void);
-int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, const int* pair_order,
-                                   const int* pair_rank, const int* pair_n_active);
-
-int a2s_log_softmax_bwd_rows_impl(hipStream_t, const float*, const float*, long, int, float*, int, int, int, int);
-int a2s_gru_gates_bwd_impl(hipStream_t, const float*, long, const float*, long, const float*, const float*, long, float*, long, float*, long,
-                           float*, long, float*, long, int, int);
-int a2s_attn_step_bwd_impl(hipStream_t, const float*, const float*, const float*, long, const float*, const float*, const float*, long,
-                           const float*, long, const float*, long, float*, long, float*, long, float*, int, int, int, float*, const a2s_attn_rows*);
-int a2s_attn_dk_accum_impl(hipStream_t, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, const int*, int);
-int a2s_col_sum_impl(hipStream_t, const float*, long, float*, long, int, float, float, float*, size_t);
-int a2s_embed_scatter_add_impl(hipStream_t, float*, const long long*, const int*, long, int, const float*, long, int, int, int, const uint8_t*, float);
-int a2s_ew_act_bwd_impl(hipStream_t, const float*, const float*, float*, long, int);
-int a2s_note_decoder_bwd_impl(hipStream_t, const a2s_note_dec_bwd_args&);
-int a2s_gru_seq_bwd_impl(hipStream_t, const float*, long, long, const float*, long, long, const float*, const float*, const float*, float*,
-                         float*, float*, float*, float*, int, int, int, int, float*, size_t);
-int a2s_staff_emb_bwd_impl(hipStream_t, const float*, const float* const*, float* const*, float*, const long long*, const int*, long,
-                           const long long*, long, const float*, long, int, const float*, int, int, int, int);
-
-int a2s_bn_bwd_impl(hipStream_t, const float*, const float*, const float*, const float*, const float*, const float*, const uint8_t*, float,
-                    float*, float*, float*, float*, float*, long, int, int, float*);
-size_t a2s_bn_bwd_partial_floats_impl(long, int, int);
-int a2s_bn_bwd_from_partial_impl(hipStream_t, const float*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
-                                 const float*, int, float*, long, int, int, float*);
-
-int a2s_conv3x3_wgrad_impl(hipStream_t, const float*, const float*, const float*, const float*, float*, float*, size_t, int, int, int, int, int,
-                           const float*, const float*, const float*, const float*, const float*, const float*, float*, const float*, const float*);
-int a2s_act_bound_impl(hipStream_t, const float*, const float*, const float*, int, float*);
-void a2s_wgrad_f16x2_set(int);
-int a2s_wgrad_f16x2_enabled(void);
-size_t a2s_conv3x3_wgrad_workspace_bytes_impl(int, int);
-
-int a2s_nll_loss_impl(hipStream_t, const float*, const long long*, long, int, long long, float*, float*, float, double*, int);
-int a2s_clip_adadelta_impl(hipStream_t, float*, float*, float*, float*, long, const float*, float, float, float, float, float*, double*, int, int);
-
-int a2s_vqt_logmag_impl(hipStream_t, const float*, float*, float*, int, long, int, float);
-int a2s_vqt_logmag_octaves_impl(hipStream_t, const float*, float*, float*, int, long, int, int, float);
-int a2s_vqt_decimate_impl(hipStream_t, const float*, long, const float*, int, float*, long, int);
-
-int a2s_bn_bwd_stats_impl(hipStream_t, const float*, const float*, const float*, const float*, const float*, const float*, const uint8_t*, float,
-                          float*, float*, long, int, int);
-int a2s_bn_bwd_apply_impl(hipStream_t, const float*, const float*, const float*, const float*, const float*, const float*, const uint8_t*, float,
-                          const float*, const float*, double, float*, float*, float*, float*, long, int, int);
-int a2s_bn_bwd_sums_from_partial_impl(hipStream_t, const float*, int, int, float*);
-int a2s_bn_bwd_c12_from_sums_impl(hipStream_t, const float*, const float*, double, float*, float*, float*, int);
-
-int a2s_linear_dgrad_bnstats_impl(hipStream_t st, int M, int N, int K, const float* A, long lda, const float* Wt, long sBk, long sBn, float* C, long ldc,
-                                  const float* ep_y, const float* mean, const float* invstd, const float* scale, const float* shift, int period,
-                                  float* partial, const float* a_absmax, const float* b_absmax, float* ws, size_t ws_bytes, float* c_absmax_out);
-size_t a2s_linear_dgrad_ws_bytes_impl(int N, int K);
-int a2s_linear_fwd_impl(hipStream_t st, int M, int N, int K, const float* A, long lda, const float* W, float* C, long ldc, const float* a_scale,
-                        const float* a_shift, int period, const float* a_absmax, const float* w_absmax, float* ws, size_t ws_bytes);
-bool a2s_linear_fwd_ok(int M, int N, int K, long lda, long ldc, int period, const void* A, const void* W, const void* C);
-int a2s_linear_wgrad_impl(hipStream_t st, int M, int N, int K, const float* dz, long ldz, const float* A, long lda, float* G, long ldg, const float* a_scale,
-                          const float* a_shift, int period, const float* dz_absmax, const float* a_absmax, float* ws, size_t ws_bytes);
-size_t a2s_linear_wgrad_ws_bytes_impl(int M, int K);
-bool a2s_linear_wgrad_ok(int M, int N, int K, long ldz, long lda, long ldg, int period, const void* dz, const void* A, const void* G);
-int a2s_linear_dgrad_blocks_impl(int M);
-bool a2s_linear_dgrad_ok(int M, int N, int K, long lda, long sBk, long sBn, long ldc, int period, const void* A, const void* B, const void* C, const void* y);
-
-bool a2s_wgrad_rows_eligible(int F, int Cin, int Cout);
-int a2s_conv3x3_wgrad_rows_bn_impl(hipStream_t st, const float* g, const float* y, const float* mean, const float* invstd, const float* scale,
-                                   const float* shift, const float* c12, const float* g_absmax, int g_absmax_n, const float* y_absmax, float* dz_out,
-                                   float* dz_absmax_out, const float* x, const float* in_scale, const float* in_shift, float* dW, float* ws, size_t ws_bytes,
-                                   int B, int T, int F, int Cin, int Cout, const float* act_absmax);
-
-void a2s_attn_bulk_cap_set(int on);
-int a2s_attn_bulk_cap_enabled(void);
 #define ST ((hipStream_t)stream)
 
 extern "C" {
@@ -228,72 +77,31 @@ void a2s_gemm_debug_tile(int cfg) { a2s_gemm_debug_tile_impl(cfg); }
 size_t a2s_note_step_workspace_floats(int H, int E) { return a2s_note_step_workspace_floats_impl(H, E); }
 int a2s_debug_set(const char* key, int value) {
     if (!key) return A2S_ERR_ARG;
-    if (!strcmp(key, "dec_fused")) { a2s_dec_fused_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_fused_combine")) { a2s_attn_fused_combine_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_nt")) { a2s_attn_nt_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_bulk_cap")) { a2s_attn_bulk_cap_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_deep")) { a2s_attn_deep_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_defer_combine")) { a2s_attn_defer_combine_set(value); return A2S_OK; }
-    if (!strcmp(key, "dec_mid")) { a2s_dec_mid_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_pair")) { a2s_attn_pair_set(value); return A2S_OK; }
-    if (!strcmp(key, "attn_pair_fused_rows")) { a2s_attn_pair_fused_rows_set(value); return A2S_OK; }
-    if (!strcmp(key, "dec_fused_max_rows")) { a2s_dec_fused_max_rows_set(value); return A2S_OK; }
-    if (!strcmp(key, "gru_fused")) { a2s_gru_step_fused_set(value); return A2S_OK; }
-    if (!strcmp(key, "gru_persist")) { a2s_gru_persist_set(value); return A2S_OK; }
-    if (!strcmp(key, "gru_persist_alone")) { a2s_gru_persist_alone_set(value); return A2S_OK; }
-    if (!strcmp(key, "dec_persist")) { a2s_dec_persist_set(value); return A2S_OK; }
-    if (!strcmp(key, "persist_force_agent")) { a2s_persist_dbg_set(PERSIST_DBG_FORCE_AGENT, value); return A2S_OK; }
-    if (!strcmp(key, "persist_inject_abort")) { a2s_persist_dbg_set(PERSIST_DBG_INJECT_ABORT, value); return A2S_OK; }
-    if (!strcmp(key, "gemm_tile")) { a2s_gemm_debug_tile_impl(value); return A2S_OK; }
-    if (!strcmp(key, "conv_bf16x3")) { a2s_conv_bf16x3_set(value); return A2S_OK; }
-    if (!strcmp(key, "conv_rows")) { a2s_conv_rows_set(value); return A2S_OK; }
-    if (!strcmp(key, "conv_c1_fast")) { a2s_conv_c1_fast_set(value); return A2S_OK; }
-    if (!strcmp(key, "wgrad_rows")) { a2s_wgrad_rows_set(value); return A2S_OK; }
-    if (!strcmp(key, "staff_emb_fast")) { a2s_staff_emb_fast_set(value); return A2S_OK; }
-    if (!strcmp(key, "conv_f16x2")) { a2s_conv_f16x2_set(value); return A2S_OK; }
-    if (!strcmp(key, "wgrad_f16x2")) { a2s_wgrad_f16x2_set(value); return A2S_OK; }
-    if (!strcmp(key, "gemm_bf16x3")) { a2s_gemm_split_set(value); return A2S_OK; }
-    if (!strcmp(key, "gemm_f16x2")) { a2s_gemm_f16x2_set(value); return A2S_OK; }
-    if (!strcmp(key, "wgrad_bf16x3")) { a2s_wgrad_split_set(value); return A2S_OK; }
+    const int id = a2s_switch_find(key);
+    if (id >= 0) { a2s_switch_store(id, value); return A2S_OK; }
+    if (!strcmp(key, "gemm_tile")) { a2s_gemm_debug_tile_impl(value); return A2S_OK; }          // write-only
     snprintf(a2s_err_msg, sizeof(a2s_err_msg), "a2s_debug_set: unknown key %s", key);
     return A2S_ERR_ARG;
+}
+int a2s_env_check(void) {
+    if (const char* e = a2s_switch_env_error()) A2S_FAIL(A2S_ERR_ARG, "%s: expected a decimal number >= 0", e);
+    return A2S_OK;
 }
 
 int a2s_persist_abort_latch(void* device_word) { a2s_persist_latch_set(device_word); return A2S_OK; }
 
 int a2s_debug_get(const char* key) {
-    if (key && !strcmp(key, "attn_bulk_cap")) return a2s_attn_bulk_cap_enabled();
-    if (key && !strcmp(key, "attn_deep")) return a2s_attn_deep_max_clips();
-    if (key && !strcmp(key, "attn_defer_combine")) return a2s_attn_defer_combine_enabled();
-    if (key && !strcmp(key, "dec_mid")) return a2s_dec_mid_enabled();
-    if (key && !strcmp(key, "attn_pair")) return a2s_attn_pair_enabled();
-    if (key && !strcmp(key, "attn_pair_fused_rows")) return a2s_attn_pair_fused_rows();
-    if (key && !strcmp(key, "attn_pair_launches")) return (int)a2s_attn_pair_launches();
-    if (key && !strcmp(key, "attn_pair_bwd_launches")) return (int)a2s_attn_pair_bwd_launches();
-    if (key && !strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
-    if (key && !strcmp(key, "conv_bf16x3")) return a2s_conv_bf16x3_enabled();
-    if (key && !strcmp(key, "conv_rows")) return a2s_conv_rows_enabled();
-    if (key && !strcmp(key, "conv_c1_fast")) return a2s_conv_c1_fast_enabled();
-    if (key && !strcmp(key, "wgrad_rows")) return a2s_wgrad_rows_enabled();
-    if (key && !strcmp(key, "staff_emb_fast")) return a2s_staff_emb_fast_enabled();
-    if (key && !strcmp(key, "conv_f16x2")) return a2s_conv_f16x2_enabled();
-    if (key && !strcmp(key, "wgrad_f16x2")) return a2s_wgrad_f16x2_enabled();
-    if (key && !strcmp(key, "gemm_bf16x3")) return a2s_gemm_split_enabled();
-    if (key && !strcmp(key, "gemm_f16x2")) return a2s_gemm_f16x2_enabled();
-    if (key && !strcmp(key, "wgrad_bf16x3")) return a2s_wgrad_split_enabled();
-    if (key && !strcmp(key, "gru_fused")) return a2s_gru_step_fused_enabled();
-    if (key && !strcmp(key, "gru_persist")) return a2s_gru_persist_enabled();
-    if (key && !strcmp(key, "gru_persist_alone")) return a2s_gru_persist_alone();
-    if (key && !strcmp(key, "dec_persist")) return a2s_dec_persist_enabled();
-    if (key && !strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
-    if (key && !strcmp(key, "persist_force_agent")) return a2s_persist_dbg_get(PERSIST_DBG_FORCE_AGENT);
-    if (key && !strcmp(key, "persist_inject_abort")) return a2s_persist_dbg_get(PERSIST_DBG_INJECT_ABORT);
-    if (key && !strcmp(key, "device_cus")) return a2s_device_geometry().cus;
-    if (key && !strcmp(key, "device_xccs")) return a2s_device_geometry().xccs;
-    if (key && !strcmp(key, "dec_fused")) return a2s_dec_fused_enabled();
-    if (key && !strcmp(key, "attn_fused_combine")) return a2s_attn_fused_combine_enabled();
-    if (key && !strcmp(key, "attn_nt")) return a2s_attn_nt_enabled();
-    if (key && !strcmp(key, "dec_fused_max_rows")) return a2s_dec_fused_max_rows();
+    if (!key) return -1;
+    const int id = a2s_switch_find(key);
+    if (id == A2S_SW_attn_pair_fused_rows) return a2s_attn_pair_fused_rows();
+    if (id >= 0) return a2s_sw((a2s_switch)id);
+    // read-only: launch counters (tests: proof of the path taken) and what the runtime reports for the current device
+    if (!strcmp(key, "attn_pair_launches")) return (int)a2s_attn_pair_launches();
+    if (!strcmp(key, "attn_pair_bwd_launches")) return (int)a2s_attn_pair_bwd_launches();
+    if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
+    if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
+    if (!strcmp(key, "device_cus")) return a2s_device_geometry().cus;
+    if (!strcmp(key, "device_xccs")) return a2s_device_geometry().xccs;
     return -1;
 }
 

@@ -3,12 +3,7 @@
 // tokens are constants (only their embedding rows receive gradient), log_softmax rows that were never decoded
 // receive nothing, attention keys are hoisted so dK/dEnc contributions of all steps are accumulated once per
 // (bar, staff) instead of once per step.
-#include "a2s_common.h"
-#include "../../include/a2s.h"
-
-int a2s_gemm_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
-                  const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
-                  int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes);
+#include "a2s_internal.h"
 
 // ------------------------------------------------------------------------------------------- log_softmax bwd
 // y = log_softmax(x) row-wise; given g = dL/dy and y: dx = g - exp(y) * sum_j g_j.
@@ -119,21 +114,17 @@ __global__ __launch_bounds__(256) void attn_step_bwd(const float* __restrict__ K
     }
 }
 
-int a2s_attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+static int attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                                  const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b,
                                  long lddb, float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, float* ws, int B, int T, int H,
                                  const a2s_attn_rows* rows);
-int a2s_attn_step_bwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
-                           const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b,
-                           long lddb, float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, int B, int T, int H, float* ws,
-                           const a2s_attn_rows* rows = nullptr);
 
 int a2s_attn_step_bwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                            const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b,
                            long lddb, float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, int B, int T, int H, float* ws,
                            const a2s_attn_rows* rows) {
     if (H == 256 && ws)
-        return a2s_attn_step_bwd_split_impl(st, Kmat, enc, q, ldq, v, attw, ctx, ldctx, dctx_a, ldda, dctx_b, lddb, dctx_out, lddo, dq, lddq, ds_out, ws, B, T, H, rows);
+        return attn_step_bwd_split_impl(st, Kmat, enc, q, ldq, v, attw, ctx, ldctx, dctx_a, ldda, dctx_b, lddb, dctx_out, lddo, dq, lddq, ds_out, ws, B, T, H, rows);
     const int n_clips = rows ? rows->n_clips : B;
     const size_t shm = (((T + 3) & ~3) + 2 * H + 16) * sizeof(float);
     A2S_REQUIRE(H >= 1 && H <= 512, "attn_step_bwd: hidden_size must be in 1 .. 512 (got %d)", H);
@@ -290,25 +281,12 @@ int a2s_ew_act_bwd_impl(hipStream_t st, const float* g, const float* y, float* d
 // Reverse of a2s_note_decoder_fwd for one (bar, staff); `steps` = steps the forward executed.
 // argument block: a2s_note_dec_bwd_args (single definition in include/a2s.h)
 
-bool a2s_dec_step_fusable(int R, int H, int E, int V, const void* const* ptrs, int nptrs, const float* ws, size_t ws_floats, bool greedy = false);
-int a2s_note_step_fused_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a);
-int a2s_note_step_fused_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const float* dh_in, float* dh_out, const a2s_attn_rows* rows,
-                            int nrows, const int* rowmap);
-
-bool a2s_note_decoder_bwd_persist_ok(const a2s_note_dec_bwd_args& a);
-int a2s_note_decoder_bwd_persist(hipStream_t st, const a2s_note_dec_bwd_args& a);
-bool a2s_note_step_mid_bwd_ok(const a2s_note_dec_bwd_args& a);
-int a2s_note_step_mid_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
-int a2s_note_step_mid_bwd_query(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
-
 // the pair's clip bookkeeping at one step and the geometry its dq partials use (both staves' sweeps of the step in one launch: attn_bwd_split256_pair)
 struct AttnPairBwdStep { const int* clip_order; const int* clip_rank; int n_clips; int n_active; int step; int G; int chunk; };
 static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, int s, AttnPairBwdStep& p);
 static int attn_pair_bwd_combine(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const AttnPairBwdStep& p);
-int a2s_attn_pair_enabled(void);
 
 static int note_bwd_step_rows(const a2s_note_dec_bwd_args& a, int s) { return (a.row_list && a.n_rows_active) ? a.n_rows_active[s] : a.R; }
-int a2s_attn_pair_fused_rows(void);             // (a2s_seq.hip: the pair loops hand over to the few-row kernels at fewer rows)
 static thread_local int t_pair_rows_limit = -1;
 struct PairRowsLimit { PairRowsLimit(int v) { t_pair_rows_limit = v; } ~PairRowsLimit() { t_pair_rows_limit = -1; } };
 static bool note_bwd_step_fused(const a2s_note_dec_bwd_args& a, int s) {
@@ -430,7 +408,7 @@ int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
                                    const int* pair_rank, const int* pair_n_active) {
     const a2s_note_dec_bwd_args* as[2] = {&au, &al};
     hipStream_t sts[2] = {su, sl};
-    const bool can_pair = a2s_attn_pair_enabled() && su != sl && pair_order && pair_rank && pair_n_active && au.n_active && al.n_active && au.n_clips > 0 &&
+    const bool can_pair = a2s_sw(A2S_SW_attn_pair) && su != sl && pair_order && pair_rank && pair_n_active && au.n_active && al.n_active && au.n_clips > 0 &&
                           au.n_clips == al.n_clips && au.R == al.R && au.T == al.T && au.H == 256 && al.H == 256 && au.enc == al.enc && au.attn_ws && al.attn_ws &&
                           !a2s_note_decoder_bwd_persist_ok(au) && !a2s_note_decoder_bwd_persist_ok(al) && a2s_note_step_mid_bwd_ok(au) && a2s_note_step_mid_bwd_ok(al);
     if (!can_pair) {
@@ -476,16 +454,6 @@ int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
 //   dgi_all (B,T,3H) <- per-step input-projection gradients (caller: dW_ih, db_ih, dX via GEMMs)
 //   dgh_shift (B,T,3H) <- dgh of the step whose h_prev is out[:,t]  (row (b,t) pairs with out[b,t]: dW_hh = dgh_shift^T out)
 //   dgh_first (B,3H)   <- dgh of the first processed step (h_prev = 0): only contributes to db_hh
-bool a2s_gru_step_fused_enabled(void);
-int a2s_skinny_gemm_acc_impl(hipStream_t st, const float* A, long lda, const float* Bt, long ldb, float* Cm, long ldc, int R, int N, int K);
-int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t, const float* dhz_in, const float* dout, long ld_dout,
-                           const float* save, const float* hprev, long ld_hprev, float* dgi, long ld_dgi, float* dgh_out, float* dgh2,
-                           long ld_dgh2, float* dhz_out, int R, int H);
-
-bool a2s_gru_seq_bwd_persist_ok(int B, int T, int H, float* ws, size_t ws_bytes, size_t ws_used);
-int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
-                                 const float* gates, const float* w_hh_t, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first, int B, int T,
-                                 int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes);
 
 // out[c][r] = in[r][c]  (rows x cols -> cols x rows); small parameter matrices only
 __global__ void transpose_f32(const float* __restrict__ in, float* __restrict__ out, int rows, int cols) {
@@ -507,7 +475,7 @@ int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, lon
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "gru_seq_bwd memset: %s", hipGetErrorString(e));
     // one launch for dh_prev += dgh W_hh (skinny_gemm_acc, a2s_seq.hip): needs W_hh^T (H x 3H) so that both operands are
     // K-contiguous rows; the transposed copy lives in the workspace
-    const bool fused = a2s_gru_step_fused_enabled() && H % 32 == 0 && ws && ws_bytes >= sizeof(float) * 3 * H * H && ((uintptr_t)ws % 16 == 0);
+    const bool fused = a2s_sw(A2S_SW_gru_fused) && H % 32 == 0 && ws && ws_bytes >= sizeof(float) * 3 * H * H && ((uintptr_t)ws % 16 == 0);
     if (fused) {
         hipLaunchKernelGGL(transpose_f32, dim3(a2s_cdiv(3 * H * H, 256)), dim3(256), 0, st, w_hh, ws, 3 * H, H);
         A2S_CHECK_LAUNCH("transpose_f32");
@@ -698,7 +666,6 @@ __global__ __launch_bounds__(128) void staff_emb_bwd(const float* __restrict__ n
 // broadcast from LDS.  For the transposed products (dx = W_ih^T dgi, dh_prev += W_hh^T dgh) every thread also holds a quarter of a
 // COLUMN (24 registers): thread = (output k of 48, quarter of the 96 rows), the four partials meet in LDS.  The embedding row and
 // h_{s-2} of the next step are in flight during the current one.  Four barriers per step.
-int a2s_staff_emb_fast_enabled(void);
 __global__ __launch_bounds__(192) void staff_emb_bwd_e16s32(const float* __restrict__ note_emb, const float* __restrict__ w_ih_f,
                                                             const float* __restrict__ w_hh_f, const float* __restrict__ b_ih_f,
                                                             const float* __restrict__ b_hh_f, const float* __restrict__ w_ih_r,
@@ -819,7 +786,7 @@ int a2s_staff_emb_bwd_impl(hipStream_t st, const float* note_emb, const float* c
     A2S_REQUIRE((ids64 != nullptr) != (ids32 != nullptr), "staff_emb_bwd: exactly one of ids64/ids32");
     A2S_REQUIRE(hsave && grads_dev && note_emb_grad && dout, "staff_emb_bwd: null tensor");
     A2S_REQUIRE(E <= 5 * S && E + S <= 128, "staff_emb_bwd: note_emb_size <= 5 * staff_emb_size and note_emb_size + staff_emb_size <= 128 expected");
-    if (E == 16 && S == 32 && a2s_staff_emb_fast_enabled()) {
+    if (E == 16 && S == 32 && a2s_sw(A2S_SW_staff_emb_fast)) {
         const size_t shm16 = sizeof(float) * (E + S + 6 * S + 6 * S) + sizeof(int) * (size_t)maxlen;
         hipLaunchKernelGGL(staff_emb_bwd_e16s32, dim3(R, 2), dim3(192), shm16, st, note_emb, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7],
                            grads_dev, note_emb_grad, ids64, ids32, id_bstride, lengths, len_stride, dout, lddo, col0, hsave, maxlen);
@@ -1351,7 +1318,6 @@ __global__ __launch_bounds__(256) void attn_bwd_combine256(const float* __restri
     dq[(long)b * lddq + j] = s;
 }
 
-size_t a2s_attn_bulk_lds(size_t shm, int n_active, int backward);
 template <int NQ>
 static void launch_bwd_mq(hipStream_t st, int nwg, size_t shm, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                           const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b, long lddb,
@@ -1362,7 +1328,7 @@ static void launch_bwd_mq(hipStream_t st, int nwg, size_t shm, const float* Kmat
                             dctx_out, lddo, ws, ds_out, T, G, chunk, r.clip_order, r.row_until, r.step, r.n_clips);
 }
 
-int a2s_attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+static int attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                                  const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b,
                                  long lddb, float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, float* ws, int B, int T, int H,
                                  const a2s_attn_rows* rows) {
@@ -1379,9 +1345,9 @@ int a2s_attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const float*
     A2S_REQUIRE(r.n_active >= 0 && r.n_active <= r.n_clips && (!r.clip_order || r.clip_rank), "attn_step_bwd_split: bad row compaction");
     int G = 1, chunk = T;
     ws += A2S_ATTN_TICKETS;                 // the head of the workspace holds the arrival counters of the fused combines (a2s_seq.hip)
-    // streaming loads as in a2s_attn_step_fwd_split_impl -- single-row launches only: measured +12 % on attn_bwd_split256, -0 .. 5 % on the
+    // streaming loads as in attn_step_fwd_split_impl -- single-row launches only: measured +12 % on attn_bwd_split256, -0 .. 5 % on the
     // fused-rows kernels, whose enc pass feeds the matrix cores (profiles/r04_attn_mq_bench.txt)
-    const bool nt = a2s_attn_nt_enabled() > 0 && r.n_active >= a2s_attn_nt_enabled() && groups == 1;
+    const bool nt = a2s_sw(A2S_SW_attn_nt) > 0 && r.n_active >= a2s_sw(A2S_SW_attn_nt) && groups == 1;
     if (r.n_active > 0) {
         a2s_attn_split_geometry(r.n_active, T, &G, &chunk);
         // a handful of clips (late in the long-clip group's chain: the one or two clips that hold a full-length bar): a finer split -- the launch

@@ -44,16 +44,10 @@ extern long long a2s_launch_counter;
 
 static inline int a2s_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// ---- persistent kernels (csrc/a2s_persist.hip, csrc/a2s_dec_persist.hip): what the device offers, the process-wide abort latch, test hooks
+// ---- persistent kernels (csrc/a2s_persist.hip, csrc/a2s_dec_persist.hip): what the device offers, test hooks (a2s_persist_dbg(), a2s_internal.h)
 struct a2s_device_geom { int cus, xccs; };             // compute units and XCDs visible to this process (current device; cached)
-a2s_device_geom a2s_device_geometry(void);
-unsigned* a2s_persist_latch_ptr(void);                  // device word the kernels OR a bit into when a bounded wait gave up (null: none registered)
-void a2s_persist_latch_set(void* dev_word);
 #define PERSIST_DBG_FORCE_AGENT 1u                      // a2s_debug_set("persist_force_agent", 1): never take the plain-store (one-XCD) hand-off
 #define PERSIST_DBG_INJECT_ABORT 2u                     // a2s_debug_set("persist_inject_abort", 1): every persistent launch behaves as if a wait had timed out
-unsigned a2s_persist_dbg(void);
-void a2s_persist_dbg_set(unsigned bit, int on);
-int a2s_persist_dbg_get(unsigned bit);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -103,11 +97,6 @@ struct a2s_attn_deferred {
 };
 // head of the attention workspace: arrival counters of the fused combine (forward: [0, 4096), backward: [4096, 8192)), in floats
 #define A2S_ATTN_TICKETS 8192
-
-// Streaming K / enc loads of the split attention kernels: 0 = off, n > 0 = launches covering at least n clips use non-temporal loads
-// (a2s_debug_set("attn_nt", n)).
-int a2s_attn_nt_enabled(void);
-void a2s_attn_nt_set(int v);
 
 // ----------------------------------------------------------------------------- device helpers
 #ifdef __HIPCC__

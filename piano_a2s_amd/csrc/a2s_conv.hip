@@ -15,7 +15,7 @@
 //   so post-activation tensors are never written; the epilogue emits per-workgroup per-channel sum / sum of
 //   squares for THIS layer's batch statistics (reduced in a fixed order by bn_finalize -> deterministic).
 // conv3x3_c1: the first layer (Cin = 1, K = 9) as a direct VALU kernel (0.7 % of the stack's flops).
-#include "a2s_common.h"
+#include "a2s_internal.h"
 
 #define CV_TR 4
 #define CV_FT 32
@@ -1067,28 +1067,10 @@ int a2s_act_bound_impl(hipStream_t st, const float* scale, const float* shift, c
 }
 
 // ------------------------------------------------------------------------------------------- launchers
-static int g_conv_c1_fast = 1;        // the first layer's compile-time-shaped kernels (conv3x3_c1_fixed, conv3x3_wgrad_c1_stream); 0 = the generic ones (tests: bit-equal)
-void a2s_conv_c1_fast_set(int on) { g_conv_c1_fast = on; }
-int a2s_conv_c1_fast_enabled(void) { return g_conv_c1_fast; }
-static int g_conv_bf16x3 = 3;         // convolutions on the bf16 matrix pipes with 3-term split operands (conv3x3_split<.., 3>): bit 0 forward, bit 1 data-gradient launches
-void a2s_conv_bf16x3_set(int on) { g_conv_bf16x3 = on; }
-int a2s_conv_bf16x3_enabled(void) { return g_conv_bf16x3; }
-// ... and of those, which use the TWO-term fp16 split instead (conv3x3_split<.., 2>: three products instead of six); a data-gradient
-// launch additionally needs the max |dy| scalar of its operand (a2s_conv3x3_dgrad_bnstats_scaled) and stays on three terms without it
-static int g_conv_f16x2 = -1;
-void a2s_conv_f16x2_set(int on) { g_conv_f16x2 = on; }
-int a2s_conv_f16x2_enabled(void) {
-    if (g_conv_f16x2 < 0) g_conv_f16x2 = 3;
-    return g_conv_f16x2;
-}
+// Switches (a2s_switches.h): "conv_c1_fast", "conv_bf16x3" and, of the latter's launches, "conv_f16x2" -- a data-gradient launch additionally
+// needs the max |dy| scalar of its operand (a2s_conv3x3_dgrad_bnstats_scaled) and stays on three terms without it
 
 // the row-streaming kernel of a2s_conv_rows.hip (forward and data-gradient launches with F % 4 == 0, 20 / 40 channels)
-bool a2s_conv_rows_eligible(int F, int Cin);
-int a2s_conv_rows_blocks(int B, int T, int F);
-size_t a2s_conv_rows_workspace_floats(int Cin);
-int a2s_channel_absmax_impl(hipStream_t, const float*, long, int, int, float*);
-int a2s_conv3x3_rows_impl(hipStream_t, const float*, const float*, float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int,
-                          float*, const float*, const float*, const float*, const float*, const float*, const float*);
 
 size_t a2s_conv3x3_workspace_floats_impl(int Cin) {
     if (Cin == 1) return 0;
@@ -1097,8 +1079,6 @@ size_t a2s_conv3x3_workspace_floats_impl(int Cin) {
     const size_t rows = a2s_conv_rows_workspace_floats(Cin);
     return tiled > rows ? tiled : rows;
 }
-
-int a2s_conv3x3_stat_blocks_impl(int B, int T, int F, int Cin);
 
 int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale,
                      const float* in_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout, int flip, float* ws,
@@ -1124,7 +1104,7 @@ int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, c
     }
     if (Cin == 1) {
         A2S_REQUIRE(Cout <= 20 && !flip && !in_scale, "conv3x3: Cin=1 path supports Cout<=20, no flip, no input affine");
-        const bool fixed = g_conv_c1_fast && Cout == 20 && F % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
+        const bool fixed = a2s_sw(A2S_SW_conv_c1_fast) && Cout == 20 && F % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
         if (fixed) hipLaunchKernelGGL(conv3x3_c1_fixed<20>, dim3(a2s_conv3x3_stat_blocks_impl(B, T, F, 1)), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(conv3x3_c1, dim3(a2s_conv3x3_stat_blocks_impl(B, T, F, 1)), dim3(256), 0, st, a);
     } else {
@@ -1132,9 +1112,9 @@ int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, c
         A2S_REQUIRE(ws, "conv3x3: needs a workspace of a2s_conv3x3_workspace_floats(Cin) floats for the packed weights");
         A2S_REQUIRE(Cout == 20 || Cout == 40, "conv3x3: Cout must be 20 or 40 (got %d)", Cout);
         const int nblk4 = B * a2s_cdiv(a2s_cdiv(T, CV_TR), C3_TPW) * a2s_cdiv(F, C2_FT);
-        if (g_conv_bf16x3 & (flip ? 2 : 1)) {
+        if (a2s_sw(A2S_SW_conv_bf16x3) & (flip ? 2 : 1)) {
             // two fp16 terms when enabled -- a gradient operand (flip) only with its max |x| scalar: fp16 has no exponent range to spare
-            const bool two = (a2s_conv_f16x2_enabled() & (flip ? 2 : 1)) && (!flip || x_absmax);
+            const bool two = (a2s_sw(A2S_SW_conv_f16x2) & (flip ? 2 : 1)) && (!flip || x_absmax);
             const int terms = two ? 2 : 3;
             const int n = c4_chunks(Cin) * C4_SLOTS * Cout * 8;
             const size_t image = c4_chunks(Cin) * c4_chunk_bytes(Cout, terms);
@@ -2092,20 +2072,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_split(const float* __res
     }
 }
 
-static int g_wgrad_split = 1;          // conv3x3_wgrad_split for the plain weight-gradient launches: 1 = where it is faster, 2 = every eligible launch
-void a2s_wgrad_split_set(int on) { g_wgrad_split = on; }
-int a2s_wgrad_split_enabled(void) { return g_wgrad_split; }
-static int g_wgrad_f16x2 = -1;         // ... with two fp16 terms (needs the max |dy| scalar) instead of three bf16 terms
-void a2s_wgrad_f16x2_set(int on) { g_wgrad_f16x2 = on; }
-int a2s_wgrad_f16x2_enabled(void) {
-    if (g_wgrad_f16x2 < 0) g_wgrad_f16x2 = 1;
-    return g_wgrad_f16x2;
-}
-
-bool a2s_wgrad_rows_eligible(int F, int Cin, int Cout);
-int a2s_conv3x3_wgrad_rows_impl(hipStream_t st, const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dW, float* ws,
-                                size_t ws_bytes, int B, int T, int F, int Cin, int Cout, const float* dy_absmax, const float* act_absmax);
-
 size_t a2s_conv3x3_wgrad_workspace_bytes_impl(int Cin, int Cout) {
     const int chunks = (Cin + CV_CK - 1) / CV_CK;
     return (size_t)chunks * 1024 * Cout * CV_CK * 9 * sizeof(float);
@@ -2123,7 +2089,7 @@ int a2s_conv3x3_wgrad_impl(hipStream_t st, const float* dy, const float* x, cons
     if (Cin == 1 && !in_scale && Cout * C1W_PARTS <= 256 && (size_t)Cout * F >= 256 * 9) {
         const size_t shm = ((size_t)Cout * F + 3 * (F + 8)) * sizeof(float);
         if (shm <= 64 * 1024) {
-            const bool stream = g_conv_c1_fast && bn_y && Cout == 20 && F == 480 && (((uintptr_t)dy | (uintptr_t)bn_y | (uintptr_t)dy_out | (uintptr_t)x) & 15) == 0;
+            const bool stream = a2s_sw(A2S_SW_conv_c1_fast) && bn_y && Cout == 20 && F == 480 && (((uintptr_t)dy | (uintptr_t)bn_y | (uintptr_t)dy_out | (uintptr_t)x) & 15) == 0;
             if (stream) hipLaunchKernelGGL((conv3x3_wgrad_c1_stream<20, 480>), dim3(WGRAD_SLABS), dim3(256), shm, st, dy, x, ws, B, T, bn);
             else hipLaunchKernelGGL(conv3x3_wgrad_c1, dim3(WGRAD_SLABS), dim3(256), shm, st, dy, x, ws, B, T, F, Cout, bn);
             A2S_CHECK_LAUNCH("conv3x3_wgrad_c1");
@@ -2132,15 +2098,15 @@ int a2s_conv3x3_wgrad_impl(hipStream_t st, const float* dy, const float* x, cons
             return A2S_OK;
         }
     }
-    const bool two = a2s_wgrad_f16x2_enabled() && dy_absmax;          // two fp16 terms: with the operand's max |dy| only
+    const bool two = a2s_sw(A2S_SW_wgrad_f16x2) && dy_absmax;          // two fp16 terms: with the operand's max |dy| only
     // round 3: the row-streaming kernel (a2s_conv_wrows.hip) wherever its operand ranges are known
     if (two && !bn_y && a2s_wgrad_rows_eligible(F, Cin, Cout) && (!in_scale || act_absmax))
         return a2s_conv3x3_wgrad_rows_impl(st, dy, x, in_scale, in_shift, dW, ws, ws_bytes, B, T, F, Cin, Cout, dy_absmax, act_absmax);
     // measured at B = 64 (tools/conv_f16x2_check.py; fp32-input kernel / three bf16 terms / two fp16 terms): 40 -> 40: 12.3 / 9.9 / 7.1 ms,
     // 20 -> 40: 6.3 / 7.4 / 5.3 ms, 20 -> 20: 4.6 / 6.2 / 4.6 ms -- the three-term kernel only pays off at 40 -> 40 channels, the two-term
     // one for 40 output channels (wgrad_bf16x3 = 2 / wgrad_f16x2 = 2: every eligible launch regardless)
-    const bool split_here = g_wgrad_split > 1 || (Cin == 40 && Cout == 40) || (two && (Cout == 40 || a2s_wgrad_f16x2_enabled() > 1));
-    if (g_wgrad_split && !bn_y && Cin > 1 && Cin <= 40 && (Cout == 20 || Cout == 40) && split_here) {
+    const bool split_here = a2s_sw(A2S_SW_wgrad_bf16x3) > 1 || (Cin == 40 && Cout == 40) || (two && (Cout == 40 || a2s_sw(A2S_SW_wgrad_f16x2) > 1));
+    if (a2s_sw(A2S_SW_wgrad_bf16x3) && !bn_y && Cin > 1 && Cin <= 40 && (Cout == 20 || Cout == 40) && split_here) {
         const int nslabs = 256;               // one 512-thread workgroup per CU
         A2S_REQUIRE(ws_bytes >= (size_t)nslabs * Cout * Cin * 9 * sizeof(float), "conv3x3_wgrad: workspace too small for the split-operand kernel");
         if (two && Cout == 20) hipLaunchKernelGGL((conv3x3_wgrad_split<20, 2>), dim3(nslabs), dim3(512), 0, st, dy, x, in_scale, in_shift, ws, B, T, F, Cin, dy_absmax, act_absmax);

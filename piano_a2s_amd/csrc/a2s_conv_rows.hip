@@ -33,7 +33,7 @@
 //   * weights: output channel co by 2^(13 - exponent(max_{ci,tap} |w 2^-k_ci|)), undone per lane in the epilogue.
 //   An element x of an operand whose scaled magnitude is below 2^-3 has an absolute error of 2^-25 (second term subnormal): relative to
 //   the channel's (tensor's) largest magnitude that is 2^-39; everything above carries 22 significand bits.
-#include "a2s_common.h"
+#include "a2s_internal.h"
 #include <type_traits>
 
 #define RW_P 120             // output columns per workgroup
@@ -1146,15 +1146,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- launcher
-static int g_conv_rows = -1;
-void a2s_conv_rows_set(int on) { g_conv_rows = on; }
-int a2s_conv_rows_enabled(void) {
-    // bit 0: the row-streaming kernels; bit 1: their second generation (conv3x3_rows16) where it exists (Cout = 40); bits 2 / 3: its form with two
-    // accumulator sets (epilogue under the next row's multiply) for the forward / data-gradient launches
-    if (g_conv_rows < 0) { const char* e = getenv("A2S_CONV_ROWS"); g_conv_rows = e ? atoi(e) : 7; }
-    return g_conv_rows;
-}
-bool a2s_conv_rows_eligible(int F, int Cin) { return a2s_conv_rows_enabled() && F % 4 == 0 && (Cin == 20 || Cin == 40); }
+// "conv_rows" -- bit 0: the row-streaming kernels; bit 1: their second generation (conv3x3_rows16) where it exists (Cout = 40); bits 2 / 3: its
+// form with two accumulator sets (epilogue under the next row's multiply) for the forward / data-gradient launches
+bool a2s_conv_rows_eligible(int F, int Cin) { return a2s_sw(A2S_SW_conv_rows) && F % 4 == 0 && (Cin == 20 || Cin == 40); }
 
 static void rows_geometry(int B, int T, int F, int* tilesF, int* nstrips, int* strip_len) {
     *tilesF = a2s_cdiv(F, RW_P);
@@ -1181,7 +1175,7 @@ template <int CIN, int COUT>
 static int rows16_launch(hipStream_t st, const RowsArgs& a, bool affine, bool bnred, int nwork) {
     constexpr int NT = 512;
     // the two-accumulator-set form (round 6): bit 2 the forward instances, bit 3 the data-gradient instance (24 spilled registers at 40 -> 40)
-    const int en = a2s_conv_rows_enabled();
+    const int en = a2s_sw(A2S_SW_conv_rows);
     if (affine && (en & 4)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false, true>), dim3(nwork), dim3(NT), 0, st, a);
     else if (affine) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false>), dim3(nwork), dim3(NT), 0, st, a);
     else if (bnred && (en & 8)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true, true>), dim3(nwork), dim3(NT), 0, st, a);
@@ -1203,8 +1197,6 @@ static void rows_pack_launch(hipStream_t st, const float* w, int flip, const flo
                              const float* x_absmax, unsigned char* wimg, float* hdr, float* out_absmax) {
     hipLaunchKernelGGL((rows_pack<CIN, COUT>), dim3(COUT / 5), dim3(256), 0, st, w, flip, in_scale, in_shift, in_absmax, x_absmax, wimg, hdr, out_absmax);
 }
-
-int a2s_absmax_impl(hipStream_t, const float*, long, float*);
 
 int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
                           const float* in_absmax, float* stat_partial, float* out_absmax, int B, int T, int F, int Cin, int Cout, int flip,
@@ -1236,7 +1228,7 @@ int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float*
     a.nwork = B * a.tilesF * a.nstrips;
     const bool affine = in_scale != nullptr, bnred = yl != nullptr;
 #define R16_CASE(CI, CO)                                                                                                     \
-    if (Cin == CI && Cout == CO && (a2s_conv_rows_enabled() & 2)) {                                                          \
+    if (Cin == CI && Cout == CO && (a2s_sw(A2S_SW_conv_rows) & 2)) {                                                          \
         hipLaunchKernelGGL((rows16_pack<CI, CO>), dim3(8), dim3(256), 0, st, w, flip, in_scale, in_shift, in_absmax, x_absmax, wimg, hdr, out_absmax); \
         A2S_CHECK_LAUNCH("rows16_pack");                                                                                     \
         return rows16_launch<CI, CO>(st, a, affine, bnred, a.nwork);                                                         \

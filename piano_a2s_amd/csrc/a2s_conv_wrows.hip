@@ -29,7 +29,7 @@
 // staging waves 40-57 %: the multiply stream is the critical one at ~5200 cycles per row against 3672 of bare MFMA issue (216 x 17), and
 // the shader clock falls from ~2.3 GHz to ~1.7 GHz once the HBM stream runs beside the matrix pipes (same cycles per row with the loads
 // redirected to one resident row: 2.83 ms instead of 3.72 ms) -- power, not latency: 3 or 4 rows of loads in flight change nothing.
-#include "a2s_common.h"
+#include "a2s_internal.h"
 
 #define WR_TP 128              // positions per strip
 #ifndef WR_SROW
@@ -400,14 +400,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_rows(WgRowsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- launcher
-static int g_wgrad_rows = -1;
-void a2s_wgrad_rows_set(int on) { g_wgrad_rows = on; }
-int a2s_wgrad_rows_enabled(void) {
-    if (g_wgrad_rows < 0) { const char* e = getenv("A2S_WGRAD_ROWS"); g_wgrad_rows = e ? atoi(e) : 1; }
-    return g_wgrad_rows;
-}
 bool a2s_wgrad_rows_eligible(int F, int Cin, int Cout) {
-    return a2s_wgrad_rows_enabled() && F % 4 == 0 && (Cin == 20 || Cin == 40) && (Cout == 20 || Cout == 40);
+    return a2s_sw(A2S_SW_wgrad_rows) && F % 4 == 0 && (Cin == 20 || Cin == 40) && (Cout == 20 || Cout == 40);
 }
 __global__ void wgrad_rows_reduce(const float* __restrict__ partial, float* __restrict__ dW, int nslabs, int n) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;

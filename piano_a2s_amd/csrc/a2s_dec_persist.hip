@@ -18,8 +18,7 @@
 // the row's (max, 1 / sum) and normalised by a small kernel after the loop.
 //
 // Every wait is bounded (SPIN_LIMIT polls, then the abort word is raised, everybody leaves and the outputs are poisoned with NaN).
-#include "a2s_common.h"
-#include "../../include/a2s.h"
+#include "a2s_internal.h"
 
 typedef unsigned long long u64;
 typedef __attribute__((address_space(1))) u64 gu64;
@@ -936,12 +935,6 @@ __global__ __launch_bounds__(256) void dec_persist_greedy_fixup(float* __restric
 // ------------------------------------------------------------------------------------------- launcher
 static int g_dec_persist_launches = 0;                  // persistent forward + backward launches so far (a2s_debug_get("dec_persist_launches"): tests)
 int a2s_dec_persist_launches(void) { return g_dec_persist_launches; }
-static int g_dec_persist = -1;                          // A2S_DEC_PERSIST=0 / a2s_debug_set("dec_persist", 0): the launch-per-step kernels
-void a2s_dec_persist_set(int v) { g_dec_persist = v ? 1 : 0; }
-int a2s_dec_persist_enabled(void) {
-    if (g_dec_persist < 0) { const char* e = getenv("A2S_DEC_PERSIST"); g_dec_persist = (e && e[0] == '0') ? 0 : 1; }
-    return g_dec_persist;
-}
 static size_t dp_lds_bytes(void) { return sizeof(float) * (CHF * HH + CHF * H2 + MAXR * HH + MAXR * 64 + 64 + DP_PART_FLOATS + MAXR * XLD); }
 size_t a2s_note_decoder_persist_ws_bytes(int n_clips, int R, int steps) {
     if (n_clips < 1 || n_clips > 8) return 0;
@@ -968,7 +961,7 @@ static bool dp_chip_ok(bool bwd) {
 }
 
 bool a2s_note_decoder_fwd_persist_ok(const a2s_note_dec_args& a) {
-    if (!a2s_dec_persist_enabled() || !a.persist_ws || a.use_graph || !dp_chip_ok(false)) return false;
+    if (!a2s_sw(A2S_SW_dec_persist) || !a.persist_ws || a.use_graph || !dp_chip_ok(false)) return false;
     if (!a.gt && (a.gates || a.attw || a.drop || a.n_active)) return false;      // greedy: inference only
     const int C = a.n_clips > 0 ? a.n_clips : a.R;
     if (C < 1 || C > 8 || a.R % C || a.R / C > MAXR) return false;
@@ -1034,18 +1027,13 @@ int a2s_note_decoder_fwd_persist(hipStream_t st, const a2s_note_dec_args& a, int
 }
 
 // ------------------------------------------------------------------------------------------- backward launcher
-int a2s_gemm_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
-                  const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
-                  int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes);
-int a2s_note_step_fused_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a);
-size_t a2s_note_step_fused_head_floats(void);
 static size_t dpb_lds_bytes(void) { return sizeof(float) * (CHF * HH + CHF * H2 + MAXR * HH + MAXR * H2 + 2 * MAXR * 64 + 64 + DPB_PART_FLOATS); }
 size_t a2s_note_decoder_bwd_persist_ws_bytes(int n_clips) {
     if (n_clips < 1 || n_clips > 8) return 0;
     return 512 + sizeof(unsigned) * 8 * NWG + sizeof(u64) * (size_t)n_clips * DPB_REGION;
 }
 bool a2s_note_decoder_bwd_persist_ok(const a2s_note_dec_bwd_args& a) {
-    if (!a2s_dec_persist_enabled() || !a.persist_ws || !dp_chip_ok(true)) return false;
+    if (!a2s_sw(A2S_SW_dec_persist) || !a.persist_ws || !dp_chip_ok(true)) return false;
     const int C = a.n_clips > 0 ? a.n_clips : a.R;
     if (C < 1 || C > 8 || a.R % C || a.R / C > MAXR) return false;
     if (a.H != HH || a.E != EE || a.T > NWG * CHF || a.steps < 1 || !a.step_ws) return false;

@@ -12,8 +12,7 @@
 // Structure: 256 threads = 4 waves; block tile BM x BN x 32; register-prefetched global->LDS staging
 // (global loads for tile t+1 are in flight while tile t is multiplied); LDS images padded so the
 // fragment reads (lane = (m&15, k>>... ) one dword each) are at most 2-way conflicted.
-#include "a2s_common.h"
-int a2s_attn_bulk_cap_enabled(void);
+#include "a2s_internal.h"
 
 struct GemmArgs {
     const float* A; const float* B; float* C; const float* bias;
@@ -541,18 +540,6 @@ __global__ void gemm_splitk_reduce(GemmArgs g) {
     *c = v;
 }
 
-// 1: 128x128 launches with two k-contiguous operands run on the bf16 matrix pipes with 3-term split operands (a2s_debug_set "gemm_bf16x3")
-static int g_gemm_split = 1;
-void a2s_gemm_split_set(int on) { g_gemm_split = on; }
-int a2s_gemm_split_enabled(void) { return g_gemm_split; }
-// ... two fp16 terms instead of three bf16 terms where the caller vouches for the operands' ranges (a2s_gemm_f32_desc: two_term)
-static int g_gemm_f16x2 = -1;
-void a2s_gemm_f16x2_set(int on) { g_gemm_f16x2 = on; }
-int a2s_gemm_f16x2_enabled(void) {
-    if (g_gemm_f16x2 < 0) g_gemm_f16x2 = 1;          // (a2s_debug_set("gemm_f16x2", 0) / A2S_ARITH=bf16x3: the three-term bf16 split)
-    return g_gemm_f16x2;
-}
-
 // max |x| of a tensor into a device scalar (atomicMax on the float bits; *out must be zero before): the power-of-two operand scales of
 // the two-term fp16 kernels
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
@@ -577,8 +564,8 @@ static void launch_cfg(const GemmArgs& g, bool akc, bool bkc, hipStream_t st) {
     if constexpr (BM == 128 && BN == 128) {
         // row-contiguous operands need unit row stride and 16-byte loads for the transposed staging (else the fp32-input path)
         const bool a_ok = akc || (g.sAm == 1 && g.vecA), b_ok = bkc || (g.sBn == 1 && g.vecB);
-        if (g_gemm_split && g.K >= (g.two_term ? 128 : 256) && a_ok && b_ok) {      // (a short K amortises the two-term staging, not the three-term one)
-            if (g.two_term && a2s_gemm_f16x2_enabled()) {
+        if (a2s_sw(A2S_SW_gemm_bf16x3) && g.K >= (g.two_term ? 128 : 256) && a_ok && b_ok) {      // (a short K amortises the two-term staging, not the three-term one)
+            if (g.two_term && a2s_sw(A2S_SW_gemm_f16x2)) {
                 if (akc && bkc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, true, 2>), grid, dim3(256), 0, st, g);
                 else if (akc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, false, 2>), grid, dim3(256), 0, st, g);
                 else if (bkc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true, 2>), grid, dim3(256), 0, st, g);
@@ -593,10 +580,10 @@ static void launch_cfg(const GemmArgs& g, bool akc, bool bkc, hipStream_t st) {
         }
     }
     // Occupancy cap of the bulk clip group's per-step products (M >= 256 rows, small tiles) while another clip group decodes beside it
-    // (a2s_attn_bulk_cap_enabled(): the same condition as the attention sweeps' cap): 16 KB of unused dynamic LDS per workgroup.
+    // ("attn_bulk_cap": the same condition as the attention sweeps' cap): 16 KB of unused dynamic LDS per workgroup.
     // The long-clip chain's kernels wait for a place beside whole grids of these workgroups (profiles/r05_trace_overlap.txt).  Default 16 KB (3 instead of
     // 4 workgroups of the 64x32 tile per CU): 447.3 -> 443.5 ms per step, 32 KB 445.2 (profiles/r05_prefix_percent.txt).
-    const size_t pad = (BM * BN <= 64 * 64 && g.M >= 256 && a2s_attn_bulk_cap_enabled()) ? 16384 : 0;
+    const size_t pad = (BM * BN <= 64 * 64 && g.M >= 256 && a2s_sw(A2S_SW_attn_bulk_cap)) ? 16384 : 0;
     if (akc && bkc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, true>), grid, dim3(256), pad, st, g);
     else if (akc && !bkc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, false>), grid, dim3(256), pad, st, g);
     else if (!akc && bkc) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true>), grid, dim3(256), pad, st, g);
@@ -610,7 +597,7 @@ static bool big_two_term_ok(const GemmArgs& g, bool akc, bool bkc) {
     const bool a_ok = akc || (g.sAm == 1 && g.vecA), b_ok = bkc || (g.sBn == 1 && g.vecB);
     // (the BatchNorm-statistics epilogue keeps its partial layout: a 256-column tile touches at most two channels of period >= 256 and
     // at most as many tiles per channel as the 128-column layout has slots; unused partial rows stay zero)
-    return g.two_term && a2s_gemm_f16x2_enabled() && g_gemm_split && (!g.ep_y || g.ep_period >= 256) && g.K >= 128 && a_ok && b_ok && g.M >= 256 && g.N >= 256 &&
+    return g.two_term && a2s_sw(A2S_SW_gemm_f16x2) && a2s_sw(A2S_SW_gemm_bf16x3) && (!g.ep_y || g.ep_period >= 256) && g.K >= 128 && a_ok && b_ok && g.M >= 256 && g.N >= 256 &&
            (long)a2s_cdiv(g.M, 256) * a2s_cdiv(g.N, 256) * g.batch * g.splitk >= 192;
 }
 static void launch_big_two_term(const GemmArgs& g, bool akc, bool bkc, hipStream_t st) {

@@ -1,0 +1,203 @@
+// What crosses translation units inside liba2s_hip.so: every function that one .hip file defines and another calls is declared here, once.
+// Every .hip file includes this header (and through it a2s_common.h, the public include/a2s.h and the switch table a2s_switches.h).
+#pragma once
+#include "a2s_common.h"
+#include "../../include/a2s.h"
+#include "a2s_switches.h"
+
+// ---- switches that are not a plain read of the table
+// the pair loop hands over to the few-row kernels at "attn_pair_fused_rows" rows, but never above the few-row path's own limit
+static inline int a2s_attn_pair_fused_rows(void) {
+    const int cap = a2s_sw(A2S_SW_dec_fused_max_rows), v = a2s_sw(A2S_SW_attn_pair_fused_rows);
+    return v < cap ? v : cap;
+}
+// the test-hook word handed to the persistent kernels (PERSIST_DBG_* bits, a2s_common.h)
+static inline unsigned a2s_persist_dbg(void) {
+    return (a2s_sw(A2S_SW_persist_force_agent) ? PERSIST_DBG_FORCE_AGENT : 0u) | (a2s_sw(A2S_SW_persist_inject_abort) ? PERSIST_DBG_INJECT_ABORT : 0u);
+}
+
+// ---- a2s_gemm.hip
+int a2s_absmax_impl(hipStream_t st, const float* x, long n, float* out);
+size_t a2s_gemm_workspace_bytes_impl(int M, int N, int batch, int splitk);
+int a2s_gemm_pick_splitk_impl(int M, int N, int K, int batch);
+int a2s_gemm_bnstats_slots(int period);
+void a2s_gemm_debug_tile_impl(int cfg);
+int a2s_gemm_affine_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
+    const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
+    int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes,
+    const float* a_scale, const float* a_shift, int a_period, const float* b_scale, const float* b_shift, int b_period,
+    const float* ep_y, const float* ep_mean, const float* ep_invstd, const float* ep_scale, const float* ep_shift,
+    float* ep_partial, int ep_period, int two_term, const float* a_absmax, const float* b_absmax);
+int a2s_gemm_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
+    const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
+    int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes);
+
+// ---- a2s_linear.hip
+size_t a2s_linear_dgrad_ws_bytes_impl(int N, int K);
+int a2s_linear_dgrad_blocks_impl(int M);
+bool a2s_linear_dgrad_ok(int M, int N, int K, long lda, long sBk, long sBn, long ldc, int period, const void* A, const void* B, const void* C, const void* y);
+int a2s_linear_dgrad_bnstats_impl(hipStream_t st, int M, int N, int K, const float* A, long lda, const float* Wt, long sBk, long sBn, float* C, long ldc,
+    const float* ep_y, const float* mean, const float* invstd, const float* scale, const float* shift, int period,
+    float* partial, const float* a_absmax, const float* b_absmax, float* ws, size_t ws_bytes, float* c_absmax_out);
+bool a2s_linear_fwd_ok(int M, int N, int K, long lda, long ldc, int period, const void* A, const void* W, const void* C);
+int a2s_linear_fwd_impl(hipStream_t st, int M, int N, int K, const float* A, long lda, const float* W, float* C, long ldc, const float* a_scale,
+    const float* a_shift, int period, const float* a_absmax, const float* w_absmax, float* ws, size_t ws_bytes);
+size_t a2s_linear_wgrad_ws_bytes_impl(int M, int K);
+bool a2s_linear_wgrad_ok(int M, int N, int K, long ldz, long lda, long ldg, int period, const void* dz, const void* A, const void* G);
+int a2s_linear_wgrad_impl(hipStream_t st, int M, int N, int K, const float* dz, long ldz, const float* A, long lda, float* G, long ldg, const float* a_scale,
+    const float* a_shift, int period, const float* dz_absmax, const float* a_absmax, float* ws, size_t ws_bytes);
+
+// ---- a2s_conv.hip
+int a2s_act_bound_impl(hipStream_t st, const float* scale, const float* shift, const float* absmax, int C, float* out);
+size_t a2s_conv3x3_workspace_floats_impl(int Cin);
+int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale,
+    const float* in_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout, int flip, float* ws,
+    const float* yl, const float* yl_mean, const float* yl_invstd, const float* yl_scale, const float* yl_shift,
+    const float* x_absmax, const float* in_absmax, float* out_absmax);
+int a2s_conv3x3_stat_blocks_impl(int B, int T, int F, int Cin);
+int a2s_bn_finalize_impl(hipStream_t st, const float* partial, int nblocks, int C, double count, const float* gamma,
+    const float* beta, float* running_mean, float* running_var, long long* nbt, float* mean,
+    float* invstd, float* scale, float* shift, float eps, float momentum, int training);
+int a2s_bn_relu_apply_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F);
+int a2s_col_stats_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
+int a2s_bn1d_relu_dropout_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift,
+    const uint8_t* mask, float inv_keep, long n, int C);
+size_t a2s_conv3x3_wgrad_workspace_bytes_impl(int Cin, int Cout);
+int a2s_conv3x3_wgrad_impl(hipStream_t st, const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dW,
+    float* ws, size_t ws_bytes, int B, int T, int F, int Cin, int Cout, const float* bn_y, const float* bn_mean,
+    const float* bn_invstd, const float* bn_scale, const float* bn_shift, const float* bn_c12, float* dy_out,
+    const float* dy_absmax, const float* act_absmax);
+int a2s_bn_bwd_impl(hipStream_t st, const float* g, const float* x, const float* mean, const float* invstd, const float* scale,
+    const float* shift, const uint8_t* mask, float inv_keep, float* dgamma, float* dbeta, float* dx, float* partial,
+    float* c12, long rows, int C, int F, float* dx_absmax);
+int a2s_bn_bwd_from_partial_impl(hipStream_t st, const float* g, const float* x, const float* mean, const float* invstd, const float* scale,
+    const float* shift, float* dgamma, float* dbeta, float* dx, const float* partial, int nblocks, float* c12,
+    long rows, int C, int F, float* dx_absmax);
+int a2s_bn_bwd_stats_impl(hipStream_t st, const float* g, const float* x, const float* mean, const float* invstd, const float* scale,
+    const float* shift, const uint8_t* mask, float inv_keep, float* partial, float* sums, long rows, int C, int F);
+int a2s_bn_bwd_apply_impl(hipStream_t st, const float* g, const float* x, const float* mean, const float* invstd, const float* scale,
+    const float* shift, const uint8_t* mask, float inv_keep, const float* sums_local, const float* sums_global,
+    double count_global, float* dgamma, float* dbeta, float* dx, float* c12, long rows, int C, int F);
+int a2s_bn_bwd_sums_from_partial_impl(hipStream_t st, const float* partial, int nblocks, int C, float* sums);
+int a2s_bn_bwd_c12_from_sums_impl(hipStream_t st, const float* sums_local, const float* sums_global, double count_global, float* dgamma, float* dbeta,
+    float* c12, int C);
+size_t a2s_bn_bwd_partial_floats_impl(long rows, int C, int F);
+
+// ---- a2s_conv_rows.hip
+int a2s_channel_absmax_impl(hipStream_t st, const float* x, long rows, int C, int F, float* out);
+bool a2s_conv_rows_eligible(int F, int Cin);
+int a2s_conv_rows_blocks(int B, int T, int F);
+size_t a2s_conv_rows_workspace_floats(int Cin);
+int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
+    const float* in_absmax, float* stat_partial, float* out_absmax, int B, int T, int F, int Cin, int Cout, int flip,
+    float* ws, const float* yl, const float* yl_mean, const float* yl_invstd, const float* yl_scale, const float* yl_shift,
+    const float* x_absmax);
+
+// ---- a2s_conv_wrows.hip
+bool a2s_wgrad_rows_eligible(int F, int Cin, int Cout);
+int a2s_conv3x3_wgrad_rows_bn_impl(hipStream_t st, const float* g, const float* y, const float* mean, const float* invstd, const float* scale,
+    const float* shift, const float* c12, const float* g_absmax, int g_absmax_n, const float* y_absmax, float* dz_out,
+    float* dz_absmax_out, const float* x, const float* in_scale, const float* in_shift, float* dW, float* ws, size_t ws_bytes,
+    int B, int T, int F, int Cin, int Cout, const float* act_absmax);
+int a2s_conv3x3_wgrad_rows_impl(hipStream_t st, const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dW, float* ws,
+    size_t ws_bytes, int B, int T, int F, int Cin, int Cout, const float* dy_absmax, const float* act_absmax);
+
+// ---- a2s_seq.hip
+int a2s_gru_gates_fwd_impl(hipStream_t st, const float* gi, long ldgi, const float* gh, long ldgh, const float* hprev,
+    long ldhp, float* hout, long ldho, float* hout2, long ldho2, float* save, int R, int H);
+int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t, const float* dhz_in, const float* dout, long ld_dout,
+    const float* save, const float* hprev, long ld_hprev, float* dgi, long ld_dgi, float* dgh_out, float* dgh2,
+    long ld_dgh2, float* dhz_out, int R, int H);
+int a2s_skinny_gemm_acc_impl(hipStream_t st, const float* A, long lda, const float* Bt, long ldb, float* Cm, long ldc, int R, int N, int K);
+int a2s_gru_seq_fwd_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh,
+    const float* b_hh, float* out, long out_bstride, long out_tstride, float* hbuf, float* gh,
+    float* save, float* hn, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
+int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+    float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, int B, int T, int H,
+    const int* n_done, int n_rows_total, float* ws, const a2s_attn_rows* rows = nullptr, a2s_attn_deferred* defer = nullptr);
+int a2s_log_softmax_rows_impl(hipStream_t st, const float* x, long ldx, float* y, long ldy, int* argmax_out, int R, int V);
+int a2s_embed_rows_impl(hipStream_t st, const float* table, const long long* ids64, const int* ids32, long id_stride,
+    int const_id, float* out, long ldo, int col0, int R, int E, const uint8_t* drop, float inv_keep);
+int a2s_note_decoder_fwd_impl(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
+int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_args& au, const a2s_note_dec_args& al, const int* pair_order,
+    const int* pair_rank, const int* pair_n_active, int* done_u, int* done_l);
+int a2s_staff_emb_fwd_impl(hipStream_t st, const float* note_emb, const float* const* w /* 8 GRU tensors f then r */,
+    const long long* ids64, const int* ids32, long id_bstride, const long long* lengths,
+    long len_stride, float* out, long ldo, int col0, float* hsave, int R, int maxlen, int E, int S);
+size_t a2s_attn_workspace_floats_impl(int B, int T, int H, int groups);
+size_t a2s_attn_bulk_lds(size_t shm, int n_active, int backward);
+long a2s_attn_pair_launches(void);
+
+// ---- a2s_bwd.hip
+int a2s_log_softmax_bwd_rows_impl(hipStream_t st, const float* g, const float* y, long outer_stride, int inner, float* dx,
+    int R, int V, int n_outer, int time_major);
+int a2s_gru_gates_bwd_impl(hipStream_t st, const float* dh_a, long lda, const float* dh_b, long ldb, const float* save,
+    const float* hprev, long ldhp, float* dgi, long ldgi, float* dgh, long ldgh, float* dgh2, long ldgh2,
+    float* dhprev, long lddp, int R, int H);
+int a2s_attn_step_bwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+    const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b,
+    long lddb, float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, int B, int T, int H, float* ws,
+    const a2s_attn_rows* rows = nullptr);
+int a2s_attn_dk_accum_impl(hipStream_t st, const float* Kmat, const float* q_all, const float* ds_all, const float* v,
+    float* dK, float* dv_partial, int B, int T, int S, int H, const int* row_until, int groups);
+int a2s_col_sum_impl(hipStream_t st, const float* x, long ld, float* out, long rows, int C, float alpha, float beta, float* ws, size_t ws_floats);
+int a2s_embed_scatter_add_impl(hipStream_t st, float* table_grad, const long long* ids64, const int* ids32, long id_stride,
+    int const_id, const float* g, long ldg, int col0, int R, int E, const uint8_t* drop, float inv_keep);
+int a2s_ew_act_bwd_impl(hipStream_t st, const float* g, const float* y, float* dx, long n, int act);
+int a2s_note_decoder_bwd_impl(hipStream_t st, const a2s_note_dec_bwd_args& a);
+int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, const int* pair_order,
+    const int* pair_rank, const int* pair_n_active);
+int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
+    long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
+    float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
+int a2s_staff_emb_bwd_impl(hipStream_t st, const float* note_emb, const float* const* w, float* const* grads_dev, float* note_emb_grad,
+    const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,
+    const float* dout, long lddo, int col0, const float* hsave, int R, int maxlen, int E, int S);
+long a2s_attn_pair_bwd_launches(void);
+
+// ---- a2s_step.hip
+size_t a2s_note_step_fused_head_floats(void);
+size_t a2s_note_step_workspace_floats_impl(int H, int E);
+int a2s_dec_mid_launches(void);
+bool a2s_dec_step_fusable(int R, int H, int E, int V, const void* const* ptrs, int nptrs, const float* ws, size_t ws_floats, bool greedy = false);
+int a2s_note_step_fused_fwd(hipStream_t st, const a2s_note_dec_args& a, int si, int so, int sv, int sv_next, int t, const int* t_base, int tf, bool last,
+    int nrows, const int* rowmap, const a2s_attn_deferred* defer = nullptr);
+int a2s_note_step_fused_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a);
+int a2s_note_step_fused_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const float* dh_in, float* dh_out, const a2s_attn_rows* rows,
+    int nrows, const int* rowmap);
+bool a2s_note_step_mid_ok(int H, int E, const void* const* ptrs, int nptrs);
+int a2s_note_step_mid_gru(hipStream_t st, const a2s_note_dec_args& a, int si, int so, int sv, int sv_next, int nrows, const int* rowmap);
+bool a2s_note_step_mid_bwd_ok(const a2s_note_dec_bwd_args& a);
+int a2s_note_step_mid_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
+int a2s_note_step_mid_bwd_query(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
+
+// ---- a2s_persist.hip
+unsigned* a2s_persist_latch_ptr(void);
+void a2s_persist_latch_set(void* p);
+a2s_device_geom a2s_device_geometry(void);
+bool a2s_gru_seq_fwd_persist_ok(const float* w_hh, const float* gi, int B, int T, int H, float* ws, size_t ws_bytes);
+int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh, const float* b_hh, float* out,
+    long out_bstride, long out_tstride, float* save, float* hn, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
+bool a2s_gru_seq_bwd_persist_ok(int B, int T, int H, float* ws, size_t ws_bytes, size_t ws_used);
+int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
+    const float* gates, const float* w_hh_t, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first, int B, int T,
+    int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes);
+
+// ---- a2s_dec_persist.hip
+int a2s_dec_persist_launches(void);
+bool a2s_note_decoder_fwd_persist_ok(const a2s_note_dec_args& a);
+int a2s_note_decoder_fwd_persist(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
+bool a2s_note_decoder_bwd_persist_ok(const a2s_note_dec_bwd_args& a);
+int a2s_note_decoder_bwd_persist(hipStream_t st, const a2s_note_dec_bwd_args& a);
+
+// ---- a2s_opt.hip
+int a2s_nll_loss_impl(hipStream_t st, const float* logp, const long long* target, long rows, int V, long long ignore_index,
+    float* loss_out /* 2 floats */, float* dlogp /* zero-filled or null */, float gscale, double* partial, int nblocks);
+int a2s_nll_grad_impl(hipStream_t st, float* dlogp, const long long* target, const float* loss_out, float gscale, long rows, int V, long long ignore_index);
+int a2s_clip_adadelta_impl(hipStream_t st, float* params, float* grads, float* square_avg, float* acc_delta, long n, const float* loss,
+    float max_norm, float lr, float rho, float eps, float* ctl /* 3 floats */, double* partial, int nblocks, int zero_grad);
+
+// ---- a2s_vqt.hip
+int a2s_vqt_logmag_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db);
+int a2s_vqt_decimate_impl(hipStream_t st, const float* ypad, long plen, const float* taps, int ntaps, float* out, long n_out, int B);
+int a2s_vqt_logmag_octaves_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, int bpo, float top_db);

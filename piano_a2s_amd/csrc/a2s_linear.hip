@@ -21,8 +21,7 @@
 // per instruction (PMC: 25.6 GB fetched = y4 + dz, the B fragments are L2 hits: 722 M hits against 392 M misses; non-temporal stores wrote
 // 32.7 GB for 23.6 GB of output, plain stores the exact bytes: hence plain).  Wave priorities or a start-up stagger between the two waves of
 // a SIMD change nothing.
-#include "a2s_common.h"
-#include "../../include/a2s.h"
+#include "a2s_internal.h"
 
 #define LIN_BM 128
 #define LIN_K 256

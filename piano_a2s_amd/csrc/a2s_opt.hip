@@ -4,7 +4,7 @@
 //   * gradient-norm clipping (SpeechBrain check_gradients -> clip_grad_norm_(5.0)) fused with
 //     Adadelta(lr, rho, eps) -- reference ASR.fit_batch pretrain.py:125-128, hparams/pretrain.yaml:44-47 --
 //     over ONE flat parameter / gradient / state buffer, fully on the device (no host sync, skip on non-finite).
-#include "a2s_common.h"
+#include "a2s_internal.h"
 
 // per-block partial: sum of -logp[target] and count of valid targets for rows [r0, r1)
 __global__ __launch_bounds__(256) void nll_partial(const float* __restrict__ logp, const long long* __restrict__ target, long rows, int V,

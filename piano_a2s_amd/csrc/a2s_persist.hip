@@ -24,8 +24,7 @@
 //
 // Residency: grid = (H / 16) x ceil(B / 16) workgroups of 256 threads (B = 256: 256 workgroups, one per CU; two directions run side by
 // side on two streams: 2 per CU), ~110 VGPRs, 2.3 KB of LDS -- far inside what a CU admits, so every workgroup of a launch is resident.
-#include "a2s_common.h"
-#include "../../include/a2s.h"
+#include "a2s_internal.h"
 
 typedef unsigned long long u64;
 typedef __attribute__((address_space(1))) u64 gu64;
@@ -365,14 +364,8 @@ __global__ __launch_bounds__(256, 2) void gru_seq_bwd_persist(GruPersistBwd a) {
 }
 
 // ------------------------------------------------------------------------------------------- launchers
-static int g_gru_persist = -1;                          // A2S_GRU_PERSIST=0 / a2s_debug_set("gru_persist", 0): the launch-per-step kernels
-void a2s_gru_persist_set(int v) { g_gru_persist = v ? 1 : 0; }
-int a2s_gru_persist_enabled(void) {
-    if (g_gru_persist < 0) { const char* e = getenv("A2S_GRU_PERSIST"); g_gru_persist = (e && e[0] == '0') ? 0 : 1; }
-    return g_gru_persist;
-}
 // workspace bytes the persistent recurrences need (granule buffers + abort word); 0: shape not supported
-size_t a2s_gru_persist_ws_bytes(int B, int H, int bwd) {
+static size_t a2s_gru_persist_ws_bytes(int B, int H, int bwd) {
     if (H != 256 || B < 1) return 0;
     const size_t rb = (size_t)(B + 15) / 16;
     return 256 + ((rb * 16 * sizeof(unsigned) + 255) & ~(size_t)255) + sizeof(u64) * 2 * rb * 16 * (size_t)(bwd ? 3 * H : H);
@@ -384,12 +377,8 @@ size_t a2s_gru_persist_ws_bytes(int B, int H, int bwd) {
 // here; that case ends in a bounded-wait abort, which sets the process-wide latch, and the host then switches the persistent paths off
 // (piano_a2s_amd/hip.py check_persist_abort).
 static unsigned* g_abort_latch = nullptr;
-static unsigned g_persist_dbg = 0;
 unsigned* a2s_persist_latch_ptr(void) { return g_abort_latch; }
 void a2s_persist_latch_set(void* p) { g_abort_latch = reinterpret_cast<unsigned*>(p); }
-unsigned a2s_persist_dbg(void) { return g_persist_dbg; }
-void a2s_persist_dbg_set(unsigned bit, int on) { g_persist_dbg = on ? (g_persist_dbg | bit) : (g_persist_dbg & ~bit); }
-int a2s_persist_dbg_get(unsigned bit) { return (g_persist_dbg & bit) ? 1 : 0; }
 a2s_device_geom a2s_device_geometry(void) {
     static a2s_device_geom cache[16];
     static bool have[16];
@@ -413,18 +402,15 @@ static int persist_blocks_per_cu(K kernel) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0) != hipSuccess) { (void)hipGetLastError(); n = 0; }
     return n;
 }
-static int g_gru_persist_alone = 0;      // a2s_debug_set("gru_persist_alone", 1): the host runs the directions of a layer one after the other
-void a2s_gru_persist_alone_set(int v) { g_gru_persist_alone = v ? 1 : 0; }
-int a2s_gru_persist_alone(void) { return g_gru_persist_alone; }
 static bool persist_fits(int B, int H, bool bwd) {
     static int occ[2] = {-1, -1};
     if (occ[bwd] < 0) occ[bwd] = bwd ? persist_blocks_per_cu(gru_seq_bwd_persist<256>) : persist_blocks_per_cu(gru_seq_fwd_persist<256>);
     const a2s_device_geom g = a2s_device_geometry();
-    return (g_gru_persist_alone ? 1L : 2L) * (H / 16) * ((B + 15) / 16) <= (long)g.cus * occ[bwd];
+    return (a2s_sw(A2S_SW_gru_persist_alone) ? 1L : 2L) * (H / 16) * ((B + 15) / 16) <= (long)g.cus * occ[bwd];
 }
 
 bool a2s_gru_seq_fwd_persist_ok(const float* w_hh, const float* gi, int B, int T, int H, float* ws, size_t ws_bytes) {
-    return a2s_gru_persist_enabled() && H == 256 && T >= 2 && persist_fits(B, H, false) && ws && ((uintptr_t)ws % 256 == 0) && ws_bytes >= a2s_gru_persist_ws_bytes(B, H, 0) &&
+    return a2s_sw(A2S_SW_gru_persist) && H == 256 && T >= 2 && persist_fits(B, H, false) && ws && ((uintptr_t)ws % 256 == 0) && ws_bytes >= a2s_gru_persist_ws_bytes(B, H, 0) &&
            ((uintptr_t)w_hh % 16 == 0) && gi;
 }
 int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh, const float* b_hh, float* out,
@@ -438,14 +424,14 @@ int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bs
     const size_t xcc_bytes = ((size_t)nrb * 16 * sizeof(unsigned) + 255) & ~(size_t)255;
     GruPersistFwd a{gi_all, gi_bstride, gi_tstride, w_hh, b_hh, out, out_bstride, out_tstride, save, hn,
                     reinterpret_cast<u64*>(base + 256 + xcc_bytes), reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + 256), B, T, reverse, nrb,
-                    g_abort_latch, g_persist_dbg};
+                    g_abort_latch, a2s_persist_dbg()};
     hipLaunchKernelGGL(gru_seq_fwd_persist<256>, dim3((H / 16) * nrb), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_seq_fwd_persist");
     return A2S_OK;
 }
 
 bool a2s_gru_seq_bwd_persist_ok(int B, int T, int H, float* ws, size_t ws_bytes, size_t ws_used) {
-    return a2s_gru_persist_enabled() && H == 256 && T >= 2 && persist_fits(B, H, true) && ws && ((uintptr_t)ws % 256 == 0) && ws_used % 256 == 0 &&
+    return a2s_sw(A2S_SW_gru_persist) && H == 256 && T >= 2 && persist_fits(B, H, true) && ws && ((uintptr_t)ws % 256 == 0) && ws_used % 256 == 0 &&
            ws_bytes >= ws_used + a2s_gru_persist_ws_bytes(B, H, 1);
 }
 // ws_off: bytes at the start of the workspace the caller keeps (W_hh^T)
@@ -461,7 +447,7 @@ int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstr
     const size_t xcc_bytes = ((size_t)nrb * 16 * sizeof(unsigned) + 255) & ~(size_t)255;
     GruPersistBwd a{dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, w_hh_t, dhn, dgi_all, dgh_shift, dgh_first,
                     reinterpret_cast<u64*>(base + 256 + xcc_bytes), reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + 256), B, T, reverse, nrb,
-                    g_abort_latch, g_persist_dbg};
+                    g_abort_latch, a2s_persist_dbg()};
     hipLaunchKernelGGL(gru_seq_bwd_persist<256>, dim3((H / 16) * nrb), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_seq_bwd_persist");
     return A2S_OK;

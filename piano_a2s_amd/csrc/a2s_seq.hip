@@ -7,12 +7,7 @@
 //   energy = tanh(W [h ; enc_t] + b) = tanh(W_h h + b  +  W_e enc_t) = tanh(q + K_t)
 // K = enc W_e^T is step-invariant and computed once per layer by the GEMM; per step only
 // q (a skinny GEMM), the score/softmax and the context remain -- one pass over K and one over enc.
-#include "a2s_common.h"
-#include "../../include/a2s.h"
-
-int a2s_gemm_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
-                  const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
-                  int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes);
+#include "a2s_internal.h"
 
 // ------------------------------------------------------------------------------------------- GRU cell
 // PyTorch packing [r; z; n].  gi = W_ih x + b_ih, gh = W_hh h + b_hh (both (R, 3H), row strides given).
@@ -244,17 +239,7 @@ int a2s_skinny_gemm_acc_impl(hipStream_t st, const float* A, long lda, const flo
     return A2S_OK;
 }
 
-static int g_gru_fused = -1;                                 // a2s_debug_set("gru_fused", 0): the three-launch step (A/B measurements)
-void a2s_gru_step_fused_set(int v) { g_gru_fused = v ? 1 : 0; }
-bool a2s_gru_step_fused_enabled(void) {
-    if (g_gru_fused < 0) g_gru_fused = 1;
-    return g_gru_fused != 0;
-}
-static bool gru_step_fusable(const float* w_hh, int H) { return a2s_gru_step_fused_enabled() && H % 16 == 0 && ((uintptr_t)w_hh % 16 == 0); }
-
-bool a2s_gru_seq_fwd_persist_ok(const float* w_hh, const float* gi, int B, int T, int H, float* ws, size_t ws_bytes);
-int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh, const float* b_hh, float* out,
-                                 long out_bstride, long out_tstride, float* save, float* hn, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
+static bool gru_step_fusable(const float* w_hh, int H) { return a2s_sw(A2S_SW_gru_fused) && H % 16 == 0 && ((uintptr_t)w_hh % 16 == 0); }
 
 // One direction of one encoder GRU layer over all T steps (h0 = 0).
 //   gi_all : (B, T, 3H) = x W_ih^T + b_ih for this direction (row stride ld_gi between time steps of a clip)
@@ -356,13 +341,10 @@ __global__ __launch_bounds__(256) void attn_step_fwd(const float* __restrict__ K
     }
 }
 
-int a2s_attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+static int attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                                  float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, float* ws, int B, int T, int H,
                                  const int* n_done, int n_rows_total, const a2s_attn_rows* rows, a2s_attn_deferred* defer = nullptr);
 
-int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
-                           float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, int B, int T, int H,
-                           const int* n_done, int n_rows_total, float* ws, const a2s_attn_rows* rows = nullptr, a2s_attn_deferred* defer = nullptr);
 // rows (optional, split kernels only): which rows are computed and how they group by clip -- see a2s_attn_rows.  Used by the fused
 // training step: once a row's remaining targets are all <pad> nothing that reaches the loss depends on it any more.
 int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
@@ -370,7 +352,7 @@ int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, 
                            const int* n_done, int n_rows_total, float* ws, const a2s_attn_rows* rows, a2s_attn_deferred* defer) {
     if (defer) defer->G = 0;
     if (H == 256 && ws)
-        return a2s_attn_step_fwd_split_impl(st, Kmat, enc, q, ldq, v, ctx, ldctx, ctx2, ldctx2, attw, ws, B, T, H, n_done, n_rows_total, rows, defer);
+        return attn_step_fwd_split_impl(st, Kmat, enc, q, ldq, v, ctx, ldctx, ctx2, ldctx2, attw, ws, B, T, H, n_done, n_rows_total, rows, defer);
     // one-workgroup-per-row kernels: every row is computed (no skipping); fused bars only change which clip a row reads
     const int n_clips = rows ? rows->n_clips : B;
     const size_t shm = (((T + 3) & ~3) + 16) * sizeof(float);
@@ -453,7 +435,7 @@ __global__ __launch_bounds__(256) void note_step_finalize(StepFinArgs a) {
     }
 }
 
-int a2s_note_step_finalize_impl(hipStream_t st, const StepFinArgs& a) {
+static int a2s_note_step_finalize_impl(hipStream_t st, const StepFinArgs& a) {
     hipLaunchKernelGGL(note_step_finalize, dim3(a2s_cdiv(a.R, 4)), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("note_step_finalize");
     return A2S_OK;
@@ -515,22 +497,15 @@ int a2s_embed_rows_impl(hipStream_t st, const float* table, const long long* ids
 // no-op once n_done == R, and the host polls n_done every `poll` steps to stop launching.
 typedef a2s_note_dec_args NoteDecArgs;   // one definition only: the public C struct (include/a2s.h)
 
-bool a2s_dec_step_fusable(int R, int H, int E, int V, const void* const* ptrs, int nptrs, const float* ws, size_t ws_floats, bool greedy = false);
-int a2s_note_step_fused_fwd(hipStream_t st, const a2s_note_dec_args& a, int si, int so, int sv, int sv_next, int t, const int* t_base, int tf, bool last,
-                            int nrows, const int* rowmap, const a2s_attn_deferred* defer = nullptr);
-bool a2s_note_step_mid_ok(int H, int E, const void* const* ptrs, int nptrs);
-int a2s_note_step_mid_gru(hipStream_t st, const a2s_note_dec_args& a, int si, int so, int sv, int sv_next, int nrows, const int* rowmap);
 // rows the fused step of step t would cover: all R, or (training, finished rows skipped) the rows still running, a prefix of row_list
 // both staves' sweeps of a step in one launch (round 6, further down): the pair's clip bookkeeping at this step and the geometry its partials use
 struct AttnPairStep { const int* clip_order; const int* clip_rank; int n_clips; int n_active; int step; int G; int chunk; };
 static int attn_pair_sweep(hipStream_t st, const NoteDecArgs& au, const NoteDecArgs& al, int sv, AttnPairStep& p);
 static int attn_pair_combine(hipStream_t st, const NoteDecArgs& a, int si, int sv, const AttnPairStep& p);
-int a2s_attn_pair_enabled(void);
 static int note_step_rows(const NoteDecArgs& a, int t) { return (a.row_list && a.n_rows_active && t >= 0) ? a.n_rows_active[t] : a.R; }
 // inside the pair loop (a2s_note_decoder_fwd_pair_impl) the few-row kernels take over later: at a2s_debug_set("attn_pair_fused_rows") rows (32) instead of
 // "dec_fused_max_rows" (192) -- above that, a lockstep step with its shared sweep beats two few-row steps (192 -> 64: +1.2 ms per step, 64 -> 32: +2.2, 32 -> 16: +0.1,
 // never: -16.8; profiles/r06_pair_fused_rows_ab.txt)
-int a2s_attn_pair_fused_rows(void);
 static thread_local int t_pair_rows_limit = -1;
 struct PairRowsLimit { PairRowsLimit(int v) { t_pair_rows_limit = v; } ~PairRowsLimit() { t_pair_rows_limit = -1; } };
 static bool note_step_fusable(const NoteDecArgs& a, int t = -1) {
@@ -673,9 +648,6 @@ static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, int* 
     return A2S_OK;
 }
 
-bool a2s_note_decoder_fwd_persist_ok(const a2s_note_dec_args& a);
-int a2s_note_decoder_fwd_persist(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
-
 // Tail steps on the few-row kernels write only the rows still running.  What the backward pass reads of the others (operands of its
 // weight-gradient products over all rows and steps, the saved gates) must be finite: everything behind slot 0 starts as zeros
 // (~6 GB per training step at B = 256, ~1.3 ms; issued here and not by the Python host: see engine.Engine._decode_staff).
@@ -730,7 +702,7 @@ int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const NoteDec
                                    const int* pair_rank, const int* pair_n_active, int* done_u, int* done_l) {
     const NoteDecArgs* as[2] = {&au, &al};
     hipStream_t sts[2] = {su, sl};
-    const bool can_pair = a2s_attn_pair_enabled() && su != sl && pair_order && pair_rank && pair_n_active && au.gt && al.gt && au.n_active && al.n_active &&
+    const bool can_pair = a2s_sw(A2S_SW_attn_pair) && su != sl && pair_order && pair_rank && pair_n_active && au.gt && al.gt && au.n_active && al.n_active &&
                           au.n_clips > 0 && au.n_clips == al.n_clips && au.R == al.R && au.T == al.T && au.H == 256 && al.H == 256 && au.enc == al.enc &&
                           au.attn_ws && al.attn_ws && !a2s_note_decoder_fwd_persist_ok(au) && !a2s_note_decoder_fwd_persist_ok(al) &&
                           note_step_mid(au, nullptr) && note_step_mid(al, nullptr);
@@ -779,12 +751,6 @@ int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const NoteDec
 }
 
 // ------------------------------------------------------------------------------------------- staff embedding
-static int g_staff_emb_fast = -1;       // the E = 16, S = 32 kernels (a2s_debug_set("staff_emb_fast", 0): the generic ones)
-void a2s_staff_emb_fast_set(int v) { g_staff_emb_fast = v ? 1 : 0; }
-int a2s_staff_emb_fast_enabled(void) {
-    if (g_staff_emb_fast < 0) g_staff_emb_fast = 1;
-    return g_staff_emb_fast;
-}
 // reference get_staff_token_* (models.py:164-189): packed bi-GRU (E -> S) final states.  One workgroup per
 // (row, direction); the 3S x (E+S) weights live in LDS and the whole (<= 398 step) recurrence runs in-kernel.
 // ids come as int32 (argmax buffer) or int64 (ground truth).  Saves per-step h for the backward pass.
@@ -916,7 +882,7 @@ int a2s_staff_emb_fwd_impl(hipStream_t st, const float* note_emb, const float* c
                            const long long* ids64, const int* ids32, long id_bstride, const long long* lengths,
                            long len_stride, float* out, long ldo, int col0, float* hsave, int R, int maxlen, int E, int S) {
     A2S_REQUIRE((ids64 != nullptr) != (ids32 != nullptr), "staff_emb_fwd: exactly one of ids64/ids32");
-    if (E == 16 && S == 32 && a2s_staff_emb_fast_enabled()) {
+    if (E == 16 && S == 32 && a2s_sw(A2S_SW_staff_emb_fast)) {
         const size_t shm16 = sizeof(float) * (E + S + 6 * S) + sizeof(int) * (size_t)maxlen;
         hipLaunchKernelGGL(staff_emb_fwd_e16s32, dim3(R, 2), dim3(192), shm16, st, note_emb, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7],
                            ids64, ids32, id_bstride, lengths, len_stride, out, ldo, col0, hsave, maxlen);
@@ -1516,19 +1482,6 @@ __global__ __launch_bounds__(512) void attn_fwd_split256_deep(const float* __res
         if (tid == 0) { pout[0] = mj[j]; pout[1] = lj[j]; }
     }
 }
-static int g_attn_deep = -1;
-void a2s_attn_deep_set(int v) { g_attn_deep = v < 0 ? 0 : v; }
-int a2s_attn_deep_max_clips(void) {
-    if (g_attn_deep < 0) g_attn_deep = 24;          // launches over at most this many active clips (a2s_debug_set("attn_deep", n))
-    return g_attn_deep;
-}
-// Combine of the few-clip training launches folded into the GRU step (a2s_debug_set("attn_defer_combine", 0): off)
-static int g_attn_defer = -1;
-void a2s_attn_defer_combine_set(int v) { g_attn_defer = v ? 1 : 0; }
-int a2s_attn_defer_combine_enabled(void) {
-    if (g_attn_defer < 0) g_attn_defer = 1;
-    return g_attn_defer;
-}
 template <int NQ>
 static void launch_fwd_deep(hipStream_t st, int nwg, const float* Kmat, const float* enc, const float* q, long ldq, const float* v, float* ws, float* attw,
                             int T, int G, int chunk, const a2s_attn_rows& r) {
@@ -1570,22 +1523,6 @@ size_t a2s_attn_workspace_floats_impl(int B, int T, int H, int groups) {
     return A2S_ATTN_TICKETS + rows * (groups > 0 ? groups : 1) * (2 * H + 4);
 }
 
-// Fused combine (OFF by default; a2s_debug_set("attn_fused_combine", 1)): the split kernels' last-arriving
-// workgroup per clip merges the partials, no separate combine launch.  Parity-tested, and measured SLOWER in the training step (632 ->
-// 692 ms): every one of the ~770 workgroups of a launch pays a device-scope release (L2 write-back) before its ticket and the last one
-// an acquire (L2 invalidate) -- on an 8-XCD part that costs more than the 7 us launch it saves and evicts the other streams' lines.
-static int g_attn_fused_combine = -1;
-void a2s_attn_fused_combine_set(int v) { g_attn_fused_combine = v < 0 ? 0 : v; }      // 0 never, 1 always, n >= 2: launches over at most n clips
-int a2s_attn_fused_combine_enabled(void) {
-    if (g_attn_fused_combine < 0) g_attn_fused_combine = 0;
-    return g_attn_fused_combine;
-}
-static int g_attn_nt = -1;
-void a2s_attn_nt_set(int v) { g_attn_nt = v < 0 ? 0 : v; }
-int a2s_attn_nt_enabled(void) {
-    if (g_attn_nt < 0) g_attn_nt = 64;      // launches over >= 64 clips
-    return g_attn_nt;
-}
 // Occupancy cap of the bulk launches.  A launch over >= 64 clips asks for at least this much LDS -- 64 KB forward (2 workgroups per CU),
 // 32 KB backward (5) -- although its kernel needs ~2-3 KB: the loaded HBM latency that every OTHER kernel on the chip sees goes with the
 // bytes the bulk launches keep in flight (8 workgroups x 256 lanes x several 16-byte loads per CU = ~30 MB against the ~6 MB that saturate the
@@ -1596,11 +1533,8 @@ int a2s_attn_nt_enabled(void) {
 // (a2s_debug_set("attn_bulk_cap", 1); off by default: greedy decoding of 256 clips 495 -> 468 clips/s with it).  The sizes were swept in rounds 4-6
 // (profiles/r04_attn_occupancy_cap.txt, r05_prefix_percent.txt, r06_cap_sweep.txt: flat within +-2 ms around these values; ONE forward workgroup
 // per CU -- 80 KB and more -- loses 5-10 ms).
-static int g_attn_bulk_cap = 0;
-void a2s_attn_bulk_cap_set(int on) { g_attn_bulk_cap = on > 0 ? 1 : 0; }
-int a2s_attn_bulk_cap_enabled(void) { return g_attn_bulk_cap; }
 size_t a2s_attn_bulk_lds(size_t shm, int n_active, int backward) {
-    if (!g_attn_bulk_cap) return shm;
+    if (!a2s_sw(A2S_SW_attn_bulk_cap)) return shm;
     // forward 64 KB: 2 workgroups per CU.  Backward 28 KB: 5 per CU with 17 KB of LDS left free on every CU -- with 5 x 32 KB the long-clip chain's
     // kernels, which all need 8-16 KB for their cross-wave reduction, could only start where a bulk workgroup had just left (round 5: 452.3 -> 449.5 ms)
     const size_t c = (backward & 1) ? 28672 : 65536;
@@ -1619,7 +1553,7 @@ static void launch_fwd_mq(hipStream_t st, int nwg, size_t shm, const float* Kmat
                             r.clip_order, r.row_until, r.step, r.n_clips, ft);
 }
 
-int a2s_attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
+static int attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
                                  float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, float* ws, int B, int T, int H,
                                  const int* n_done, int n_rows_total, const a2s_attn_rows* rows, a2s_attn_deferred* defer) {
     A2S_REQUIRE(H == 256 && ws, "attn_step_fwd_split: needs hidden_size 256 and a workspace");
@@ -1636,21 +1570,25 @@ int a2s_attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float*
     // workspace: [A2S_ATTN_TICKETS ints: arrival counters, zero between launches (the allocation must be zero-initialised once)] [partials]
     int* tickets = reinterpret_cast<int*>(ws);
     float* part = ws + A2S_ATTN_TICKETS;
+    // Fused combine (OFF by default; a2s_debug_set("attn_fused_combine", 1)): the split kernels' last-arriving
+    // workgroup per clip merges the partials, no separate combine launch.  Parity-tested, and measured SLOWER in the training step (632 ->
+    // 692 ms): every one of the ~770 workgroups of a launch pays a device-scope release (L2 write-back) before its ticket and the last one
+    // an acquire (L2 invalidate) -- on an 8-XCD part that costs more than the 7 us launch it saves and evicts the other streams' lines.
     // (mode n >= 2: only launches over at most n active clips -- the long-clip group's latency chain, where one launch and one dependent round
     // trip less per step count and the per-workgroup release is paid by a few dozen workgroups instead of ~770)
-    const int fmode = a2s_attn_fused_combine_enabled();
+    const int fmode = a2s_sw(A2S_SW_attn_fused_combine);
     const bool fused = fmode && (fmode == 1 || r.n_active <= fmode) && r.n_clips <= A2S_ATTN_TICKETS / 2;
     // fused tail: one extra workgroup per clip (row) WITHOUT unfinished rows zero-fills its outputs
     const int n_zero = fused ? r.n_clips - r.n_active : 0;
     const AttnFusedTail ft = {fused ? tickets : nullptr, ctx, ldctx, ctx2, ldctx2, r.n_active, B};
     // streaming (non-temporal) K / enc loads when many clips are active: the sweep is far larger than any cache, and the lines of a
     // concurrently decoding few-clip group (its K / enc and its weights) then survive in L2 / Infinity Cache ("attn_nt")
-    const bool nt = a2s_attn_nt_enabled() > 0 && r.n_active >= a2s_attn_nt_enabled();
+    const bool nt = a2s_sw(A2S_SW_attn_nt) > 0 && r.n_active >= a2s_sw(A2S_SW_attn_nt);
     if (r.n_active > 0 || n_zero > 0) {
         // the grid covers the clips that still have unfinished rows, re-split so that it still fills the chip
         if (r.n_active > 0) a2s_attn_split_geometry(r.n_active, T, &G, &chunk);
         const int nwg = r.n_active * G + n_zero;
-        if (!fused && !n_done && groups <= 4 && r.n_active <= a2s_attn_deep_max_clips() && chunk <= 80) {       // the few-clip form: every load of a chunk in one round trip
+        if (!fused && !n_done && groups <= 4 && r.n_active <= a2s_sw(A2S_SW_attn_deep) && chunk <= 80) {       // the few-clip form: every load of a chunk in one round trip
             // (five fused bars: the instantiation needs scratch; measured slower on the one-segment steps, which are the only ones that fuse five)
             switch (groups) {
                 case 1: launch_fwd_deep<1>(st, nwg, Kmat, enc, q, ldq, v, part, attw, T, G, chunk, r); break;
@@ -1679,7 +1617,7 @@ int a2s_attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float*
     }
     if (fused) return A2S_OK;
     // the few-clip launches of a training step leave the combine to the GRU step that consumes the contexts (a2s_step.hip: dec_gru_step_cmb)
-    if (defer && !n_done && r.n_active > 0 && r.n_active <= a2s_attn_deep_max_clips() && groups <= 4 && G <= 16 && a2s_attn_defer_combine_enabled()) {
+    if (defer && !n_done && r.n_active > 0 && r.n_active <= a2s_sw(A2S_SW_attn_deep) && groups <= 4 && G <= 16 && a2s_sw(A2S_SW_attn_defer_combine)) {
         *defer = a2s_attn_deferred{part, attw, r.clip_rank, r.row_until, G, groups, r.n_clips, r.n_active, r.step, T};
         return A2S_OK;
     }
@@ -1692,15 +1630,8 @@ int a2s_attn_step_fwd_split_impl(hipStream_t st, const float* Kmat, const float*
 // ---- the two staves' sweeps of one decode step as ONE launch (attn_fwd_split256_pair), then each staff's own combine (attn_pair_combine, on
 // that staff's stream).  rows_u / rows_l: the staves' row bookkeeping (row_until of their own); pair: clip order / rank / active count of the
 // PAIR at this step.  Both staves' partials use the pair's geometry.
-static int g_attn_pair = 1;                  // a2s_debug_set("attn_pair", 0): every staff sweeps on its own (the A/B and the parity tests)
 static long g_attn_pair_launches = 0;
-void a2s_attn_pair_set(int on) { g_attn_pair = on ? 1 : 0; }
-int a2s_attn_pair_enabled(void) { return g_attn_pair; }
 long a2s_attn_pair_launches(void) { return g_attn_pair_launches; }
-int a2s_dec_fused_max_rows(void);
-static int g_attn_pair_fused_rows = 32;
-void a2s_attn_pair_fused_rows_set(int v) { g_attn_pair_fused_rows = v; }
-int a2s_attn_pair_fused_rows(void) { const int cap = a2s_dec_fused_max_rows(); return g_attn_pair_fused_rows < cap ? g_attn_pair_fused_rows : cap; }
 
 template <int NQ>
 static void launch_fwd_pair(hipStream_t st, int nwg, size_t shm, const AttnPairSide& s0, const AttnPairSide& s1, const float* enc, long ldq, int T,
@@ -1720,7 +1651,7 @@ static int attn_pair_sweep(hipStream_t st, const NoteDecArgs& au, const NoteDecA
     a2s_attn_split_geometry(p.n_active, T, &p.G, &p.chunk);
     const AttnPairSide s0 = {au.keys, au.q + (long)sv * au.R * H, au.attn_v, au.attn_ws + A2S_ATTN_TICKETS, au.attw ? au.attw + (long)sv * au.R * T : nullptr, au.row_until};
     const AttnPairSide s1 = {al.keys, al.q + (long)sv * al.R * H, al.attn_v, al.attn_ws + A2S_ATTN_TICKETS, al.attw ? al.attw + (long)sv * al.R * T : nullptr, al.row_until};
-    const bool nt = a2s_attn_nt_enabled() > 0 && p.n_active >= a2s_attn_nt_enabled();
+    const bool nt = a2s_sw(A2S_SW_attn_nt) > 0 && p.n_active >= a2s_sw(A2S_SW_attn_nt);
     const size_t shm = a2s_attn_bulk_lds(((size_t)2 * groups * p.chunk + 16 + (size_t)2 * groups * 128 * 4) * sizeof(float), p.n_active, 2);
     const int nwg = p.n_active * p.G;
     switch (groups) {

@@ -19,22 +19,8 @@
 // of a workgroup take the 16-wide k-steps round robin and their partial tiles meet in a fixed-order tree through LDS (deterministic).
 // Used when the call has at most a2s_debug_set("dec_fused_max_rows") rows (default 192): with many rows every workgroup re-reads the weights from
 // L2 and the tiled GEMMs win again (they only run under the other staff's attention there anyway).
-#include "a2s_common.h"
+#include "a2s_internal.h"
 #include <type_traits>
-#include "../../include/a2s.h"
-
-int a2s_gemm_impl(hipStream_t st, int M, int N, int K, float alpha, const float* A, long sAm, long sAk,
-                  const float* B, long sBk, long sBn, float beta, float* C, long ldc, const float* bias, int act,
-                  int batch, long bsA, long bsB, long bsC, int splitk, float* ws, size_t ws_bytes);
-int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
-                           float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, int B, int T, int H, const int* n_done, int n_rows,
-                           float* ws, const a2s_attn_rows* rows, a2s_attn_deferred* defer = nullptr);
-int a2s_attn_step_bwd_impl(hipStream_t st, const float* Kmat, const float* enc, const float* q, long ldq, const float* v,
-                           const float* attw, const float* ctx, long ldctx, const float* dctx_a, long ldda, const float* dctx_b, long lddb,
-                           float* dctx_out, long lddo, float* dq, long lddq, float* ds_out, int B, int T, int H, float* ws, const a2s_attn_rows* rows);
-int a2s_gru_gates_bwd_impl(hipStream_t st, const float* dh_a, long lda, const float* dh_b, long ldb, const float* save,
-                           const float* hprev, long ldhp, float* dgi, long ldgi, float* dgh, long ldgh, float* dgh2, long ldgh2,
-                           float* dhprev, long lddp, int R, int H);
 
 #define NW 8                      // waves per workgroup
 // k-steps of operand loads a wave has in flight at a time in the few-row kernels (the CH argument of mfma_rows8): a wave's share of the k-steps is
@@ -877,17 +863,6 @@ __global__ void transpose_ld(const float* __restrict__ in, long ld, float* __res
 }
 
 // ------------------------------------------------------------------------------------------- switches / eligibility
-static int g_dec_fused = -1, g_dec_fused_max_rows = -1;
-void a2s_dec_fused_set(int v) { g_dec_fused = v ? 1 : 0; }
-void a2s_dec_fused_max_rows_set(int v) { g_dec_fused_max_rows = v; }
-int a2s_dec_fused_enabled(void) {
-    if (g_dec_fused < 0) { const char* e = getenv("A2S_DEC_FUSED"); g_dec_fused = (e && e[0] == '0') ? 0 : 1; }      // (documented fallback: INTEGRATION.md)
-    return g_dec_fused;
-}
-int a2s_dec_fused_max_rows(void) {
-    if (g_dec_fused_max_rows < 0) g_dec_fused_max_rows = 192;
-    return g_dec_fused_max_rows;
-}
 // scratch layout (floats): [16: flags | FUSED_MAX_RB: tickets | max_rows x 176: logits] then [W_ih^T | W_hh^T | W_h^T] for the backward
 #define FUSED_MAX_ROWS_CAP 2048
 #define FUSED_HEAD (16 + FUSED_MAX_ROWS_CAP / 16 + (long)FUSED_MAX_ROWS_CAP * 16 * NTV)
@@ -900,18 +875,15 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // The mid-size kernels (dec_gru_mid, dec_bwd_mid: 64-row workgroups, weights staged through LDS) take the launches over more than 160 rows --
 // below that the 16-row kernels fill the chip better (32-33 column tiles x rows / 16 workgroups).  a2s_debug_set("dec_mid", 0): never (A/B
 // measurements, tests: the bulk calls' per-step products then run as library-style launches, the few-row path on the 16-row kernels only).
-static int g_dec_mid = 1;
-void a2s_dec_mid_set(int v) { g_dec_mid = v ? 1 : 0; }
-int a2s_dec_mid_enabled(void) { return g_dec_mid; }
 static int g_dec_mid_launches = 0;          // dec_gru_mid / dec_bwd_mid launches of this process (tests: proof of the path taken)
 int a2s_dec_mid_launches(void) { return g_dec_mid_launches; }
-static bool dec_use_mid(int nrows, int H2) { return g_dec_mid && nrows > 160 && H2 % MID_KC == 0; }
+static bool dec_use_mid(int nrows, int H2) { return a2s_sw(A2S_SW_dec_mid) && nrows > 160 && H2 % MID_KC == 0; }
 // greedy: the call is a greedy decode (no ground truth, no backward).  There the 4-launch step wins at every batch size the workspace admits
 // (B = 256: 497 -> 536 clips/s, B = 64: 313 -> 317, profiles/r05_infer_variants.txt) -- one stream decodes a staff, nothing runs beside it that
-// the weight re-reads of the 16-row tiles could disturb -- so the row limit of the training path (a2s_dec_fused_max_rows) does not apply.
+// the weight re-reads of the 16-row tiles could disturb -- so the row limit of the training path ("dec_fused_max_rows") does not apply.
 bool a2s_dec_step_fusable(int R, int H, int E, int V, const void* const* ptrs, int nptrs, const float* ws, size_t ws_floats, bool greedy) {
-    const int max_rows = greedy ? FUSED_MAX_ROWS_CAP : a2s_dec_fused_max_rows();
-    if (!a2s_dec_fused_enabled() || R > max_rows || R > FUSED_MAX_ROWS_CAP || !ws || ws_floats < a2s_note_step_workspace_floats_impl(H, E)) return false;
+    const int max_rows = greedy ? FUSED_MAX_ROWS_CAP : a2s_sw(A2S_SW_dec_fused_max_rows);
+    if (!a2s_sw(A2S_SW_dec_fused) || R > max_rows || R > FUSED_MAX_ROWS_CAP || !ws || ws_floats < a2s_note_step_workspace_floats_impl(H, E)) return false;
     if (H % 16 || E % 16 || (V + 15) / 16 != NTV || !aligned16(ws)) return false;
     for (int i = 0; i < nptrs; ++i) if (!aligned16(ptrs[i])) return false;
     return true;
@@ -1014,11 +986,11 @@ int a2s_note_step_fused_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int 
 
 
 // ------------------------------------------------------------------------------------------- the bulk calls' steps on the mid-size kernels (round 6)
-// A decoder call over more rows than the few-row path takes (a2s_dec_fused_max_rows) keeps its launch-per-step loop (a2s_seq.hip / a2s_bwd.hip: query
+// A decoder call over more rows than the few-row path takes ("dec_fused_max_rows") keeps its launch-per-step loop (a2s_seq.hip / a2s_bwd.hip: query
 // and output products, attention, epilogue as library-style launches), but its GRU cell -- two products + the gate kernel -- is ONE dec_gru_mid
 // launch behind the attention, and the reverse loop's dx / dh products ONE dec_bwd_mid launch in front of it.
 bool a2s_note_step_mid_ok(int H, int E, const void* const* ptrs, int nptrs) {
-    if (!g_dec_mid || H % MID_KC || E % 16) return false;          // (K = 2H, 4H, 6H and H are walked in 64-wide chunks)
+    if (!a2s_sw(A2S_SW_dec_mid) || H % MID_KC || E % 16) return false;          // (K = 2H, 4H, 6H and H are walked in 64-wide chunks)
     for (int i = 0; i < nptrs; ++i) if (!aligned16(ptrs[i])) return false;
     return true;
 }

@@ -3,7 +3,7 @@
 // (A(n, m) = y[n*hop + m], a Hankel view expressed with the GEMM's row stride = hop), B is the precomputed kernel bank
 // [taps][2*bins] (real | imaginary parts, each bin's Hann-windowed complex exponential centred in the tap axis), C = (frames, 2*bins).
 // This file turns C into the network input: magnitude -> dB relative to the clip maximum (floor 1e-5, top_db 80) -> /80 + 1 in [0,1].
-#include "a2s_common.h"
+#include "a2s_internal.h"
 
 // per-block maximum of |C| over one clip's rows; partial[b][blk]
 __global__ __launch_bounds__(256) void vqt_mag_max(const float* __restrict__ C, float* __restrict__ partial, long rows, int bins, int blocks_per_clip) {

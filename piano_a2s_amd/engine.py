@@ -758,7 +758,7 @@ class Engine:
             # per step, and the step from 514 to 540 ms (profiles/r04_dec_persist_beside_bulk.txt).
             alone = len(clip_groups) == 1 or _PERSIST_BESIDE
             persist_g = (Bg <= 8 and gidx == len(clip_groups) - 1 and alone and H == 256 and E == 16 and (plan is not None or (inference and not greedy_graph))
-                         and _os.environ.get("A2S_DEC_PERSIST", "1") != "0")
+                         and hip.lib().a2s_debug_get(b"dec_persist") != 0)
             concurrent_g = concurrent and staves_concurrent(gidx, len(clip_groups)) and not persist_g
             streams = staff_streams(dev, gidx) if concurrent_g else None
 

@@ -53,28 +53,29 @@ def lib():
         if not os.path.exists(LIB):
             raise A2SError(f"HIP extension not built: {LIB} is missing (run `python __graft_entry__.py build`). "
                            "There is no CPU fallback for the transcription hot path.")
-        _lib = C.CDLL(LIB)
-        _lib.a2s_last_error.restype = C.c_char_p
-        _lib.a2s_launch_count.restype = C.c_longlong
-        for fn in ("a2s_note_step_workspace_floats", "a2s_note_decoder_persist_ws_bytes", "a2s_note_decoder_bwd_persist_ws_bytes", "a2s_linear_dgrad_ws_bytes", "a2s_linear_wgrad_ws_bytes", "a2s_gemm_workspace_bytes", "a2s_bn_bwd_partial_floats", "a2s_conv3x3_wgrad_workspace_bytes", "a2s_attn_workspace_floats", "a2s_attn_workspace_floats_fused",
-                   "a2s_conv3x3_workspace_floats"):
-            getattr(_lib, fn).restype = C.c_size_t
         # A2S_ARITH: the arithmetic of the dense contractions -- "f16x2" (default: two exact fp16 terms per fp32 operand, three
         # products), "bf16x3" (rounds 1-2: three bf16 terms, six products) or "f32" (fp32-input matrix instructions / vector FMAs); per-kernel keys:
         # a2s_debug_set("conv_f16x2" | "wgrad_f16x2" | "gemm_f16x2" | "conv_bf16x3" | "gemm_bf16x3" | "wgrad_bf16x3", n)
         arith = os.environ.get("A2S_ARITH", "f16x2")
         if arith not in ("f16x2", "bf16x3", "f32"):
             raise A2SError(f"A2S_ARITH={arith!r}: expected f16x2, bf16x3 or f32")
+        L = C.CDLL(LIB)
+        L.a2s_last_error.restype = C.c_char_p
+        L.a2s_launch_count.restype = C.c_longlong
+        for fn in ("a2s_note_step_workspace_floats", "a2s_note_decoder_persist_ws_bytes", "a2s_note_decoder_bwd_persist_ws_bytes", "a2s_linear_dgrad_ws_bytes", "a2s_linear_wgrad_ws_bytes", "a2s_gemm_workspace_bytes", "a2s_bn_bwd_partial_floats", "a2s_conv3x3_wgrad_workspace_bytes", "a2s_attn_workspace_floats", "a2s_attn_workspace_floats_fused",
+                   "a2s_conv3x3_workspace_floats"):
+            getattr(L, fn).restype = C.c_size_t
+        # the library has read the variables that override a switch's default itself (csrc/a2s_switches.h: the documented fallbacks of INTEGRATION.md)
+        # (a build from before that call -- A2S_LIB, tools/lib_ab.sh -- reads them lazily and has nothing to report)
+        if hasattr(L, "a2s_env_check") and L.a2s_env_check() != 0:
+            raise A2SError(L.a2s_last_error().decode())
         if arith != "f16x2":
             for key in (b"conv_f16x2", b"wgrad_f16x2", b"gemm_f16x2"):
-                _lib.a2s_debug_set(key, 0)
+                L.a2s_debug_set(key, 0)
         if arith == "f32":
             for key in (b"conv_bf16x3", b"gemm_bf16x3", b"wgrad_bf16x3"):
-                _lib.a2s_debug_set(key, 0)
-        # documented fallbacks: the row-streaming convolutions, the few-row decoder path, the persistent note decoder
-        for env, key in (("A2S_CONV_ROWS", b"conv_rows"), ("A2S_DEC_FUSED", b"dec_fused"), ("A2S_DEC_PERSIST", b"dec_persist")):
-            if os.environ.get(env):
-                _lib.a2s_debug_set(key, int(os.environ[env]))
+                L.a2s_debug_set(key, 0)
+        _lib = L          # published only once it is fully configured: a failed first call leaves nothing half-made behind
     return _lib
 
 
