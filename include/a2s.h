@@ -431,6 +431,18 @@ int a2s_vqt_logmag_octaves(void* stream, const float* C, float* out, float* part
  * padded_len >= 2 n_out + ntaps (reads beyond are taken as zero), out (B, n_out). */
 int a2s_vqt_decimate(void* stream, const float* ypad, long padded_len, const float* taps, int ntaps, float* out, long n_out, int B);
 
+/* ---- scoring of the VALID / TEST stages (pretrain.py:216-249: jiwer.wer per clip on the host): unit-cost Levenshtein distance of n_pairs
+ * independent pairs of word sequences, one launch, one wave per pair (csrc/a2s_metrics.hip).  ref / hyp: the pairs' words (any int32 codes;
+ * equal code = equal word) one after the other; ref_off / hyp_off: n_pairs + 1 offsets into them; order: n_pairs pair indices in the order the
+ * device should take them (longest first keeps the tail of the launch short; NULL: as they come); dist: n_pairs ints.  All of these are device
+ * pointers.  No side of a pair may be longer than a2s_edit_distance_max_len() words (>= 2047): checked on max_ref_len / max_hyp_len, the HOST
+ * values the caller passes -- the library neither reads device memory back nor synchronises; a pair that is longer all the same is not
+ * indexed and gets dist = -1.  Bad arguments (negative counts, over-capacity lengths, a null pointer with n_pairs > 0) are refused before
+ * anything is launched; n_pairs == 0 returns 0 and launches nothing.  a2s_debug_get("edit_distance_launches") counts the launches. */
+int a2s_edit_distance(void* stream, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, const int* order,
+                      int n_pairs, int max_ref_len, int max_hyp_len, int* dist);
+int a2s_edit_distance_max_len(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,7 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "attn_pair_bwd_launches")) return (int)a2s_attn_pair_bwd_launches();
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
     if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
+    if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
     if (!strcmp(key, "device_cus")) return a2s_device_geometry().cus;
     if (!strcmp(key, "device_xccs")) return a2s_device_geometry().xccs;
     return -1;
@@ -323,6 +324,12 @@ int a2s_clip_adadelta(void* stream, float* params, float* grads, float* square_a
 int a2s_vqt_logmag(void* stream, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db) {
     return a2s_vqt_logmag_impl(ST, C, out, partial, B, rows, bins, top_db);
 }
+
+int a2s_edit_distance(void* stream, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, const int* order,
+                      int n_pairs, int max_ref_len, int max_hyp_len, int* dist) {
+    return a2s_edit_distance_impl(ST, ref, ref_off, hyp, hyp_off, order, n_pairs, max_ref_len, max_hyp_len, dist);
+}
+int a2s_edit_distance_max_len(void) { return a2s_edit_distance_max_len_impl(); }
 
 int a2s_bn_bwd_stats(void* stream, const float* g, const float* x, const float* mean, const float* invstd, const float* scale, const float* shift,
                      const uint8_t* keep_mask, float inv_keep, float* partial, float* sums, long rows, int C, int F) {

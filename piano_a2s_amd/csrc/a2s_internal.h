@@ -197,6 +197,12 @@ int a2s_nll_grad_impl(hipStream_t st, float* dlogp, const long long* target, con
 int a2s_clip_adadelta_impl(hipStream_t st, float* params, float* grads, float* square_avg, float* acc_delta, long n, const float* loss,
     float max_norm, float lr, float rho, float eps, float* ctl /* 3 floats */, double* partial, int nblocks, int zero_grad);
 
+// ---- a2s_metrics.hip
+int a2s_edit_distance_max_len_impl(void);
+long a2s_edit_distance_launches(void);
+int a2s_edit_distance_impl(hipStream_t st, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, const int* order,
+    int n_pairs, int max_ref_len, int max_hyp_len, int* dist);
+
 // ---- a2s_vqt.hip
 int a2s_vqt_logmag_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db);
 int a2s_vqt_decimate_impl(hipStream_t st, const float* ypad, long plen, const float* taps, int ntaps, float* out, long n_out, int B);

@@ -69,6 +69,8 @@ def lib():
         # (a build from before that call -- A2S_LIB, tools/lib_ab.sh -- reads them lazily and has nothing to report)
         if hasattr(L, "a2s_env_check") and L.a2s_env_check() != 0:
             raise A2SError(L.a2s_last_error().decode())
+        if hasattr(L, "a2s_edit_distance"):          # (absent from builds older than the device-side scoring: metrics.edit_distances then raises)
+            L.a2s_edit_distance.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]
         if arith != "f16x2":
             for key in (b"conv_f16x2", b"wgrad_f16x2", b"gemm_f16x2"):
                 L.a2s_debug_set(key, 0)

@@ -94,6 +94,29 @@ def make_batch(batch, cfg, seed, frames=1201, upper_range=(20, 120), lower_range
             torch.zeros(batch, dtype=torch.long))
 
 
+def make_wer_corpus(n_clips, seed, bars=5, max_length=(398, 189), upper_range=(20, 120), lower_range=(10, 80)):
+    """Seeded inputs of metrics.corpus_wer at the benchmark's length distribution.  Returns {"upper": (target, near, no_eos), "lower": ...}, each a
+    dict clip id -> list of per-bar id lists as the recipe collects them: `target` rows of U{range} note tokens, `near` the targets with about
+    5 % of the tokens dropped and 5 % substituted (a trained model), `no_eos` max_length random ids per bar (an untrained decoder never emits
+    <eos>, so metrics.unpad keeps the whole row)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for staff, maxlen, (lo, hi) in (("upper", max_length[0], upper_range), ("lower", max_length[1], lower_range)):
+        target, near, no_eos = {}, {}, {}
+        for c in range(n_clips):
+            cid = f"wer{seed}_{c}"
+            rows = [_NOTE_IDS[rng.integers(0, len(_NOTE_IDS), size=int(rng.integers(min(lo, maxlen), min(hi, maxlen) + 1)))] for _ in range(bars)]
+            target[cid] = [r.tolist() for r in rows]
+            near[cid] = []
+            for r in rows:
+                u = rng.random(len(r))
+                r = np.where(u < 0.05, _NOTE_IDS[rng.integers(0, len(_NOTE_IDS), size=len(r))], r)
+                near[cid].append(r[(u < 0.05) | (u >= 0.10)].tolist())
+            no_eos[cid] = [_NOTE_IDS[rng.integers(0, len(_NOTE_IDS), size=maxlen)].tolist() for _ in range(bars)]
+        out[staff] = (target, near, no_eos)
+    return out
+
+
 def make_waveforms(batch, seed, seconds=12.0, sr=16000, device="cpu"):
     """Synthetic 16 kHz clips for the online VQT front-end: up to 6 simultaneous decaying harmonic tones at MIDI 21-108,
     peak-normalised to 0.9.  Returns (batch, seconds*sr) float32."""
