@@ -136,7 +136,8 @@ int a2s_conv3x3(void* stream, const float* x, const float* w, float* y, const fl
  * in_absmax[Cin] = max |x| per input channel (as written into `out_absmax` by the launch that produced x; NULL: measured here by an
  * extra pass), out_absmax[Cout] = max |y| per output channel, written by this launch (NULL: not wanted).  The row-streaming kernel
  * (csrc/a2s_conv_rows.hip) derives exact power-of-two operand scales from them, so that its fp16 operand terms never overflow or lose
- * precision whatever BatchNorm's scale is. */
+ * precision whatever BatchNorm's scale is; the tiled two-term kernel (F % 4 != 0, "conv_rows" 0) scales the activated operand by the power
+ * of two of its bound max_c(|in_scale_c| in_absmax_c + |in_shift_c|). */
 int a2s_conv3x3_ranged(void* stream, const float* x, const float* w, float* y, const float* in_scale, const float* in_shift, const float* in_absmax,
                        float* stat_partial, float* out_absmax, int B, int T, int F, int Cin, int Cout, float* workspace);
 int a2s_conv3x3_stat_blocks(int B, int T, int F, int Cin);
@@ -156,8 +157,11 @@ int a2s_bn_bwd_from_partial(void* stream, const float* g, const float* x, const 
 int a2s_conv3x3_dgrad_bnstats_scaled(void* stream, const float* dy, const float* w, float* g, const float* yl, const float* yl_mean, const float* yl_invstd,
                                      const float* yl_scale, const float* yl_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout,
                                      float* workspace, const float* dy_absmax);
-/* Round 4: the same, also writing g_absmax_out[Cout] = max |g| per channel of the gradient it writes (the launch zeroes it): the range from which
- * a2s_conv3x3_wgrad_bn_ranged bounds the BatchNorm backward of the layer below. */
+/* Round 4: the same, also writing the range of the gradient it writes into g_absmax_out[Cout] (the launch zeroes it): the MAXIMUM over the Cout
+ * entries is max |g| exactly, every entry is >= 0 and none exceeds that maximum -- nothing more (the row-streaming kernels keep one running
+ * maximum per lane whatever the channel, so an entry is NOT the maximum of its channel; only the 20 -> 20 launch and the tiled kernels, which
+ * run a per-channel pass, happen to write max |g_c|).  The consumer, a2s_conv3x3_wgrad_bn_ranged (g_absmax, g_absmax_n = Cout), takes the
+ * maximum over the entries to bound the BatchNorm backward of the layer below. */
 int a2s_conv3x3_dgrad_bnstats_ranged(void* stream, const float* dy, const float* w, float* g, const float* yl, const float* yl_mean, const float* yl_invstd,
                                      const float* yl_scale, const float* yl_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout,
                                      float* workspace, const float* dy_absmax, float* g_absmax_out);

@@ -473,8 +473,9 @@ __device__ __forceinline__ void c4_multiply(const unsigned char* __restrict__ li
 // TERMS = 3: every fp32 operand as three bf16 terms, six products (conv3x3_bf16x3 of round 1).  TERMS = 2: two fp16 terms, THREE
 // products -- half the matrix-pipe work and two thirds of the LDS traffic for the same fp32-level result (a2s_common.h:
 // split2_pair_f16); fp16's narrow exponent range is handled by exact power-of-two scales: the weights by 2^(13 - exponent of max|w|)
-// (pack kernel), a gradient operand by 2^(12 - exponent of max|x|) (x_absmax, written by the kernel that produced it), activations
-// unscaled; the accumulators are multiplied by the inverse power of two in the epilogue.
+// (pack kernel), a gradient operand by 2^(12 - exponent of max|x|) (x_absmax, written by the kernel that produced it), an activated
+// forward operand by the same power of two of its bound max_c(|scale_c| max|x_c| + |shift_c|) (the launcher puts that scalar in x_absmax); the
+// accumulators are multiplied by the inverse power of two in the epilogue.
 #ifdef C4_TRACE
 // timing instrumentation (tools/conv_trace.py): shader-clock stamps of wave 0 of a few mid-grid workgroups, 8 stamps per stage
 #define C4_TRACE_WGS 8
@@ -649,8 +650,8 @@ __global__ __launch_bounds__(256, (TERMS == 2 ? C4_WGS : 2)) void conv3x3_split(
                 split3_pair(v[4], v[5], o[0].z, o[1].z, o[TERMS - 1].z);
                 split3_pair(v[6], v[7], o[0].w, o[1].w, o[TERMS - 1].w);
             } else {
-                // the odd stages' sign rides on the power-of-two scale; activations (unscaled) are clamped to fp16's range in one
-                // v_med3 (it only bites on absurd values), a gradient operand is already inside it by construction of its scale
+                // the odd stages' sign rides on the power-of-two scale; activations are clamped to fp16's range in one v_med3 (with the
+                // launcher's bound in x_absmax it never bites), a gradient operand is already inside it by construction of its scale
                 const float xs = sgn ? -xscale : xscale;
                 if (a.in_scale) {
 #pragma unroll
@@ -1075,7 +1076,8 @@ int a2s_act_bound_impl(hipStream_t st, const float* scale, const float* shift, c
 size_t a2s_conv3x3_workspace_floats_impl(int Cin) {
     if (Cin == 1) return 0;
     const size_t f32_image = (size_t)(Cin / CV_CK) * C2_WCHUNK, split_image = (size_t)c4_chunks(Cin) * c4_chunk_bytes(40) / 4;
-    const size_t tiled = (f32_image > split_image ? f32_image : split_image) + 4;          // + the max |w| scalar of the two-term path
+    // + the per-channel max |x| scratch, the max |w| scalar and the activation bound of the two-term path
+    const size_t tiled = (f32_image > split_image ? f32_image : split_image) + 64 + 4;
     const size_t rows = a2s_conv_rows_workspace_floats(Cin);
     return tiled > rows ? tiled : rows;
 }
@@ -1127,6 +1129,20 @@ int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, c
                 hipLaunchKernelGGL(conv_pack_weights_split<2>, dim3(a2s_cdiv(n, 256)), dim3(256), 0, st, w, (unsigned short*)ws, Cin, Cout, flip, (const float*)wmax);
                 A2S_CHECK_LAUNCH("conv_pack_weights_split<2>");
                 a.w_absmax = wmax;
+                if (!flip && in_scale) {
+                    // An ACTIVATED forward operand relu(x scale_c + shift_c) is scaled like a gradient operand, by the power of two that brings its bound
+                    // (a2s_act_bound of the per-channel max |x| its producer wrote; measured here for a caller without it) to 2^12: BatchNorm's gamma is
+                    // a free parameter, unscaled activations of order 1e5 saturate fp16 (finite, wrong outputs), those of order 1e-3 lose the second term.
+                    if (!in_absmax) {
+                        float* scratch = wmax - 64;
+                        const int rc = a2s_channel_absmax_impl(st, x, (long)B * T, Cin, F, scratch);
+                        if (rc != A2S_OK) return rc;
+                        in_absmax = scratch;
+                    }
+                    hipLaunchKernelGGL(act_bound_kernel, dim3(1), dim3(64), 0, st, in_scale, in_shift, in_absmax, Cin, wmax + 1);
+                    A2S_CHECK_LAUNCH("act_bound (tiled forward)");
+                    a.x_absmax = wmax + 1;
+                }
                 if (Cout == 20 && !yl) hipLaunchKernelGGL((conv3x3_split<20, false, 2>), dim3(nblk4), dim3(256), 0, st, a, wp);
                 else if (Cout == 20) hipLaunchKernelGGL((conv3x3_split<20, true, 2>), dim3(nblk4), dim3(256), 0, st, a, wp);
                 else if (!yl) hipLaunchKernelGGL((conv3x3_split<40, false, 2>), dim3(nblk4), dim3(256), 0, st, a, wp);
