@@ -263,6 +263,20 @@ typedef struct a2s_note_dec_args {
     float* persist_ws; size_t persist_ws_bytes;   /* a2s_note_decoder_persist_ws_bytes(n_clips, R, steps) bytes, 256-byte aligned, or NULL */
 } a2s_note_dec_args;
 int a2s_note_decoder_fwd(void* stream, const a2s_note_dec_args* args, int* steps_done);
+/* ---- grammar-constrained greedy decoding (csrc/a2s_grammar.hip).  A token grammar is a finite automaton given as a
+ * device table next_state[s * V + v] (n_states x V signed bytes, 1 <= n_states <= 127, V <= 256): the state after token v in state s, negative
+ * where v is illegal in s; every row carries one state in row_state (device ints, updated in place).  A row emits the legal token with the
+ * largest logit (lowest index on ties) and moves to its next state; the log-probabilities written stay the UNCONSTRAINED log_softmax.
+ * a2s_grammar_argmax_rows: the constrained sibling of a2s_log_softmax_rows for R rows of V logits (y may be NULL; choice_out: R ints).
+ * a2s_note_decoder_fwd_grammar: a2s_note_decoder_fwd for greedy calls (args->gt, the training buffers and the row bookkeeping must be NULL:
+ * A2S_ERR_ARG otherwise), always on the launch-per-step loop (mid-size kernels at H = 256, library-style products otherwise; args->use_graph
+ * replays it as a graph) with the grammar kernel as the step epilogue -- never the persistent or the few-row decoders, whose epilogues hold
+ * their own argmax.  args->argmax_out receives the EMITTED ids; <eos> bookkeeping as a2s_note_decoder_fwd (a table that allows only <pad>
+ * behind <eos> makes a row's length final at its first <eos>).  a2s_grammar_launches: step epilogues launched so far (proof of the path). */
+int a2s_grammar_argmax_rows(void* stream, const float* x, long ldx, float* y, long ldy, const signed char* next_state, int n_states, int* row_state,
+                            int* choice_out, int R, int V);
+int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state, int* steps_done);
+int a2s_grammar_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

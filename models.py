@@ -75,8 +75,12 @@ class _Transcribe(torch.autograd.Function):
         S = dict(zip(names, params))
         S.update(module._buffer_dict())
         eng = engine.Engine(module.cfg)
+        if module.constrained_decoding and inference:
+            eng.kern_grammar = module._kern_grammar()
+        module.last_decoded = None
         outs = eng.forward(S, spectrogram, inference=inference, ground_truth=ground_truth, teacher_forcing_ratio=tf_ratio,
                            training=module.training, rng=random, dropout=True)
+        module.last_decoded = eng.decoded
         ctx.eng, ctx.S, ctx.names, ctx.can_backward = eng, S, names, module.training
         if not need_grad:
             eng.saved = None          # nothing to keep alive
@@ -92,6 +96,18 @@ class _Transcribe(torch.autograd.Function):
 
 
 class ScoreTranscription(nn.Module):
+    # True: inference (forward(inference=True)) decodes under the kern token grammar (piano_a2s_amd.kern_grammar: every decoded bar is a
+    # well-formed token sequence); the emitted ids are then in `last_decoded` = {"up": (ids, lengths), "lo": ...} -- the four returned
+    # log-probability tensors stay the unconstrained ones.  False (default): the reference's greedy decoder, `last_decoded` is None.
+    constrained_decoding = False
+    last_decoded = None
+
+    def _kern_grammar(self):
+        if getattr(self, "_grammar", None) is None:
+            from piano_a2s_amd.kern_grammar import KernGrammar
+            self._grammar = KernGrammar(labels.labels)
+        return self._grammar
+
     def __init__(self, in_channels=1, freq_bins=480, conv_feature_size=256,
                  hidden_size=256, max_bars=5, num_time_sig=7, num_keys=14,
                  max_length=(437, 129), note_emb_size=16, staff_emb_size=32,

@@ -194,6 +194,16 @@ int a2s_note_decoder_fwd(void* stream, const a2s_note_dec_args* args, int* steps
     if (!args) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd: null args"); return A2S_ERR_ARG; }
     return a2s_note_decoder_fwd_impl(ST, *args, steps_done);
 }
+int a2s_grammar_argmax_rows(void* stream, const float* x, long ldx, float* y, long ldy, const signed char* next_state, int n_states, int* row_state,
+                            int* choice_out, int R, int V) {
+    return a2s_grammar_argmax_rows_impl(ST, x, ldx, y, ldy, next_state, n_states, row_state, choice_out, R, V);
+}
+int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state, int* steps_done) {
+    if (!args) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_grammar: null args"); return A2S_ERR_ARG; }
+    const a2s_grammar_ref g = {next_state, n_states, row_state};
+    return a2s_note_decoder_fwd_grammar_impl(ST, *args, g, steps_done);
+}
+int a2s_grammar_launches(void) { return a2s_grammar_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

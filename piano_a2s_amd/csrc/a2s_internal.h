@@ -103,6 +103,23 @@ int a2s_conv3x3_wgrad_rows_impl(hipStream_t st, const float* dy, const float* x,
     size_t ws_bytes, int B, int T, int F, int Cin, int Cout, const float* dy_absmax, const float* act_absmax);
 
 // ---- a2s_seq.hip
+// argument block of the step epilogue (note_step_finalize; grammar_step_finalize of a2s_grammar.hip)
+struct StepFinArgs {
+    const float* logits; long ldl;        // (R, V)
+    float* probs; long probs_bstride;     // row b, step t at probs + b*probs_bstride + t*V
+    const long long* gt; long gt_bstride; // ground-truth ids (row b at gt + b*gt_bstride), null in inference
+    const float* emb;                     // (V, E) embedding table
+    float* xnext; long ldx;               // next GRU input rows; token embedding -> columns [0, E)
+    const uint8_t* drop; float inv_keep;  // (R, E) keep mask for the NEXT token or null
+    int* argmax_out; long am_bstride;     // ids[b*am_bstride + t] (int32) or null
+    int* eos_seen; long long* lengths; int* n_done; int* steps_exec;
+    const int* t_base;                    // graph replay: step index = t + *t_base (null: t)
+    const int* row_until;                 // training: rows finished at this step (t >= row_until[row]) keep their outputs untouched
+    int n_clips;                          // rows per group (fused bars); teacher_force bit g applies to the rows of group g
+    int R, V, E, t, teacher_force, eos_id, max_t;
+};
+// a token grammar for the greedy decoder: next[s * V + v] = state after token v in state s, negative where v is illegal; one state per row
+struct a2s_grammar_ref { const signed char* next; int n_states; int* row_state; };
 int a2s_gru_gates_fwd_impl(hipStream_t st, const float* gi, long ldgi, const float* gh, long ldgh, const float* hprev,
     long ldhp, float* hout, long ldho, float* hout2, long ldho2, float* save, int R, int H);
 int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t, const float* dhz_in, const float* dout, long ld_dout,
@@ -119,6 +136,7 @@ int a2s_log_softmax_rows_impl(hipStream_t st, const float* x, long ldx, float* y
 int a2s_embed_rows_impl(hipStream_t st, const float* table, const long long* ids64, const int* ids32, long id_stride,
     int const_id, float* out, long ldo, int col0, int R, int E, const uint8_t* drop, float inv_keep);
 int a2s_note_decoder_fwd_impl(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
+int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_grammar_ref& g, int* steps_done);
 int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_args& au, const a2s_note_dec_args& al, const int* pair_order,
     const int* pair_rank, const int* pair_n_active, int* done_u, int* done_l);
 int a2s_staff_emb_fwd_impl(hipStream_t st, const float* note_emb, const float* const* w /* 8 GRU tensors f then r */,
@@ -170,6 +188,13 @@ int a2s_note_step_mid_gru(hipStream_t st, const a2s_note_dec_args& a, int si, in
 bool a2s_note_step_mid_bwd_ok(const a2s_note_dec_bwd_args& a);
 int a2s_note_step_mid_bwd(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
 int a2s_note_step_mid_bwd_query(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, float* dh_out, int nrows, const int* rowmap);
+
+// ---- a2s_grammar.hip
+bool a2s_grammar_ref_ok(const a2s_grammar_ref& g, int R, int V);
+int a2s_grammar_argmax_rows_impl(hipStream_t st, const float* x, long ldx, float* y, long ldy, const signed char* next, int n_states, int* row_state,
+    int* choice_out, int R, int V);
+int a2s_grammar_step_finalize_impl(hipStream_t st, const StepFinArgs& a, const a2s_grammar_ref& g);
+int a2s_grammar_launches_impl(void);
 
 // ---- a2s_persist.hip
 unsigned* a2s_persist_latch_ptr(void);

@@ -378,20 +378,7 @@ int a2s_attn_step_fwd_impl(hipStream_t st, const float* Kmat, const float* enc, 
 // next input token = gt[b,t] when teacher-forced else the argmax; its embedding (optionally dropped out)
 // goes to the first E columns of the next step's GRU input row; EOS bookkeeping of reference
 // models.py:411-419: every hit overwrites lengths[b] = t+1; n_done counts rows that have hit at least once.
-struct StepFinArgs {
-    const float* logits; long ldl;        // (R, V)
-    float* probs; long probs_bstride;     // row b, step t at probs + b*probs_bstride + t*V
-    const long long* gt; long gt_bstride; // ground-truth ids (row b at gt + b*gt_bstride), null in inference
-    const float* emb;                     // (V, E) embedding table
-    float* xnext; long ldx;               // next GRU input rows; token embedding -> columns [0, E)
-    const uint8_t* drop; float inv_keep;  // (R, E) keep mask for the NEXT token or null
-    int* argmax_out; long am_bstride;     // ids[b*am_bstride + t] (int32) or null
-    int* eos_seen; long long* lengths; int* n_done; int* steps_exec;
-    const int* t_base;                    // graph replay: step index = t + *t_base (null: t)
-    const int* row_until;                 // training: rows finished at this step (t >= row_until[row]) keep their outputs untouched
-    int n_clips;                          // rows per group (fused bars); teacher_force bit g applies to the rows of group g
-    int R, V, E, t, teacher_force, eos_id, max_t;
-};
+// (StepFinArgs: a2s_internal.h -- the grammar-constrained epilogue of a2s_grammar.hip takes the same block)
 
 __global__ __launch_bounds__(256) void note_step_finalize(StepFinArgs a) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -530,7 +517,8 @@ static int enqueue_query(hipStream_t st, const NoteDecArgs& a, int si, int sv) {
 // per-step saved tensors (q, o, gates, attention weights) go to index `sv`.  fused: the few-row path of a2s_step.hip -- the query
 // of slot sv must already be there (enqueue_query / the previous step), this step leaves the next one's in slot sv_next (!last).
 static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int so, int sv, int t, const int* t_base, int tf,
-                             bool fused = false, int sv_next = 0, bool last = false, const AttnPairStep* pair = nullptr) {
+                             bool fused = false, int sv_next = 0, bool last = false, const AttnPairStep* pair = nullptr,
+                             const a2s_grammar_ref* grammar = nullptr) {
     const int H2 = 2 * a.H, ldx = a.E + H2;
     if (fused) {
         float* xs = a.x + (long)si * a.R * ldx;
@@ -604,6 +592,7 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     f.t_base = t_base;
     f.row_until = a.n_active ? a.row_until : nullptr; f.n_clips = a.n_clips > 0 ? a.n_clips : a.R;
     f.R = a.R; f.V = a.V; f.E = a.E; f.t = t; f.teacher_force = tf; f.eos_id = a.eos_id; f.max_t = a.steps;
+    if (grammar) return a2s_grammar_step_finalize_impl(st, f, *grammar);       // the constrained choice in the place of the argmax (a2s_grammar.hip)
     return a2s_note_step_finalize_impl(st, f);
 }
 
@@ -612,19 +601,19 @@ __global__ void advance_counter(int* p, int inc) { if (threadIdx.x == 0 && block
 // Greedy decode as a replayed hipGraph: the state ping-pongs between two slots (nothing is kept for a backward pass), the step
 // index comes from a device counter, so ONE captured chunk of `chunk` steps serves the whole sequence; the host replays it and
 // looks at the done counter after every replay.  Removes the per-launch host cost that dominates small-batch decoding.
-static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, int* steps_done) {
+static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar = nullptr) {
     int chunk = a.poll > 0 ? a.poll : 16;
     if (chunk & 1) ++chunk;                                   // even: the state is back in slot 0 after every replay
     hipError_t e = hipMemsetAsync(a.t_base, 0, sizeof(int), st);
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "greedy graph memset: %s", hipGetErrorString(e));
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    const bool fused = note_step_fusable(a);
+    const bool fused = !grammar && note_step_fusable(a);
     int rc = fused ? enqueue_query(st, a, 0, 0) : A2S_OK;     // the very first query; every later one is left behind by the previous step
     if (rc) return rc;
     e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
-    for (int j = 0; j < chunk && rc == A2S_OK; ++j) rc = enqueue_note_step(st, a, j & 1, (j + 1) & 1, 0, j, a.t_base, 0, fused, 0, false);
+    for (int j = 0; j < chunk && rc == A2S_OK; ++j) rc = enqueue_note_step(st, a, j & 1, (j + 1) & 1, 0, j, a.t_base, 0, fused, 0, false, nullptr, grammar);
     if (rc == A2S_OK) hipLaunchKernelGGL(advance_counter, dim3(1), dim3(64), 0, st, a.t_base, chunk);
     e = hipStreamEndCapture(st, &graph);
     if (rc != A2S_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -663,11 +652,12 @@ static int note_decoder_zero_fill(hipStream_t st, const NoteDecArgs& a) {
     return A2S_OK;
 }
 
-int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_done) {
+// grammar: the constrained greedy decoder (a2s_note_decoder_fwd_grammar_impl) -- the launch-per-step loop only, every step's epilogue the grammar kernel
+static int note_decoder_fwd_loop(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar) {
     // few clips: one persistent launch for the whole call (a2s_dec_persist.hip)
-    if (a2s_note_decoder_fwd_persist_ok(a)) return a2s_note_decoder_fwd_persist(st, a, steps_done);
+    if (!grammar && a2s_note_decoder_fwd_persist_ok(a)) return a2s_note_decoder_fwd_persist(st, a, steps_done);
     // stream capture is not allowed on the legacy default stream: callers that want the graph path run on a created stream
-    if (!a.gt && a.use_graph && a.t_base && !a.gates && !a.attw && !a.drop && st != nullptr) return note_decoder_greedy_graph(st, a, steps_done);
+    if (!a.gt && a.use_graph && a.t_base && !a.gates && !a.attw && !a.drop && st != nullptr) return note_decoder_greedy_graph(st, a, steps_done, grammar);
     { const int rc0 = note_decoder_zero_fill(st, a); if (rc0) return rc0; }
     int s = 0;
     // The few-row step kernels take over as soon as the rows still running fit them (the whole call when it is small; the tail of a large
@@ -676,10 +666,10 @@ int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_d
     bool prev_q = false;                     // did the previous step leave this step's query behind?
     const bool mid = note_step_mid(a, nullptr);
     for (; s < a.steps; ++s) {
-        const bool fused = note_step_fusable(a, s);
+        const bool fused = !grammar && note_step_fusable(a, s);
         if ((fused || mid) && !prev_q) { int rc = enqueue_query(st, a, s, s); if (rc) return rc; }
         prev_q = fused || mid;
-        int rc = enqueue_note_step(st, a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, fused, s + 1, s + 1 == a.steps);
+        int rc = enqueue_note_step(st, a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, fused, s + 1, s + 1 == a.steps, nullptr, grammar);
         if (rc) return rc;
         if (!a.gt && a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
             int done = 0;   // greedy only: one small D2H + sync per `poll` steps
@@ -691,6 +681,17 @@ int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_d
     }
     if (steps_done) *steps_done = s;
     return A2S_OK;
+}
+
+int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_done) { return note_decoder_fwd_loop(st, a, steps_done, nullptr); }
+
+// Greedy decoding under a token grammar: row r starts in row_state[r] and walks the table with every token it emits.
+int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, const a2s_grammar_ref& g, int* steps_done) {
+    A2S_REQUIRE(!a.gt && !a.tf_flags_dev, "note_decoder_fwd_grammar: greedy decoding only (ground truth given)");
+    A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list, "note_decoder_fwd_grammar: inference only (training buffers or row bookkeeping given)");
+    A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_grammar: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
+    A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_grammar: null bookkeeping or output buffers");
+    return note_decoder_fwd_loop(st, a, steps_done, &g);
 }
 
 // The two NoteDecoders of a segment (models.py:261-275) decoded by ONE host loop on their two streams: while both staves run a step on the

@@ -316,6 +316,10 @@ class Engine:
         self.attn_clip_steps = []
         self.attn_shared_clip_steps = []       # ... of which: pairs served by a pass shared between the two staves (Engine._decode_pair)
         self.poll = 16            # greedy decode: host looks at the device-side done counter every `poll` steps
+        # kern_grammar.KernGrammar or None: greedy decoding emits only token sequences the grammar accepts; after such a
+        # forward `decoded` = {"up": (ids (B, bars, U) int32, lengths (B, bars) int64), "lo": ...}, None otherwise
+        self.kern_grammar = None
+        self.decoded = None
         # Synchronised BatchNorm (what SpeechBrain's DDP wrapping gives the reference): batch statistics over the
         # GLOBAL minibatch -- per-channel (sum, sum of squares, count) are all-reduced between the ranks.  Off by default:
         # per-rank statistics (plain DDP semantics).  Needs an initialised process group.
@@ -506,6 +510,12 @@ class Engine:
         dev = enc.device
         n = steps
         graph = gt_bar is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH)     # greedy decode: replayed hipGraph
+        # greedy decode under the kern token grammar (kern_grammar.KernGrammar, csrc/a2s_grammar.hip): one automaton state per row, the launch-per-step loop only
+        grammar = self.kern_grammar if (gt_bar is None and not training) else None
+        if grammar is not None:
+            if grammar.vocab_size != V:
+                raise hip.A2SError(f"Engine.kern_grammar is a table over {grammar.vocab_size} symbols, the decoder's vocabulary has {V}")
+            persist = False
         t_base = torch.zeros(1, dtype=torch.int32, device=dev) if graph else None
         # (with row_list the tail steps write only the rows still running; a2s_note_decoder_fwd zero-fills these buffers itself -- from C,
         # where a memset that has to wait for room in a busy stream's queue does not hold the interpreter lock)
@@ -518,7 +528,8 @@ class Engine:
         attw = self._empty(n, B, T, dev=dev) if training else None
         gh, gi = self._empty(B, 3 * H2, dev=dev), self._empty(B, 3 * H2, dev=dev)
         logits = self._empty(B, V, dev=dev)
-        ids = torch.zeros((B, max_steps), dtype=torch.int32, device=dev)
+        # (under a grammar the steps a call never runs read <pad>, what a finished row emits: a whole row of `decoded` is then a sentence of the grammar)
+        ids = torch.zeros((B, max_steps), dtype=torch.int32, device=dev) if grammar is None else torch.full((B, max_steps), PAD, dtype=torch.int32, device=dev)
         eos_seen = torch.zeros(B, dtype=torch.int32, device=dev)
         lengths = torch.full((B,), max_steps, dtype=torch.long, device=dev)
         n_done = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -584,6 +595,13 @@ class Engine:
         if defer_launch:                      # _decode_pair: the arguments are ready, the caller launches both staves with one call
             return a, finish
         done = C.c_int(0)
+        if grammar is not None:
+            row_state = torch.full((B,), grammar.start, dtype=torch.int32, device=dev)
+            hip.check(L.a2s_note_decoder_fwd_grammar(hip.stream(), C.byref(a), hip._p(grammar.device_table(dev)), grammar.n_states, hip._p(row_state),
+                                                     C.byref(done)), "a2s_note_decoder_fwd_grammar")
+            ids_, lengths_, saved = finish(done.value)
+            saved["row_state"] = row_state
+            return ids_, lengths_, saved
         hip.check(L.a2s_note_decoder_fwd(hip.stream(), C.byref(a), C.byref(done)), "a2s_note_decoder_fwd")
         return finish(done.value)
 
@@ -721,6 +739,7 @@ class Engine:
         tokw = 4 * Sz + te + ke
         ldxb = tokw + 2 * H
         greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH)
+        constrained = self.kern_grammar is not None and gt_cpu is None and not training     # (the persistent decoder's epilogue holds its own argmax)
         # the two staves of a segment run on two streams, each issued by its own host thread -- also in greedy decoding, where each
         # thread polls the done counter of its own stream (the hipGraph variant captures on one created stream and stays sequential)
         concurrent = getattr(self, "concurrent_staves", True) and not greedy_graph
@@ -758,7 +777,7 @@ class Engine:
             # per step, and the step from 514 to 540 ms (profiles/r04_dec_persist_beside_bulk.txt).
             alone = len(clip_groups) == 1 or _PERSIST_BESIDE
             persist_g = (Bg <= 8 and gidx == len(clip_groups) - 1 and alone and H == 256 and E == 16 and (plan is not None or (inference and not greedy_graph))
-                         and hip.lib().a2s_debug_get(b"dec_persist") != 0)
+                         and hip.lib().a2s_debug_get(b"dec_persist") != 0 and not constrained)
             concurrent_g = concurrent and staves_concurrent(gidx, len(clip_groups)) and not persist_g
             streams = staff_streams(dev, gidx) if concurrent_g else None
 
@@ -1030,6 +1049,12 @@ class Engine:
                 gens.append(g_)
             _trace("generators made")
             group_saved = run_clip_groups(dev, [lambda gi=gi, r=r: decode_group(gi, r[0], r[1], gens[gi]) for gi, r in enumerate(clip_groups)])
+        self.decoded = None
+        if constrained:
+            # the EMITTED ids and the lengths of every bar (the log-probabilities stay the unconstrained ones: their argmax is not what was decoded)
+            segs = group_saved[0]["segments"]
+            self.decoded = {k: (torch.stack([sg["staff"][k][0] for sg in segs], dim=1), torch.stack([sg["staff"][k][1] for sg in segs], dim=1))
+                            for k in ("up", "lo")}
         self.saved = dict(conv=conv_saved, enc=enc_saved, keys=keys, groups=group_saved, enc_out=enc,
                           bars=group_saved[0]["bars"], segments=group_saved[0]["segments"], sos_rec=group_saved[0]["sos_rec"],
                           training=training, concurrent=concurrent, outs=(ts_out, key_out, up_out, lo_out), bar_major=bar_major,

@@ -214,6 +214,24 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def grammar_argmax_rows(x, table, row_state, y=None, V=None):
+    """a2s_grammar_argmax_rows: rows of logits x (R, >= V) float32, table (n_states, V) int8 (kern_grammar.KernGrammar.device_table),
+    row_state (R,) int32 updated in place -> the emitted ids (R,) int32; y (R, >= V) receives the unconstrained log_softmax when given."""
+    V = table.shape[1] if V is None else V
+    R = x.shape[0]
+    if table.dtype != torch.int8 or row_state.dtype != torch.int32 or x.dtype != torch.float32 or not table.is_contiguous():
+        raise A2SError("grammar_argmax_rows: expects float32 logits, a contiguous int8 table and int32 row states")
+    choice = torch.empty(R, dtype=torch.int32, device=x.device)
+    check(lib().a2s_grammar_argmax_rows(stream(), _p(x), C.c_long(x.stride(0)), _p(y), C.c_long(y.stride(0) if y is not None else 0), _p(table),
+                                        table.shape[0], _p(row_state), _p(choice), R, V), "a2s_grammar_argmax_rows")
+    return choice
+
+
+def grammar_launches():
+    """Grammar step epilogues the library has launched in this process (a2s_grammar_launches)."""
+    return int(lib().a2s_grammar_launches())
+
+
 def check(rc, what):
     if rc != 0:
         raise A2SError(f"{what} failed ({rc}): {lib().a2s_last_error().decode()}")

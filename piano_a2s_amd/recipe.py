@@ -50,8 +50,24 @@ class ASR(sb.Brain):
             return self.modules.transcription(spectrogram=spectrogram, inference=False,
                                               ground_truth=[ts_t, key_t, up_t, up_len, lo_t, lo_len],
                                               teacher_forcing_ratio=self.teacher_forcing_ratio, device=self.device)
+        self._set_constrained_decoding()
         return self.modules.transcription(spectrogram=spectrogram, inference=True, ground_truth=None,
                                           teacher_forcing_ratio=0., device=self.device)
+
+    def _constrained(self):
+        """--constrained_decoding=true (an optional override, not a key of the yaml files): VALID / TEST decode under the kern token grammar."""
+        v = getattr(self.hparams, "constrained_decoding", False)
+        return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
+    def _set_constrained_decoding(self):
+        if not self._constrained():
+            return
+        model = self.modules.transcription
+        model = getattr(model, "module", model)                      # (a DistributedDataParallel wrapper)
+        if not hasattr(model, "constrained_decoding"):
+            raise ValueError(f"--constrained_decoding needs a transcription module that decodes under the kern grammar; {type(model).__name__} has no "
+                             "`constrained_decoding` attribute")
+        model.constrained_decoding = True
 
     def compute_objectives(self, predictions, batch, stage):
         batch = _to_device(batch, self.device)
@@ -78,7 +94,13 @@ class ASR(sb.Brain):
     def _record_predictions(self, predictions, targets, names, versions):
         ts_o, key_o, up_o, lo_o = predictions
         ts_t, key_t, up_t, lo_t = targets
-        up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
+        if self._constrained():
+            # the ids the constrained decoder EMITTED (the log-probabilities stay the unconstrained ones, their argmax is not what was decoded)
+            model = self.modules.transcription
+            decoded = getattr(model, "module", model).last_decoded
+            up_ids, lo_ids = decoded["up"][0].cpu().numpy(), decoded["lo"][0].cpu().numpy()
+        else:
+            up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
         ts_ids, key_ids = ts_o.argmax(-1).cpu().numpy(), key_o.argmax(-1).cpu().numpy()
         up_t, lo_t, ts_t, key_t = up_t.cpu().numpy(), lo_t.cpu().numpy(), ts_t.cpu().numpy(), key_t.cpu().numpy()
         for b, name in enumerate(names):
@@ -121,6 +143,7 @@ class ASR(sb.Brain):
         lr is the truth, and the idle torch optimizer (which update_learning_rate also addresses) is brought in line with it -- without
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
         super().on_fit_start()
+        self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
         fused = self._fused_step()
         if fused and self.optimizer is not None:
             for g in self.optimizer.param_groups:

@@ -1,29 +1,106 @@
 #!/usr/bin/env python3
 """Greedy-decode throughput (BASELINE.json configs[4]): batched 12 s clips -> Kern tokens on one MI355X, eval mode, procedural
-weights with <eos> bias so decoding terminates at data-dependent steps.  Prints one JSON line (clips/s, tokens/s, decode steps)."""
+weights with <eos> bias so decoding terminates at data-dependent steps.  Prints one JSON line (clips/s, tokens/s, decode steps).
+
+    infer_bench.py [B]                  greedy as shipped
+    infer_bench.py [B] --stepwise       greedy forced onto the launch-per-step loop (dec_persist 0, dec_fused 0)
+    infer_bench.py [B] --constrained    greedy under the kern token grammar (Engine.kern_grammar)
+    infer_bench.py --compare OUT.json [--batches 256,8] [--repeats 3]
+                                        the three variants in ONE process, alternating, `repeats` timed forwards each (after one warm-up each):
+                                        one JSON line per forward, the summary (median, spread) to OUT.json"""
+import argparse
 import json
+import os
+import statistics
 import sys
 import time
 
 import torch
 
-sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
-from piano_a2s_amd import engine, spec, synthetic
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from piano_a2s_amd import engine, hip, spec, synthetic
+from piano_a2s_amd.kern_grammar import KernGrammar, legal_share
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=64)
+ap.add_argument("--constrained", action="store_true")
+ap.add_argument("--stepwise", action="store_true")
+ap.add_argument("--compare", metavar="OUT.json")
+ap.add_argument("--batches", default="256,8")
+ap.add_argument("--repeats", type=int, default=3)
+args = ap.parse_args()
+
 dev = torch.device("cuda:0")
 cfg = spec.default_cfg()
 S = {k: v.to(dev) for k, v in spec.procedural_state(cfg, 2032, eos_bias=2.5, lively="token").items()}
-batch = synthetic.make_batch(B, cfg, 77, spectrogram="ridges", full_tail=0.0)
-x = batch[0].to(dev)
-eng = engine.Engine(cfg)
-for it in range(3):
+GRAMMAR = KernGrammar()
+L = hip.lib()
+
+
+def set_stepwise(on):
+    for key in (b"dec_persist", b"dec_fused"):
+        hip.check(L.a2s_debug_set(key, 0 if on else 1), "a2s_debug_set")
+
+
+def forward(x, variant):
+    """One timed forward of `variant` ("greedy", "stepwise" or "constrained") -> the record of the run."""
+    set_stepwise(variant == "stepwise")
+    eng = engine.Engine(cfg)
+    eng.kern_grammar = GRAMMAR if variant == "constrained" else None
+    n0, g0 = L.a2s_launch_count(), hip.grammar_launches()
     torch.cuda.synchronize(); t0 = time.time()
     with torch.no_grad():
         ts, key, up, lo = eng.forward(S, x, inference=True)
     torch.cuda.synchronize(); dt = time.time() - t0
-steps = sum(b["staff"][k][2]["steps"] for b in eng.saved["bars"] for k in ("up", "lo"))
-launched = sum(b["staff"][k][2]["launched"] for b in eng.saved["bars"] for k in ("up", "lo"))
-tokens = int((up.abs().sum(-1) > 0).sum() + (lo.abs().sum(-1) > 0).sum())
-print(json.dumps({"metric": "greedy decode clips/s", "batch": B, "seconds": round(dt, 4), "clips_per_s": round(B / dt, 2),
-                  "decoded_token_rows_per_s": round(tokens / dt), "executed_steps": steps, "launched_steps": launched}))
+    set_stepwise(False)
+    B = x.shape[0]
+    calls = [b["staff"][k][2] for b in eng.saved["bars"] for k in ("up", "lo")]
+    steps, launched = sum(c["steps"] for c in calls), sum(c["launched"] for c in calls)
+    tokens = int((up.abs().sum(-1) > 0).sum() + (lo.abs().sum(-1) > 0).sum())
+    if eng.decoded is not None:
+        ids = {k: eng.decoded[k][0].cpu().numpy() for k in ("up", "lo")}
+    else:
+        ids = {"up": up.argmax(-1).cpu().numpy(), "lo": lo.argmax(-1).cpu().numpy()}
+    from piano_a2s_amd import metrics
+    rows = {k: [metrics.unpad(r).tolist() for clip in v for r in clip] for k, v in ids.items()}
+    return {"metric": "greedy decode clips/s", "variant": variant, "batch": B, "seconds": round(dt, 4), "clips_per_s": round(B / dt, 2),
+            "decoded_token_rows_per_s": round(tokens / dt), "executed_steps": steps, "launched_steps": launched,
+            "us_per_executed_step": round(1e6 * dt / max(steps, 1), 2),
+            # every launch of the forward (ConvStack, encoder and bar level included) over the decode steps it launched
+            "launches_per_launched_step": round((L.a2s_launch_count() - n0) / max(launched, 1), 2),
+            "grammar_epilogues": hip.grammar_launches() - g0, "persistent_calls": sum(c.get("persist_ws") is not None for c in calls),
+            "well_formed_bar_share": round(legal_share(rows, GRAMMAR), 4)}
+
+
+if args.compare:
+    variants = ("greedy", "stepwise", "constrained")
+    summary = {"what": "tools/infer_bench.py --compare: greedy as shipped / forced onto the launch-per-step loop / under the kern grammar; "
+                       "one process, variants alternating, median of the timed forwards", "repeats": args.repeats, "batches": {}}
+    for B in [int(b) for b in args.batches.split(",")]:
+        x = synthetic.make_batch(B, cfg, 77, spectrogram="ridges", full_tail=0.0)[0].to(dev)
+        runs = {v: [] for v in variants}
+        for v in variants:
+            forward(x, v)                                   # warm-up
+        for _ in range(args.repeats):
+            for v in variants:
+                rec = forward(x, v)
+                print(json.dumps(rec), flush=True)
+                runs[v].append(rec)
+        out = {}
+        for v in variants:
+            secs = [r["seconds"] for r in runs[v]]
+            med = statistics.median(secs)
+            out[v] = dict(runs[v][-1], seconds=med, seconds_all=secs, clips_per_s=round(B / med, 2),
+                          us_per_executed_step=round(1e6 * med / max(runs[v][-1]["executed_steps"], 1), 2),
+                          spread=round((max(secs) - min(secs)) / med, 4))
+            del out[v]["decoded_token_rows_per_s"]
+        summary["batches"][str(B)] = out
+    os.makedirs(os.path.dirname(os.path.abspath(args.compare)), exist_ok=True)
+    with open(args.compare, "w") as f:
+        json.dump(summary, f, indent=1)
+else:
+    variant = "constrained" if args.constrained else ("stepwise" if args.stepwise else "greedy")
+    x = synthetic.make_batch(args.batch, cfg, 77, spectrogram="ridges", full_tail=0.0)[0].to(dev)
+    for it in range(3):
+        rec = forward(x, variant)
+    print(json.dumps(rec))
