@@ -277,6 +277,39 @@ int a2s_grammar_argmax_rows(void* stream, const float* x, long ldx, float* y, lo
                             int* choice_out, int R, int V);
 int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state, int* steps_done);
 int a2s_grammar_launches(void);
+/* ---- beam-search decoding of one (bar, staff) call (csrc/a2s_beam.hip).  The call runs over B clips with K beam slots
+ * each, 1 <= K <= A2S_BEAM_MAX: args->R = K * B, args->n_clips = B, row = slot * B + clip (the fused-bars layout, so the attention kernels read a
+ * clip's key image and encoder rows once for its K rows); every row of args->h / args->x starts from the same state and the <sos> embedding.
+ * Nothing is kept per step: args->h, args->x, args->q and args->o hold TWO slots of K * B rows each (step parity).
+ * A candidate (slot k, token v) scores score[k] + log_softmax(logits_k)[v] (one fp32 add), -inf where next_state forbids v in the slot's state; a
+ * finished slot has the one candidate (k, <pad>) at its score; the new beam is the K best candidates of the clip, ties to the lowest k * V + v,
+ * best first.  Behind the loop each clip keeps the slot with the largest score / len^alpha (alpha = 0: the raw score; ties to the lowest slot).
+ * a2s_note_decoder_fwd_beam: greedy calls only (args->gt, the training buffers and the row bookkeeping must be NULL; K outside 1 .. 4 or
+ * R != K * n_clips: A2S_ERR_ARG), always the launch-per-step loop (mid-size kernels at H = 256, library-style products otherwise; never the
+ * persistent or the few-row decoders; args->use_graph is ignored) with beam_step_finalize as the step epilogue, then one beam_backtrack launch.
+ * It initialises score / finished / done_count / args->n_done itself; row_state holds the start state of every row.  args->probs receives, at
+ * step t, the UNCONSTRAINED log-probabilities computed at step t in the slot the winning hypothesis then occupied; args->argmax_out,
+ * args->lengths and args->eos_seen are not used.  a2s_beam_launches: step epilogues launched so far (proof of the path). */
+#define A2S_BEAM_MAX 4
+typedef struct a2s_beam_args {
+    int K; float alpha;                      /* beam slots per clip; length penalty of the final pick */
+    const signed char* next_state; int n_states;   /* the grammar's table as in a2s_note_decoder_fwd_grammar; NULL / 0: none */
+    int pad_id;                              /* what a finished slot emits, and the ids behind the executed steps */
+    int* row_state;                          /* device, K * B ints (read and written also without a grammar) */
+    float* score; int* finished;             /* device, K * B each */
+    int* done_count;                         /* device, max_steps + 1 ints: finished slots BEFORE step t (a step is a no-op at K * B) */
+    int* token_hist; int* parent_hist; float* score_hist;      /* device, (max_steps, K * B) each: per step the new slots' token, parent slot, score */
+    float* probs_scratch;                    /* device, (K * B, max_steps, V), zero-filled: every row's log-probabilities per step */
+    int* ids_out; long long* lengths_out; float* score_out;    /* device: (B, max_steps) ids, (B) lengths, (B) raw scores of the winners */
+} a2s_beam_args;
+int a2s_note_decoder_fwd_beam(void* stream, const a2s_note_dec_args* args, const a2s_beam_args* beam, int* steps_done);
+/* one step epilogue on its own (tests): logits (K * B, ldl), step t of max_steps; emb (V, E) -> xnext (K * B, ldx); h (K * B, h_cols) and, if not
+ * NULL, q (K * B, q_cols) are re-parented in place; n_done / steps_exec: device ints.  a2s_beam_backtrack: the pick and the walk back, probs row
+ * b at probs + b * probs_bstride (max_steps x V); steps_exec: device int, the steps that ran. */
+int a2s_beam_step(void* stream, const a2s_beam_args* beam, const float* logits, long ldl, const float* emb, float* xnext, long ldx, float* h, int h_cols,
+                  float* q, int q_cols, int* n_done, int* steps_exec, int B, int V, int E, int t, int max_steps, int eos_id);
+int a2s_beam_backtrack(void* stream, const a2s_beam_args* beam, float* probs, long probs_bstride, const int* steps_exec, int B, int V, int max_steps, int eos_id);
+int a2s_beam_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -77,10 +77,14 @@ class _Transcribe(torch.autograd.Function):
         eng = engine.Engine(module.cfg)
         if module.constrained_decoding and inference:
             eng.kern_grammar = module._kern_grammar()
+        if inference:
+            eng.beam_size, eng.beam_length_penalty = module.beam_size, module.beam_length_penalty
         module.last_decoded = None
+        module.last_beam_scores = None
         outs = eng.forward(S, spectrogram, inference=inference, ground_truth=ground_truth, teacher_forcing_ratio=tf_ratio,
                            training=module.training, rng=random, dropout=True)
         module.last_decoded = eng.decoded
+        module.last_beam_scores = eng.beam_scores
         ctx.eng, ctx.S, ctx.names, ctx.can_backward = eng, S, names, module.training
         if not need_grad:
             eng.saved = None          # nothing to keep alive
@@ -101,6 +105,13 @@ class ScoreTranscription(nn.Module):
     # log-probability tensors stay the unconstrained ones.  False (default): the reference's greedy decoder, `last_decoded` is None.
     constrained_decoding = False
     last_decoded = None
+    # beam search over the note sequences of every (bar, staff) in inference (csrc/a2s_beam.hip): beam_size hypotheses per
+    # clip, 1 .. 4, 1 = greedy; each clip keeps the one with the largest score / len^beam_length_penalty.  With >= 2 the emitted ids are in
+    # `last_decoded` (they are not argmax of the returned log-probabilities) and the kept hypotheses' scores in `last_beam_scores`
+    # = {"up": (B, bars), "lo": ...}.  Composes with constrained_decoding.
+    beam_size = 1
+    beam_length_penalty = 0.0
+    last_beam_scores = None
 
     def _kern_grammar(self):
         if getattr(self, "_grammar", None) is None:

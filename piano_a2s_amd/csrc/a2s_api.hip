@@ -204,6 +204,26 @@ int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, co
     return a2s_note_decoder_fwd_grammar_impl(ST, *args, g, steps_done);
 }
 int a2s_grammar_launches(void) { return a2s_grammar_launches_impl(); }
+int a2s_note_decoder_fwd_beam(void* stream, const a2s_note_dec_args* args, const a2s_beam_args* beam, int* steps_done) {
+    if (!args || !beam) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_beam: null args"); return A2S_ERR_ARG; }
+    return a2s_note_decoder_fwd_beam_impl(ST, *args, *beam, steps_done);
+}
+int a2s_beam_step(void* stream, const a2s_beam_args* beam, const float* logits, long ldl, const float* emb, float* xnext, long ldx, float* h, int h_cols,
+                  float* q, int q_cols, int* n_done, int* steps_exec, int B, int V, int E, int t, int max_steps, int eos_id) {
+    if (!beam) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "beam_step: null args"); return A2S_ERR_ARG; }
+    const a2s_beam_args& g = *beam;
+    const BeamStepArgs a = {logits, ldl, emb, xnext, ldx, h, h_cols, q, q_cols, g.next_state, g.n_states, g.row_state, g.score, g.finished, g.done_count,
+                            g.token_hist, g.parent_hist, g.score_hist, g.probs_scratch, n_done, steps_exec, B, g.K, V, E, t, max_steps, eos_id, g.pad_id};
+    return a2s_beam_step_finalize_impl(ST, a);
+}
+int a2s_beam_backtrack(void* stream, const a2s_beam_args* beam, float* probs, long probs_bstride, const int* steps_exec, int B, int V, int max_steps, int eos_id) {
+    if (!beam) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "beam_backtrack: null args"); return A2S_ERR_ARG; }
+    const a2s_beam_args& g = *beam;
+    const BeamBackArgs a = {g.score, g.token_hist, g.parent_hist, g.probs_scratch, probs, probs_bstride, g.ids_out, (long)max_steps, g.lengths_out, g.score_out,
+                            steps_exec, g.alpha, B, g.K, V, max_steps, eos_id, g.pad_id};
+    return a2s_beam_backtrack_impl(ST, a);
+}
+int a2s_beam_launches(void) { return a2s_beam_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

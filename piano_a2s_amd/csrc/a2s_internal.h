@@ -196,6 +196,36 @@ int a2s_grammar_argmax_rows_impl(hipStream_t st, const float* x, long ldx, float
 int a2s_grammar_step_finalize_impl(hipStream_t st, const StepFinArgs& a, const a2s_grammar_ref& g);
 int a2s_grammar_launches_impl(void);
 
+// ---- a2s_beam.hip
+// argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
+struct BeamStepArgs {
+    const float* logits; long ldl;        // (K * B, V)
+    const float* emb;                     // (V, E) embedding table
+    float* xnext; long ldx;               // next GRU input rows; token embedding -> columns [0, E)
+    float* h; int h_cols;                 // what the next step reads of this one per row, permuted in place: the state rows ...
+    float* q; int q_cols;                 // ... and the next step's query rows where the step kernels have left them behind (or null)
+    const signed char* next; int n_states; int* row_state;     // the grammar (a2s_grammar_ref), next null: none
+    float* score; int* finished; int* done_count;
+    int* token_hist; int* parent_hist; float* score_hist;      // (max_t, K * B)
+    float* probs_scratch;                 // (K * B, max_t, V)
+    int* n_done; int* steps_exec;
+    int B, K, V, E, t, max_t, eos_id, pad_id;
+};
+struct BeamBackArgs {
+    const float* score; const int* token_hist; const int* parent_hist; const float* probs_scratch;
+    float* probs; long probs_bstride;     // clip b, step t at probs + b * probs_bstride + t * V
+    int* ids_out; long ids_bstride; long long* lengths_out; float* score_out;
+    const int* steps_exec;                // device: steps executed (null: max_t)
+    float alpha;
+    int B, K, V, max_t, eos_id, pad_id;
+};
+bool a2s_beam_args_ok(const a2s_beam_args& g, int R, int n_clips, int V);
+int a2s_beam_init_impl(hipStream_t st, const a2s_beam_args& g, int* n_done, int B, int steps);
+int a2s_beam_step_finalize_impl(hipStream_t st, const BeamStepArgs& a);
+int a2s_beam_backtrack_impl(hipStream_t st, const BeamBackArgs& a);
+int a2s_beam_launches_impl(void);
+int a2s_note_decoder_fwd_beam_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_beam_args& g, int* steps_done);
+
 // ---- a2s_persist.hip
 unsigned* a2s_persist_latch_ptr(void);
 void a2s_persist_latch_set(void* p);

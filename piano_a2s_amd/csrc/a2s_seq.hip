@@ -518,7 +518,7 @@ static int enqueue_query(hipStream_t st, const NoteDecArgs& a, int si, int sv) {
 // of slot sv must already be there (enqueue_query / the previous step), this step leaves the next one's in slot sv_next (!last).
 static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int so, int sv, int t, const int* t_base, int tf,
                              bool fused = false, int sv_next = 0, bool last = false, const AttnPairStep* pair = nullptr,
-                             const a2s_grammar_ref* grammar = nullptr) {
+                             const a2s_grammar_ref* grammar = nullptr, const a2s_beam_args* beam = nullptr) {
     const int H2 = 2 * a.H, ldx = a.E + H2;
     if (fused) {
         float* xs = a.x + (long)si * a.R * ldx;
@@ -547,6 +547,13 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     int rc;
     a2s_attn_rows rows_v = {a.clip_order, a.clip_rank, a.row_until, a.n_clips > 0 ? a.n_clips : a.R, a.n_active ? a.n_active[t] : 0, t};
     const a2s_attn_rows* rows = a.n_active ? &rows_v : nullptr;
+    // beam search (a2s_beam.hip): the rows are K slots of n_clips clips, every clip running, in the order of the call -- the K rows of a clip share
+    // one pass over its key image and encoder rows (without this, row r would be read as clip r).  The kernels that fuse rows know no done
+    // counter: with more than one slot the sweep runs until the host's poll ends the loop.
+    const a2s_attn_rows rows_b = {nullptr, nullptr, nullptr, a.n_clips, a.n_clips, t};
+    if (beam) rows = &rows_b;
+    const int* attn_done = (a.gt || (beam && beam->K > 1)) ? nullptr : a.n_done;
+    float* q_left = nullptr;                  // the next step's query, where this step leaves it behind (a beam re-parents it with the state)
     if (note_step_mid(a, t_base)) {
         // round 6 (a2s_step.hip): the query of slot sv is already there (enqueue_query / the previous step, as on the few-row path); behind the
         // attention ONE launch for the GRU cell (dec_gru_mid: gh, gi, gates) and ONE for the logits and the next step's query (dec_outq_mid), over
@@ -554,11 +561,12 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
         // (pair: the sweep of this step has been launched for both staves at once -- only this staff's combine is left)
         rc = pair ? attn_pair_combine(st, a, si, sv, *pair)
                   : a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2,
-                                           a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, a.gt ? nullptr : a.n_done, a.R, a.attn_ws, rows);
+                                           a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, attn_done, a.R, a.attn_ws, rows);
         if (rc) return rc;
         const int nrows = note_step_rows(a, t);
         rc = a2s_note_step_mid_gru(st, a, si, so, sv, last ? -1 : sv_next, nrows, nrows < a.R ? a.row_list : nullptr);
         if (rc) return rc;
+        if (!last) q_left = a.q + (long)sv_next * a.R * a.H;
     } else {
     // q = h W_h^T + b   (W = [W_h | W_e], W_h = first 2H columns of the (H, 4H) matrix)
     rc = a2s_gemm_impl(st, gM, a.H, H2, 1.f, hp, H2, 1, a.attn_w, 1, 2 * H2, 0.f, qs, a.H, a.attn_b, 0, gB, gS * H2, 0, gS * a.H, 0, a.gemm_ws, a.gemm_ws_bytes);
@@ -568,7 +576,7 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     if (rc) return rc;
     // attention -> ctx into x[si][:, E:] and o[sv][:, 2H:]
     rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2,
-                                a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, a.gt ? nullptr : a.n_done, a.R, a.attn_ws,
+                                a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, attn_done, a.R, a.attn_ws,
                                 rows);
     if (rc) return rc;
     // gi = x W_ih^T + b_ih
@@ -581,6 +589,13 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     // logits = o W_out^T + b_out
     rc = a2s_gemm_impl(st, gM, a.V, 2 * H2, 1.f, os, 2 * H2, 1, a.out_w, 1, 2 * H2, 0.f, a.logits, a.V, a.out_b, 0, gB, gS * 2 * H2, 0, gS * a.V, 0, a.gemm_ws, a.gemm_ws_bytes);
     if (rc) return rc;
+    }
+    if (beam) {
+        const a2s_beam_args& g = *beam;
+        const BeamStepArgs bs = {a.logits, a.V, a.emb, a.x + (long)so * a.R * ldx, ldx, hq, H2, q_left, a.H, g.next_state, g.n_states, g.row_state, g.score, g.finished,
+                                 g.done_count, g.token_hist, g.parent_hist, g.score_hist, g.probs_scratch, a.n_done, a.steps_exec, a.n_clips, g.K, a.V, a.E, t, a.steps,
+                                 a.eos_id, g.pad_id};
+        return a2s_beam_step_finalize_impl(st, bs);
     }
     StepFinArgs f;
     f.logits = a.logits; f.ldl = a.V; f.probs = a.probs; f.probs_bstride = a.probs_bstride;
@@ -692,6 +707,40 @@ int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, cons
     A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_grammar: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
     A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_grammar: null bookkeeping or output buffers");
     return note_decoder_fwd_loop(st, a, steps_done, &g);
+}
+
+// Beam search over one greedy call: K slots per clip as extra rows, the launch-per-step loop with the beam
+// epilogue, then the pick and the walk back.  The query a mid-size step leaves behind is re-parented by the epilogue together with the state.
+// Nothing is kept for a backward pass: state, input, query and output rows ping-pong between two slots (step parity), as in graph replay.
+int a2s_note_decoder_fwd_beam_impl(hipStream_t st, const NoteDecArgs& a, const a2s_beam_args& g, int* steps_done) {
+    A2S_REQUIRE(!a.gt && !a.tf_flags_dev, "note_decoder_fwd_beam: greedy decoding only (ground truth given)");
+    A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list && !a.m_active && !a.clip_order && !a.row_until,
+                "note_decoder_fwd_beam: inference only (training buffers or row bookkeeping given)");
+    A2S_REQUIRE(a2s_beam_args_ok(g, a.R, a.n_clips, a.V), "note_decoder_fwd_beam: needs 1 <= K <= %d, R = K * n_clips, V <= 256, a table of 1..127 states or none, and "
+                "every beam buffer (got K = %d, R = %d, n_clips = %d, V = %d, %d states)", A2S_BEAM_MAX, g.K, a.R, a.n_clips, a.V, g.n_states);
+    A2S_REQUIRE(g.ids_out && g.lengths_out && g.score_out, "note_decoder_fwd_beam: null output buffers");
+    A2S_REQUIRE(a.steps >= 0 && a.n_done && a.logits && a.probs && a.h && a.x && a.q && a.o, "note_decoder_fwd_beam: null bookkeeping or output buffers");
+    int rc = a2s_beam_init_impl(st, g, a.n_done, a.n_clips, a.steps);
+    if (rc) return rc;
+    const bool mid = note_step_mid(a, nullptr);
+    int s = 0;
+    for (; s < a.steps; ++s) {
+        if (mid && s == 0) { rc = enqueue_query(st, a, 0, 0); if (rc) return rc; }     // every later query is left behind by the previous step
+        rc = enqueue_note_step(st, a, s & 1, (s + 1) & 1, s & 1, s, nullptr, 0, false, (s + 1) & 1, s + 1 == a.steps, nullptr, nullptr, &g);
+        if (rc) return rc;
+        if (a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
+            int done = 0;
+            hipError_t e = hipMemcpyAsync(&done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_beam poll: %s", hipGetErrorString(e));
+            if (done >= a.R) { ++s; break; }
+        }
+    }
+    const BeamBackArgs bk = {g.score, g.token_hist, g.parent_hist, g.probs_scratch, a.probs, a.probs_bstride, g.ids_out, (long)a.steps, g.lengths_out, g.score_out,
+                             a.steps_exec, g.alpha, a.n_clips, g.K, a.V, a.steps, a.eos_id, g.pad_id};
+    if (a.steps > 0) { rc = a2s_beam_backtrack_impl(st, bk); if (rc) return rc; }
+    if (steps_done) *steps_done = s;
+    return A2S_OK;
 }
 
 // The two NoteDecoders of a segment (models.py:261-275) decoded by ONE host loop on their two streams: while both staves run a step on the

@@ -104,6 +104,9 @@ _BAR_ATTN_WS = {}
 # the round-4 persistent note decoder for the last clip group also while another group decodes beside it (tests only: it owns every CU it runs on
 # and stops the bulk group there -- 540 against 514 ms per step, profiles/r04_dec_persist_beside_bulk.txt)
 _PERSIST_BESIDE = False
+# the beam-search loop (csrc/a2s_beam.hip) also at Engine.beam_size == 1 (tests only: one slot under the kern grammar is the constrained greedy decoder
+# bit for bit, which pins the loop, the epilogue and the walk back to an already-tested path)
+_BEAM_FORCE = False
 _PAIR_STAVES = True             # group 0's two staves issued by one host loop, their sweeps sharing the encoder-output reads (Engine._decode_pair)
 
 
@@ -320,6 +323,13 @@ class Engine:
         # forward `decoded` = {"up": (ids (B, bars, U) int32, lengths (B, bars) int64), "lo": ...}, None otherwise
         self.kern_grammar = None
         self.decoded = None
+        # beam search over the note sequences of every (bar, staff) call: beam_size slots per clip, 1 .. 4; 1 = greedy, and
+        # nothing of the beam path is touched.  With >= 2 the greedy, non-training calls keep each clip's best hypothesis under
+        # score / len^beam_length_penalty; `decoded` is set as under the grammar (which composes with the beam) and
+        # `beam_scores` = {"up": (B, bars) float32 sums of the emitted tokens' log-probabilities, "lo": ...}, None otherwise
+        self.beam_size = 1
+        self.beam_length_penalty = 0.0
+        self.beam_scores = None
         # Synchronised BatchNorm (what SpeechBrain's DDP wrapping gives the reference): batch statistics over the
         # GLOBAL minibatch -- per-channel (sum, sum of squares, count) are all-reduced between the ranks.  Off by default:
         # per-rank statistics (plain DDP semantics).  Needs an initialised process group.
@@ -516,6 +526,10 @@ class Engine:
             if grammar.vocab_size != V:
                 raise hip.A2SError(f"Engine.kern_grammar is a table over {grammar.vocab_size} symbols, the decoder's vocabulary has {V}")
             persist = False
+        if gt_bar is None and not training and self._beam_slots():
+            if active is not None or defer_launch:
+                raise hip.A2SError("beam search decodes bar by bar: no fused bars, no pair loop")
+            return self._decode_staff_beam(S, prefix, keys, enc, h0, max_steps, probs_bar, n, B, T, grammar, self._beam_slots())
         t_base = torch.zeros(1, dtype=torch.int32, device=dev) if graph else None
         # (with row_list the tail steps write only the rows still running; a2s_note_decoder_fwd zero-fills these buffers itself -- from C,
         # where a memset that has to wait for room in a busy stream's queue does not hold the interpreter lock)
@@ -604,6 +618,60 @@ class Engine:
             return ids_, lengths_, saved
         hip.check(L.a2s_note_decoder_fwd(hip.stream(), C.byref(a), C.byref(done)), "a2s_note_decoder_fwd")
         return finish(done.value)
+
+    def _beam_slots(self):
+        """Beam slots per clip of the greedy calls, 0 = the beam path is not taken."""
+        K = self.beam_size
+        if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= 4:
+            raise ValueError(f"Engine.beam_size must be an integer in 1 .. 4 (got {K!r})")
+        return K if (K >= 2 or _BEAM_FORCE) else 0
+
+    def _decode_staff_beam(self, S, prefix, keys, enc, h0, max_steps, probs_bar, n, B, T, grammar, K):
+        """_decode_staff for a greedy call under beam search (csrc/a2s_beam.hip): K slots per clip as K * B rows, row = slot * B + clip, the
+        launch-per-step loop with the beam epilogue, then the pick and the walk back.  -> ids (B, max_steps) int32, lengths (B,), saved."""
+        L = hip.lib()
+        H, E, V = self.cfg["hidden_size"], self.cfg["note_emb_size"], VOCAB_SIZE
+        H2, ldx = 2 * H, E + 2 * H
+        dev = enc.device
+        R = K * B
+        # (nothing is kept for a backward pass: state, input, query and output rows ping-pong between two slots)
+        h = self._empty(2, R, H2, dev=dev)
+        h[0].view(K, B, H2).copy_(h0.unsqueeze(0).expand(K, B, H2))
+        x = self._empty(2, R, ldx, dev=dev)
+        q = self._empty(2, R, H, dev=dev)
+        o = self._empty(2, R, 2 * H2, dev=dev)
+        gh, gi = self._empty(R, 3 * H2, dev=dev), self._empty(R, 3 * H2, dev=dev)
+        logits = self._empty(R, V, dev=dev)
+        n_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        steps_exec = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S[prefix + ".embedding.weight"]), C.c_void_p(0), C.c_void_p(0), C.c_long(0), SOS,
+                                   hip._p(x), C.c_long(ldx), 0, R, E, C.c_void_p(0), hip.f32(1.0)), "a2s_embed_rows")
+        # scratch of the call's own: the K rows of a clip share one attention sweep (fused rows), which the bar-by-bar workspaces are not sized for
+        attn_ws = hip.attn_workspace(B, T, H, dev, groups=K)
+        gemm_ws = hip.gemm_workspace(R, dev)
+        step_ws = hip.step_workspace(H, E, dev)
+        g, bt = hip.beam_buffers(B, K, max_steps, V, dev, PAD, table=grammar.device_table(dev) if grammar is not None else None,
+                                 start=grammar.start if grammar is not None else 0, alpha=self.beam_length_penalty)
+        a = hip.NoteDecArgs()
+        for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_b", S[prefix + ".attn.attn.bias"]),
+                        ("attn_v", S[prefix + ".attn.v.weight"]), ("w_ih", S[prefix + ".gru.weight_ih_l0"]),
+                        ("w_hh", S[prefix + ".gru.weight_hh_l0"]), ("b_ih", S[prefix + ".gru.bias_ih_l0"]),
+                        ("b_hh", S[prefix + ".gru.bias_hh_l0"]), ("out_w", S[prefix + ".out.weight"]), ("out_b", S[prefix + ".out.bias"]),
+                        ("emb", S[prefix + ".embedding.weight"]), ("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q), ("o", o), ("gh", gh),
+                        ("gi", gi), ("logits", logits), ("n_done", n_done), ("steps_exec", steps_exec), ("attn_ws", attn_ws), ("gemm_ws", gemm_ws)):
+            setattr(a, name, t.data_ptr() if t is not None else None)
+        a.gemm_ws_bytes = gemm_ws.numel() * 4
+        a.step_ws, a.step_ws_floats = step_ws.data_ptr(), step_ws.numel()
+        a.probs, a.probs_bstride = probs_bar.data_ptr(), probs_bar.stride(0)
+        a.inv_keep, a.am_bstride, a.n_clips = 1.0, max_steps, B
+        a.R, a.T, a.H, a.E, a.V, a.steps, a.poll, a.eos_id, a.use_graph = R, T, H, E, V, n, self.poll, EOS, 0
+        done = C.c_int(0)
+        hip.check(L.a2s_note_decoder_fwd_beam(hip.stream(), C.byref(a), C.byref(g), C.byref(done)), "a2s_note_decoder_fwd_beam")
+        executed = int(steps_exec.item())
+        saved = dict(h=h, x=x, q=q, o=o, gates=None, attw=None, drop=None, steps=executed, launched=done.value, ids=bt["ids_out"], gt_bar=None, prefix=prefix,
+                     max_steps=max_steps, attn_ws=attn_ws, gemm_ws=gemm_ws, step_ws=step_ws, logits=logits, gh=gh, gi=gi, n_done=n_done, beam=bt, beam_size=K,
+                     row_state=bt["row_state"])
+        return bt["ids_out"], bt["lengths_out"], saved
 
     def _decode_pair(self, calls, streams, pair):
         """The two NoteDecoder calls of a segment (models.py:261-275) issued by ONE host loop: calls = the argument tuples of _decode_staff for the
@@ -738,8 +806,10 @@ class Engine:
 
         tokw = 4 * Sz + te + ke
         ldxb = tokw + 2 * H
-        greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH)
-        constrained = self.kern_grammar is not None and gt_cpu is None and not training     # (the persistent decoder's epilogue holds its own argmax)
+        # beam search (csrc/a2s_beam.hip) runs the launch-per-step loop only: no graph replay, no persistent decoder
+        beam = gt_cpu is None and not training and self._beam_slots() > 0
+        greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH) and not beam
+        constrained = (self.kern_grammar is not None or beam) and gt_cpu is None and not training     # (the persistent decoder's epilogue holds its own argmax)
         # the two staves of a segment run on two streams, each issued by its own host thread -- also in greedy decoding, where each
         # thread polls the done counter of its own stream (the hipGraph variant captures on one created stream and stays sequential)
         concurrent = getattr(self, "concurrent_staves", True) and not greedy_graph
@@ -1055,6 +1125,9 @@ class Engine:
             segs = group_saved[0]["segments"]
             self.decoded = {k: (torch.stack([sg["staff"][k][0] for sg in segs], dim=1), torch.stack([sg["staff"][k][1] for sg in segs], dim=1))
                             for k in ("up", "lo")}
+        self.beam_scores = None
+        if beam:
+            self.beam_scores = {k: torch.stack([sg["staff"][k][2]["beam"]["score_out"] for sg in group_saved[0]["segments"]], dim=1) for k in ("up", "lo")}
         self.saved = dict(conv=conv_saved, enc=enc_saved, keys=keys, groups=group_saved, enc_out=enc,
                           bars=group_saved[0]["bars"], segments=group_saved[0]["segments"], sos_rec=group_saved[0]["sos_rec"],
                           training=training, concurrent=concurrent, outs=(ts_out, key_out, up_out, lo_out), bar_major=bar_major,

@@ -36,6 +36,13 @@ class NoteDecArgs(C.Structure):
         ("tf_flags_dev", C.c_void_p), ("persist_ws", C.c_void_p), ("persist_ws_bytes", C.c_size_t)]
 
 
+class BeamArgs(C.Structure):
+    """Mirror of `a2s_beam_args` (include/a2s.h) -- same members, same order."""
+    _fields_ = [("K", C.c_int), ("alpha", C.c_float), ("next_state", C.c_void_p), ("n_states", C.c_int), ("pad_id", C.c_int)] + [
+        (n, C.c_void_p) for n in ("row_state", "score", "finished", "done_count", "token_hist", "parent_hist", "score_hist", "probs_scratch",
+                                  "ids_out", "lengths_out", "score_out")]
+
+
 class NoteDecBwdArgs(C.Structure):
     """Mirror of `a2s_note_dec_bwd_args` (include/a2s.h) -- same members, same order."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -230,6 +237,55 @@ def grammar_argmax_rows(x, table, row_state, y=None, V=None):
 def grammar_launches():
     """Grammar step epilogues the library has launched in this process (a2s_grammar_launches)."""
     return int(lib().a2s_grammar_launches())
+
+
+def beam_buffers(B, K, max_steps, V, device, pad_id, table=None, start=0, alpha=0.0):
+    """The buffers of one beam-search call (a2s_beam_args) over B clips with K slots: -> (BeamArgs, dict of the tensors it points to).  Scores,
+    finished flags and counters are those of the start: slot 0 alive at 0, the others dead; a2s_note_decoder_fwd_beam sets them again itself."""
+    R = K * B
+    t = dict(row_state=torch.full((R,), start, dtype=torch.int32, device=device),
+             score=torch.full((R,), float("-inf"), dtype=torch.float32, device=device),
+             finished=torch.ones(R, dtype=torch.int32, device=device),
+             done_count=torch.zeros(max_steps + 1, dtype=torch.int32, device=device),
+             token_hist=torch.full((max_steps, R), pad_id, dtype=torch.int32, device=device),
+             parent_hist=torch.zeros((max_steps, R), dtype=torch.int32, device=device),
+             score_hist=torch.zeros((max_steps, R), dtype=torch.float32, device=device),
+             probs_scratch=torch.zeros((R, max_steps, V), dtype=torch.float32, device=device),
+             ids_out=torch.full((B, max_steps), pad_id, dtype=torch.int32, device=device),
+             lengths_out=torch.full((B,), max_steps, dtype=torch.long, device=device),
+             score_out=torch.zeros(B, dtype=torch.float32, device=device))
+    t["score"][:B] = 0
+    t["finished"][:B] = 0
+    t["done_count"][0] = (K - 1) * B
+    g = BeamArgs()
+    g.K, g.alpha, g.pad_id = K, float(alpha), pad_id
+    if table is not None:
+        if table.dtype != torch.int8 or not table.is_contiguous() or table.shape[1] != V:
+            raise A2SError("beam_buffers: expects a contiguous int8 table of (n_states, V)")
+        g.next_state, g.n_states = table.data_ptr(), table.shape[0]
+        t["table"] = table
+    else:
+        g.next_state, g.n_states = None, 0
+    for name in ("row_state", "score", "finished", "done_count", "token_hist", "parent_hist", "score_hist", "probs_scratch", "ids_out", "lengths_out", "score_out"):
+        setattr(g, name, t[name].data_ptr())
+    return g, t
+
+
+def beam_step(g, logits, emb, xnext, h, q, n_done, steps_exec, B, t, max_steps, eos_id, V=None):
+    """a2s_beam_step: one beam step epilogue over logits (K * B, >= V); h (K * B, cols) and q (or None) are re-parented in place."""
+    V = logits.shape[1] if V is None else V
+    check(lib().a2s_beam_step(stream(), C.byref(g), _p(logits), C.c_long(logits.stride(0)), _p(emb), _p(xnext), C.c_long(xnext.stride(0)), _p(h), h.shape[1],
+                              _p(q), q.shape[1] if q is not None else 0, _p(n_done), _p(steps_exec), B, V, emb.shape[1], t, max_steps, eos_id), "a2s_beam_step")
+
+
+def beam_backtrack(g, probs, steps_exec, B, V, max_steps, eos_id):
+    """a2s_beam_backtrack: the pick and the walk back; probs (B, max_steps, V) receives the winning lineage's log-probabilities."""
+    check(lib().a2s_beam_backtrack(stream(), C.byref(g), _p(probs), C.c_long(probs.stride(0)), _p(steps_exec), B, V, max_steps, eos_id), "a2s_beam_backtrack")
+
+
+def beam_launches():
+    """Beam step epilogues the library has launched in this process (a2s_beam_launches)."""
+    return int(lib().a2s_beam_launches())
 
 
 def check(rc, what):

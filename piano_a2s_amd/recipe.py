@@ -59,7 +59,24 @@ class ASR(sb.Brain):
         v = getattr(self.hparams, "constrained_decoding", False)
         return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
 
+    def _beam_size(self):
+        """--beam_size=K (an optional override as --constrained_decoding): VALID / TEST decode by beam search with K hypotheses per clip; 1 = greedy."""
+        return int(getattr(self.hparams, "beam_size", 1))
+
+    def _set_beam(self):
+        K = self._beam_size()
+        if not 1 <= K <= 4:
+            raise ValueError(f"--beam_size must be in 1 .. 4 (got {K})")
+        if K == 1:
+            return
+        model = self.modules.transcription
+        model = getattr(model, "module", model)                      # (a DistributedDataParallel wrapper)
+        if not hasattr(model, "beam_size"):
+            raise ValueError(f"--beam_size needs a transcription module that decodes by beam search; {type(model).__name__} has no `beam_size` attribute")
+        model.beam_size, model.beam_length_penalty = K, float(getattr(self.hparams, "beam_length_penalty", 0.0))
+
     def _set_constrained_decoding(self):
+        self._set_beam()
         if not self._constrained():
             return
         model = self.modules.transcription
@@ -94,8 +111,8 @@ class ASR(sb.Brain):
     def _record_predictions(self, predictions, targets, names, versions):
         ts_o, key_o, up_o, lo_o = predictions
         ts_t, key_t, up_t, lo_t = targets
-        if self._constrained():
-            # the ids the constrained decoder EMITTED (the log-probabilities stay the unconstrained ones, their argmax is not what was decoded)
+        if self._constrained() or self._beam_size() >= 2:
+            # the ids the constrained / beam decoder EMITTED (the log-probabilities stay the unconstrained ones, their argmax is not what was decoded)
             model = self.modules.transcription
             decoded = getattr(model, "module", model).last_decoded
             up_ids, lo_ids = decoded["up"][0].cpu().numpy(), decoded["lo"][0].cpu().numpy()

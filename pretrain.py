@@ -3,7 +3,8 @@
 ``torchrun --nproc_per_node=N pretrain.py hparams/pretrain.yaml ...`` (one process per GPU, RCCL).
 
 Same command line, yaml keys and recipe hooks as the reference's pretrain.py (:251-305); the recipe class lives in
-piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic clips instead of a rendered corpus."""
+piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic clips instead of a rendered corpus.  Optional overrides of the
+VALID / TEST decoder: ``--constrained_decoding=true`` (kern grammar), ``--beam_size=K [--beam_length_penalty=A]`` (beam search, K in 1 .. 4)."""
 import sys
 
 from piano_a2s_amd.recipe import ASR, sb, write_run_summary

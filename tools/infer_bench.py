@@ -7,7 +7,11 @@ weights with <eos> bias so decoding terminates at data-dependent steps.  Prints 
     infer_bench.py [B] --constrained    greedy under the kern token grammar (Engine.kern_grammar)
     infer_bench.py --compare OUT.json [--batches 256,8] [--repeats 3]
                                         the three variants in ONE process, alternating, `repeats` timed forwards each (after one warm-up each):
-                                        one JSON line per forward, the summary (median, spread) to OUT.json"""
+                                        one JSON line per forward, the summary (median, spread) to OUT.json
+    infer_bench.py --compare OUT.json --beam [--batches 256,8] [--repeats 3]
+                                        the same for beam search (Engine.beam_size), all under the kern grammar: constrained
+                                        greedy on the launch-per-step loop (the like-for-like baseline, run twice per round: its spread against
+                                        itself is the margin of every comparison), the beam loop forced at K = 1, K = 2 and K = 4"""
 import argparse
 import json
 import os
@@ -26,6 +30,7 @@ ap.add_argument("batch", nargs="?", type=int, default=64)
 ap.add_argument("--constrained", action="store_true")
 ap.add_argument("--stepwise", action="store_true")
 ap.add_argument("--compare", metavar="OUT.json")
+ap.add_argument("--beam", action="store_true")
 ap.add_argument("--batches", default="256,8")
 ap.add_argument("--repeats", type=int, default=3)
 args = ap.parse_args()
@@ -43,15 +48,20 @@ def set_stepwise(on):
 
 
 def forward(x, variant):
-    """One timed forward of `variant` ("greedy", "stepwise" or "constrained") -> the record of the run."""
+    """One timed forward of `variant` ("greedy", "stepwise", "constrained", "constrained_again", "beam1", "beam2" or "beam4") -> the record of the run."""
     set_stepwise(variant == "stepwise")
     eng = engine.Engine(cfg)
-    eng.kern_grammar = GRAMMAR if variant == "constrained" else None
-    n0, g0 = L.a2s_launch_count(), hip.grammar_launches()
+    eng.kern_grammar = GRAMMAR if variant.startswith(("constrained", "beam")) else None
+    eng.beam_size = int(variant[4:]) if variant.startswith("beam") else 1
+    engine._BEAM_FORCE = variant == "beam1"                 # one slot through the beam loop: what the loop itself costs
+    n0, g0, b0 = L.a2s_launch_count(), hip.grammar_launches(), hip.beam_launches()
     torch.cuda.synchronize(); t0 = time.time()
-    with torch.no_grad():
-        ts, key, up, lo = eng.forward(S, x, inference=True)
-    torch.cuda.synchronize(); dt = time.time() - t0
+    try:
+        with torch.no_grad():
+            ts, key, up, lo = eng.forward(S, x, inference=True)
+        torch.cuda.synchronize(); dt = time.time() - t0
+    finally:
+        engine._BEAM_FORCE = False
     set_stepwise(False)
     B = x.shape[0]
     calls = [b["staff"][k][2] for b in eng.saved["bars"] for k in ("up", "lo")]
@@ -68,19 +78,22 @@ def forward(x, variant):
             "us_per_executed_step": round(1e6 * dt / max(steps, 1), 2),
             # every launch of the forward (ConvStack, encoder and bar level included) over the decode steps it launched
             "launches_per_launched_step": round((L.a2s_launch_count() - n0) / max(launched, 1), 2),
-            "grammar_epilogues": hip.grammar_launches() - g0, "persistent_calls": sum(c.get("persist_ws") is not None for c in calls),
+            "grammar_epilogues": hip.grammar_launches() - g0, "beam_epilogues": hip.beam_launches() - b0, "persistent_calls": sum(c.get("persist_ws") is not None for c in calls),
             "well_formed_bar_share": round(legal_share(rows, GRAMMAR), 4)}
 
 
 if args.compare:
-    variants = ("greedy", "stepwise", "constrained")
-    summary = {"what": "tools/infer_bench.py --compare: greedy as shipped / forced onto the launch-per-step loop / under the kern grammar; "
-                       "one process, variants alternating, median of the timed forwards", "repeats": args.repeats, "batches": {}}
+    variants = ("constrained", "constrained_again", "beam1", "beam2", "beam4") if args.beam else ("greedy", "stepwise", "constrained")
+    what = ("constrained greedy on the launch-per-step loop (twice: its spread against itself) / the beam loop at K = 1 (forced), 2 and 4, all under the "
+            "kern grammar" if args.beam else "greedy as shipped / forced onto the launch-per-step loop / under the kern grammar")
+    summary = {"what": f"tools/infer_bench.py --compare: {what}; one process, variants alternating, median of the timed forwards", "repeats": args.repeats,
+               "batches": {}}
     for B in [int(b) for b in args.batches.split(",")]:
         x = synthetic.make_batch(B, cfg, 77, spectrogram="ridges", full_tail=0.0)[0].to(dev)
         runs = {v: [] for v in variants}
         for v in variants:
             forward(x, v)                                   # warm-up
+            torch.cuda.empty_cache()                        # (a beam call holds K times the buffers of a greedy one)
         for _ in range(args.repeats):
             for v in variants:
                 rec = forward(x, v)
