@@ -158,9 +158,9 @@ int a2s_conv3x3_dgrad_bnstats_scaled(void* stream, const float* dy, const float*
                                      const float* yl_scale, const float* yl_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout,
                                      float* workspace, const float* dy_absmax);
 /* Round 4: the same, also writing the range of the gradient it writes into g_absmax_out[Cout] (the launch zeroes it): the MAXIMUM over the Cout
- * entries is max |g| exactly, every entry is >= 0 and none exceeds that maximum -- nothing more (the row-streaming kernels keep one running
- * maximum per lane whatever the channel, so an entry is NOT the maximum of its channel; only the 20 -> 20 launch and the tiled kernels, which
- * run a per-channel pass, happen to write max |g_c|).  The consumer, a2s_conv3x3_wgrad_bn_ranged (g_absmax, g_absmax_n = Cout), takes the
+ * entries is max |g| exactly, every entry is >= 0 and none exceeds that maximum -- nothing more (the first-generation row-streaming kernels keep
+ * one running maximum per lane whatever the channel, so an entry is NOT the maximum of its channel; conv3x3_rows16, one channel per lane, and the
+ * tiled kernels, which run a per-channel pass, happen to write max |g_c|).  The consumer, a2s_conv3x3_wgrad_bn_ranged (g_absmax, g_absmax_n = Cout), takes the
  * maximum over the entries to bound the BatchNorm backward of the layer below. */
 int a2s_conv3x3_dgrad_bnstats_ranged(void* stream, const float* dy, const float* w, float* g, const float* yl, const float* yl_mean, const float* yl_invstd,
                                      const float* yl_scale, const float* yl_shift, float* stat_partial, int B, int T, int F, int Cin, int Cout,

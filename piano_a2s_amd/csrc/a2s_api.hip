@@ -101,6 +101,7 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
     if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
     if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
+    if (!strcmp(key, "conv_rows16_c20_launches")) return (int)a2s_conv_rows16_c20_launches();
     if (!strcmp(key, "device_cus")) return a2s_device_geometry().cus;
     if (!strcmp(key, "device_xccs")) return a2s_device_geometry().xccs;
     return -1;

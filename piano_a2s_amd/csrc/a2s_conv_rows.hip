@@ -586,7 +586,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows(RowsArgs a) {
 }
 
 // =========================================================================================== rows16
-// Second generation of the row-streaming kernel (Cout = 40 launches): the n-tiles are [df][16 output channels] -- tile (cg, df) holds
+// Second generation of the row-streaming kernel (every launch: Cout = 40 and Cout = 20): the n-tiles are [df][16 output channels] -- tile (cg, df) holds
 // D_df of the 16 channels of channel group cg, one channel per lane -- so the df-combination out[p][co] = D0[p-1] + D1[p] + D2[p+1] adds
 // three ACCUMULATOR REGISTERS OF THE SAME LANE (the row shift p +- 1 is a register rename inside a lane's 4 rows, one lane permute per
 // quad for the rows that cross a 16-lane group), every lane finishes an output channel, and a store writes 64 lanes x 16 B.  The first
@@ -599,24 +599,47 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows(RowsArgs a) {
 //   * one output row per iteration, ring of 4 slots, ONE barrier per row: all waves multiply (row t + 2 is converted into the free slot
 //     between the k-steps), barrier, epilogue + next row's loads;
 //   * both weight terms live in registers (96).
-// One block per n-tile: 0-5 = (group cg, df) of groups 0 / 1, 6 = [df0 | df1] and 7 = [df2 | idle] of group 2.
+// In general (R16Geom): Cout = 16 NWG + R channels are NWG groups of 16 and a remainder ("narrow") group of R, whose three df share
+// ceil(3 R / 16) tiles, R lanes per df.  Waves 0-3 split the 8 m-tiles of the strip among the NWG wide groups (4 / NWG column ranges per
+// group), waves 4-7 take a column quarter of the narrow group each.
+//   * 20 channels = one group of 16 (3 tiles) + one of 4 in ONE tile ([df0 x 4 | df1 x 4 | df2 x 4 | idle x 4]: D1 and D2 reach lanes
+//     0-3 from lanes + 4 and + 8 by DPP row rotates): 4 n-tiles, as many as the first generation needs; waves 0-3 own a column QUARTER
+//     of the wide group (3 tiles x 2 m-tiles), waves 4-7 one of the narrow group (1 tile x 2 m-tiles): 6 + 2 = 8 tile products per SIMD,
+//     k-step and term product (96 MFMAs per row at Cin = 40), and half the accumulators of the 40-channel form.
+// One block per n-tile: tiles 3 cg + df = (group cg, df) of the wide groups, then the narrow group's (Cout = 40: 6 = [df0 | df1] and
+// 7 = [df2 | idle]; Cout = 20: 3 = [df0 | df1 | df2 | idle]).
 // wimg[(tile * KS + s) * 2 + term][lane * 16 + (4 r + e) * 2]; header as rows_pack.
+template <int COUT>
+struct R16Geom {
+    static_assert(COUT == 40 || COUT == 20, "rows16: 20 or 40 output channels");
+    static constexpr int NWG = COUT / 16;               // groups of 16 channels
+    static constexpr int WSPLIT = 4 / NWG;              // column ranges of a wide group (one wave each)
+    static constexpr int WNM = 8 / WSPLIT;              // m-tiles of a wide wave
+    static constexpr int R = COUT % 16;                 // channels of the narrow group
+    static constexpr int NNT = (3 * R + 15) / 16;       // its tiles
+    static constexpr int NTILES = 3 * NWG + NNT;
+    static constexpr int NWB = NWG * (WSPLIT - 1);      // boundaries between the column ranges of the wide groups; 3 more between the quarters
+    static constexpr int NBND = NWB + 3;
+};
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void rows16_pack(const float* __restrict__ w, int flip, const float* __restrict__ in_scale,
                                                    const float* __restrict__ in_shift, const float* __restrict__ in_absmax,
                                                    const float* __restrict__ x_absmax, unsigned char* __restrict__ wimg, float* __restrict__ hdr,
                                                    float* __restrict__ out_absmax) {
-    static_assert(COUT == 40, "rows16: 40 output channels");
     using G = RwGeom<CIN>;
+    using N = R16Geom<COUT>;
     __shared__ int kci[CIN];
     __shared__ float red[16];
     __shared__ int kw[16];
     const int tile = blockIdx.x, tid = threadIdx.x;
     // column li of this tile -> (output channel, df); co < 0: idle column
     auto column = [&](int li, int& co, int& df) {
-        if (tile < 6) { co = (tile / 3) * 16 + li; df = tile % 3; }
-        else if (tile == 6) { co = 32 + (li & 7); df = li >> 3; }
-        else { co = li < 8 ? 32 + li : -1; df = 2; }
+        if (tile < 3 * N::NWG) { co = (tile / 3) * 16 + li; df = tile % 3; }
+        else {      // narrow group: columns (df, channel) in runs of R over its tiles
+            const int c = (tile - 3 * N::NWG) * 16 + li;
+            df = c / N::R;
+            co = df < 3 ? 16 * N::NWG + c % N::R : -1;
+        }
     };
     if (tid < CIN) {
         int k = 0;
@@ -666,6 +689,11 @@ __global__ __launch_bounds__(256) void rows16_pack(const float* __restrict__ w, 
 __device__ __forceinline__ float rw_ror8(float x) {        // lane li of a 16-lane row receives lane (li + 8) % 16's value
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));
 }
+// ... lane (li + 4) % 16's value.  A row rotate moves values towards HIGHER lanes (as rw_shr1 does): receiving from 4 lanes up is a rotate
+// by 16 - 4 = 12, the mirror image of what the name of `row_ror:4` suggests.
+__device__ __forceinline__ float rw_rol4(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x12c, 0xf, 0xf, true));
+}
 
 #define R16_SLOTS 4
 // PIPE (round 6): the epilogue of output row t - 1 runs UNDER the multiply of row t.  The kernel above spends 3.1 k of its 7.0 k clocks per row
@@ -677,16 +705,21 @@ __device__ __forceinline__ float rw_ror8(float x) {        // lane li of a 16-la
 // instructions of an epilogue ride in the issue slots in between.  The barrier per row stays (ring slot hand-off, boundary rows).
 template <int CIN, int COUT, bool AFFINE, bool BNRED, bool PIPE = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
-    static_assert(COUT == 40, "rows16: 40 output channels");
     using G = RwGeom<CIN>;
+    using N = R16Geom<COUT>;
     constexpr int NTHR = 512, KS = G::KS;
+    constexpr int WNM = N::WNM, NNT = N::NNT;             // m-tiles of a wide wave (a narrow wave: 2), tiles of a narrow wave (a wide wave: 3)
+    // second weight term in LDS instead of registers: the two-set form, and the 20 -> 20 data gradient (138 registers otherwise: with the 24 of the
+    // term back it stays under 128, and two workgroups share a CU -- the instance has little else to cover its barrier per row with)
+    constexpr bool B1L = PIPE || (CIN == 20 && COUT == 20 && BNRED);
     constexpr int XIT = (G::ITEMS + NTHR - 1) / NTHR;
     __shared__ __attribute__((aligned(16))) unsigned char ring[R16_SLOTS * G::SLOT];
-    __shared__ __attribute__((aligned(16))) unsigned char b1img[PIPE ? 8 * G::KS * 1024 : 16];      // second fp16 term of the weights: [tile][k-step][lane x 16 B]
+    __shared__ __attribute__((aligned(16))) unsigned char b1img[B1L ? N::NTILES * G::KS * 1024 : 16];      // second fp16 term of the weights: [tile][k-step][lane x 16 B]
     // accumulator rows that cross the boundary between neighbouring column ranges of a channel group, as TRUE values (sign undone):
-    // [iteration parity][boundary: 0 / 1 = halves of group 0 / 1, 2..4 = quarters of group 2][0: left range's last row of D0 | 1: right
+    // [iteration parity][boundary: first those between the column ranges of the wide groups (Cout = 40: 0 / 1 = halves of group 0 / 1;
+    // Cout = 20: 0..2 = quarters of group 0), then the 3 between the quarters of the narrow group][0: left range's last row of D0 | 1: right
     // range's first row of D2][channel]
-    __shared__ float xch[2][5][2][16];
+    __shared__ float xch[2][N::NBND][2][16];
     __shared__ float red[8][16][3];
     __shared__ float tab[(AFFINE ? 2 * CIN : 0) + (BNRED ? 4 * COUT : 0) + 4];
     // where the threads without an item in the last staging round put their (meaningless) 8 + 8 bytes: the conversion then has no
@@ -696,14 +729,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane & 15, g = lane >> 4;
-    const bool wide = wave < 4;                           // waves 0-3: (group wave >> 1, half wave & 1); waves 4-7: quarter wave - 4 of group 2
-    const int m0 = wide ? 4 * (wave & 1) : 2 * (wave - 4); // first m-tile of the wave's column range
-    const int nm = wide ? 4 : 2;
-    const int tile0 = wide ? 3 * (wave >> 1) : 6;
+    const bool wide = wave < 4;                           // waves 0-3: (wide group wg, column range rng); waves 4-7: quarter wave - 4 of the narrow group
+    const int wg = wave / N::WSPLIT, rng = wave % N::WSPLIT;
+    const int m0 = wide ? WNM * rng : 2 * (wave - 4);     // first m-tile of the wave's column range
+    const int nm = wide ? WNM : 2;
+    const int tile0 = wide ? 3 * wg : 3 * N::NWG;
     const bool neg = wave & 1;                            // odd column ranges multiply by the negated weights (the matrix pipe's truncation
     const float sg = neg ? -1.f : 1.f;                    // bias then cancels between neighbouring ranges in every per-channel sum)
-    const int bnd_l = wide ? (wave & 1 ? (wave >> 1) : -1) : (wave > 4 ? wave - 3 : -1);      // boundary index to the left / right (-1: tile edge)
-    const int bnd_r = wide ? (wave & 1 ? -1 : (wave >> 1)) : (wave < 7 ? wave - 2 : -1);
+    const int bnd_l = wide ? (rng > 0 ? wg * (N::WSPLIT - 1) + rng - 1 : -1) : (wave > 4 ? N::NWB + wave - 5 : -1);      // boundary index to the left / right (-1: tile edge)
+    const int bnd_r = wide ? (rng < N::WSPLIT - 1 ? wg * (N::WSPLIT - 1) + rng : -1) : (wave < 7 ? N::NWB + wave - 4 : -1);
 
     int bid = blockIdx.x;
     {
@@ -715,9 +749,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     const int f_base = ft * RW_P;
     const int t_lo = strip * a.strip_len, t_hi = min(a.T, t_lo + a.strip_len);
 
-    // ---- weights: both terms of the wave's tiles (3 or 2), all k-steps
+    // ---- weights: both terms of the wave's tiles (3, or the narrow group's NNT), all k-steps
     const unsigned sgn = neg ? 0x80008000u : 0u;
-    constexpr int BWT = PIPE ? 1 : 2;                       // weight terms kept in registers
+    constexpr int BWT = B1L ? 1 : 2;                        // weight terms kept in registers
     s16x8 bw[3][KS][BWT];
 #pragma unroll
     for (int d = 0; d < 3; ++d)
@@ -725,25 +759,25 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
         for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int tm = 0; tm < BWT; ++tm) {
-                uint4 v = *reinterpret_cast<const uint4*>(a.wimg + ((size_t)((tile0 + ((wide || d < 2) ? d : 0)) * KS + s) * 2 + tm) * 1024 + lane * 16);
+                uint4 v = *reinterpret_cast<const uint4*>(a.wimg + ((size_t)((tile0 + ((wide || d < NNT) ? d : 0)) * KS + s) * 2 + tm) * 1024 + lane * 16);
                 v.x ^= sgn; v.y ^= sgn; v.z ^= sgn; v.w ^= sgn;
                 bw[d][s][tm] = __builtin_bit_cast(s16x8, v);
             }
-    if (PIPE) {
-        for (int e = tid; e < 8 * KS * 64; e += NTHR)
+    if (B1L) {
+        for (int e = tid; e < N::NTILES * KS * 64; e += NTHR)
             *reinterpret_cast<uint4*>(b1img + (size_t)e * 16) = *reinterpret_cast<const uint4*>(a.wimg + ((size_t)(e >> 6) * 2 + 1) * 1024 + (e & 63) * 16);
     }
     // second weight term of tile d, k-step s (this wave's sign)
     auto bterm1 = [&](int d, int s) -> s16x8 {
-        if (PIPE) {
-            uint4 v = *reinterpret_cast<const uint4*>(b1img + ((tile0 + ((wide || d < 2) ? d : 0)) * KS + s) * 1024 + lane * 16);
+        if (B1L) {
+            uint4 v = *reinterpret_cast<const uint4*>(b1img + ((tile0 + ((wide || d < NNT) ? d : 0)) * KS + s) * 1024 + lane * 16);
             v.x ^= sgn; v.y ^= sgn; v.z ^= sgn; v.w ^= sgn;
             return __builtin_bit_cast(s16x8, v);
         }
         return bw[d][s][BWT - 1];
     };
-    const int co = wide ? (wave >> 1) * 16 + q : 32 + (q & 7);      // this lane's output channel
-    const bool useful = wide || q < 8;
+    const int co = wide ? wg * 16 + q : 16 * N::NWG + (q & (N::R - 1));      // this lane's output channel
+    const bool useful = wide || q < N::R;
     const float xscale = a.hdr[120];
     const float unsc = useful ? a.hdr[80 + co] / xscale * sg : 0.f;
     if (AFFINE && tid < 2 * CIN) tab[tid] = a.hdr[tid < CIN ? tid : 40 + tid - CIN];
@@ -808,7 +842,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
         *reinterpret_cast<uint2*>(p1) = t1;
     };
 
-    f32x4 acc[4][3];                                     // [m-tile][tile of the wave]
+    f32x4 acc[WNM][3];                                   // [m-tile][tile of the wave]
+    // D0 / D1 / D2 of m-tile i, row r, from an accumulator set A[m-tile][tile][row].  WIDE: tiles 0 / 1 / 2, same lane.  Narrow, R = 8:
+    // D0 = tile 0 lanes 0-7, D1 = tile 0 lanes 8-15 (row rotate by 8), D2 = tile 1 lanes 0-7; R = 4: all in tile 0, D1 / D2 from lanes + 4 / + 8.
+    // (row r of the wave's tiles t0 / t1 / t2 of the m-tile)
+    auto dterm1 = [](auto WIDEc, const f32x4 t0, const f32x4 t1, int r) -> float {
+        if constexpr (decltype(WIDEc)::value) return t1[r];
+        else if constexpr (N::R == 8) return rw_ror8(t0[r]);
+        else return rw_rol4(t0[r]);
+    };
+    auto dterm2 = [](auto WIDEc, const f32x4 t0, const f32x4 t1, const f32x4 t2, int r) -> float {
+        if constexpr (decltype(WIDEc)::value) return t2[r];
+        else if constexpr (N::R == 8) return t1[r];
+        else return rw_ror8(t0[r]);
+    };
     // NM m-tiles x NT tiles; the conversion of input row crow (held in xr) rides between the k-steps
     auto multiply = [&](auto NMc, auto NTc, int crow, int cslot, const f32x4 (&xr)[XIT]) {
         constexpr int NM = decltype(NMc)::value, NT = decltype(NTc)::value;
@@ -820,6 +867,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             for (int d = 0; d < NT; ++d) acc[i][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
+            s16x8 b1[NT];
+#pragma unroll
+            for (int d = 0; d < NT; ++d) b1[d] = bterm1(d, s);
 #pragma unroll
             for (int ig = 0; ig < NM / 2; ++ig) {
                 s16x8 av[2][2];
@@ -832,13 +882,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
                         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(RW_LDS(ring + aaddr[s][1] + off));
                         av[tm][ii] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                     }
-#define R16_PRODUCT(TA, TB)                                                                                                  \
+#define R16_PRODUCT(TA, BV)                                                                                                  \
     _Pragma("unroll") for (int d = 0; d < NT; ++d)                                                                           \
         _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                                                     \
-            acc[ig * 2 + ii][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[TA][ii]), __builtin_bit_cast(f16x8, bw[d][s][TB < BWT ? TB : 0]), acc[ig * 2 + ii][d], 0, 0, 0);
-                R16_PRODUCT(1, 0)
-                R16_PRODUCT(0, 1)
-                R16_PRODUCT(0, 0)
+            acc[ig * 2 + ii][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[TA][ii]), __builtin_bit_cast(f16x8, BV), acc[ig * 2 + ii][d], 0, 0, 0);
+                R16_PRODUCT(1, bw[d][s][0])
+                R16_PRODUCT(0, b1[d])
+                R16_PRODUCT(0, bw[d][s][0])
 #undef R16_PRODUCT
             }
             // (the conversion has no branch: the compiler's scheduler weaves it and the next k-step's fragment reads between the MFMAs.
@@ -864,7 +914,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     const int dn_addr = (((g + 1) & 3) * 16 + q) * 4;     // same column, next 4-row group
     unsigned okbits = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < WNM; ++i) {
         const int p = 16 * (m0 + i) + 4 * g;
         if (useful && i < nm && p >= 4 && p < 4 + RW_P && f_base - 4 + p < a.F) okbits |= 1u << i;
     }
@@ -872,20 +922,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     const __amdgpu_buffer_rsrc_t ylrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(BNRED ? a.yl + (long)b * a.T * COUT * a.F : a.x), 0,
                                                                             BNRED ? (unsigned)((long)a.T * COUT * a.F * 4) : 0u, 0x00020000);
     const int yvo = (co * a.F + f_base - 4 + 16 * m0 + 4 * g) * 4;       // + 64 i
-    // WIDE: D0 / D1 / D2 = tiles 0 / 1 / 2, same lane.  Narrow (group 2): D0 = tile 0 lanes 0-7, D1 = tile 0 lanes 8-15 (row rotate by 8),
-    // D2 = tile 1 lanes 0-7.
     // data gradient: yl at this lane's output positions, fetched BEFORE the multiply of the row (in flight under the MFMAs)
-    f32x4 ylv[BNRED ? 4 : 1];
+    f32x4 ylv[BNRED ? WNM : 1];
     auto yl_fetch = [&](int t) {
         if (!BNRED) return;
         const int yrow_off = t * COUT * a.F * 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < WNM; ++i)
             if (i < nm) ylv[BNRED ? i : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ylrsrc, yvo + 64 * i, yrow_off, 0));
     };
     auto epilogue = [&](auto WIDEc, int t, int par) {
         constexpr bool WIDE = decltype(WIDEc)::value;
-        constexpr int NM = WIDE ? 4 : 2, D2 = WIDE ? 2 : 1;
+        constexpr int NM = WIDE ? WNM : 2;
         const int yrow_off = t * COUT * a.F * 4;
         // rows across the boundaries to the neighbouring column ranges (true values -> this wave's sign)
         const float xl = bnd_l >= 0 ? xch[par][bnd_l >= 0 ? bnd_l : 0][0][q] * sg : 0.f;
@@ -898,7 +946,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             // row p - 1 of D0 lives in the previous 4-row group (lane - 16; for g = 0: the previous m-tile's group 3, for the first
             // m-tile of the range: the left neighbour's value), row p + 1 of D2 in the next one
             const float up_src = (g == 3) ? (i > 0 ? acc[i > 0 ? i - 1 : 0][0][3] : xl) : acc[i][0][3];
-            const float dn_src = (g == 0) ? (i < NM - 1 ? acc[i < NM - 1 ? i + 1 : NM - 1][D2][0] : xr_) : acc[i][D2][0];
+            const int in = i < NM - 1 ? i + 1 : NM - 1;
+            const float dn_src = (g == 0) ? (i < NM - 1 ? dterm2(WIDEc, acc[in][0], acc[in][1], acc[in][2], 0) : xr_) : dterm2(WIDEc, acc[i][0], acc[i][1], acc[i][2], 0);
             X[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(up_addr, __float_as_int(up_src)));
             Y[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(dn_addr, __float_as_int(dn_src)));
         }
@@ -908,11 +957,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             const float us = ok ? unsc : 0.f;
             f32x4 d1;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) d1[r] = WIDE ? acc[i][1][r] : rw_ror8(acc[i][0][r]);
+            for (int r = 0; r < 4; ++r) d1[r] = dterm1(WIDEc, acc[i][0], acc[i][1], r);
             f32x4 o;
-            o[0] = ((X[i] + d1[0]) + acc[i][D2][1]) * us;
-            o[1] = ((acc[i][0][0] + d1[1]) + acc[i][D2][2]) * us;
-            o[2] = ((acc[i][0][1] + d1[2]) + acc[i][D2][3]) * us;
+            o[0] = ((X[i] + d1[0]) + dterm2(WIDEc, acc[i][0], acc[i][1], acc[i][2], 1)) * us;
+            o[1] = ((acc[i][0][0] + d1[1]) + dterm2(WIDEc, acc[i][0], acc[i][1], acc[i][2], 2)) * us;
+            o[2] = ((acc[i][0][1] + d1[2]) + dterm2(WIDEc, acc[i][0], acc[i][1], acc[i][2], 3)) * us;
             o[3] = ((acc[i][0][2] + d1[3]) + Y[i]) * us;
             if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, yvo + 64 * i, yrow_off, 0);
             if (BNRED) {
@@ -947,11 +996,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
 
     if constexpr (PIPE) {
         // ======================================================================== two accumulator sets: epilogue of row t - 1 under the multiply of row t
-        f32x4 accp[2][4][3];
+        f32x4 accp[2][WNM][3];
 #pragma unroll
         for (int e = 0; e < 2; ++e)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < WNM; ++i)
 #pragma unroll
                 for (int d = 0; d < 3; ++d) accp[e][i][d] = (f32x4){0.f, 0.f, 0.f, 0.f};      // (the first row's "previous row" is masked out, but must be finite)
         // one m-tile of the epilogue of row t from accumulator set SET (the arithmetic of `epilogue` above)
@@ -962,21 +1011,22 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
         };
         auto epi_tile = [&](auto WIDEc, auto SETc, int i, int t, float xl, float xr_, unsigned ob, const f32x4& ylt) {
             constexpr bool WIDE = decltype(WIDEc)::value;
-            constexpr int SET = decltype(SETc)::value, NM = WIDE ? 4 : 2, D2 = WIDE ? 2 : 1;
+            constexpr int SET = decltype(SETc)::value, NM = WIDE ? WNM : 2;
             const int yrow_off = t * COUT * a.F * 4;
             const float up_src = (g == 3) ? (i > 0 ? accp[SET][i > 0 ? i - 1 : 0][0][3] : xl) : accp[SET][i][0][3];
-            const float dn_src = (g == 0) ? (i < NM - 1 ? accp[SET][i < NM - 1 ? i + 1 : NM - 1][D2][0] : xr_) : accp[SET][i][D2][0];
+            const int in = i < NM - 1 ? i + 1 : NM - 1;
+            const float dn_src = (g == 0) ? (i < NM - 1 ? dterm2(WIDEc, accp[SET][in][0], accp[SET][in][1], accp[SET][in][2], 0) : xr_) : dterm2(WIDEc, accp[SET][i][0], accp[SET][i][1], accp[SET][i][2], 0);
             const float X = __int_as_float(__builtin_amdgcn_ds_bpermute(up_addr, __float_as_int(up_src)));
             const float Y = __int_as_float(__builtin_amdgcn_ds_bpermute(dn_addr, __float_as_int(dn_src)));
             const bool ok = ob >> i & 1;
             const float us = ok ? unsc : 0.f;
             f32x4 d1;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) d1[r] = WIDE ? accp[SET][i][1][r] : rw_ror8(accp[SET][i][0][r]);
+            for (int r = 0; r < 4; ++r) d1[r] = dterm1(WIDEc, accp[SET][i][0], accp[SET][i][1], r);
             f32x4 o;
-            o[0] = ((X + d1[0]) + accp[SET][i][D2][1]) * us;
-            o[1] = ((accp[SET][i][0][0] + d1[1]) + accp[SET][i][D2][2]) * us;
-            o[2] = ((accp[SET][i][0][1] + d1[2]) + accp[SET][i][D2][3]) * us;
+            o[0] = ((X + d1[0]) + dterm2(WIDEc, accp[SET][i][0], accp[SET][i][1], accp[SET][i][2], 1)) * us;
+            o[1] = ((accp[SET][i][0][0] + d1[1]) + dterm2(WIDEc, accp[SET][i][0], accp[SET][i][1], accp[SET][i][2], 2)) * us;
+            o[2] = ((accp[SET][i][0][1] + d1[2]) + dterm2(WIDEc, accp[SET][i][0], accp[SET][i][1], accp[SET][i][2], 3)) * us;
             o[3] = ((accp[SET][i][0][2] + d1[3]) + Y) * us;
             if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, yvo + 64 * i, yrow_off, 0);
             if (BNRED) {
@@ -1000,7 +1050,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
         // in front of the strip (the first iteration has no previous row: its accumulators are the zeros above)
         auto multiply_p = [&](auto WIDEc, auto CURc, int t_e, int crow, int cslot, const f32x4 (&xr)[XIT]) {
             constexpr bool WIDE = decltype(WIDEc)::value;
-            constexpr int CUR = decltype(CURc)::value, NM = WIDE ? 4 : 2, NT = WIDE ? 3 : 2;
+            constexpr int CUR = decltype(CURc)::value, NM = WIDE ? WNM : 2, NT = WIDE ? 3 : NNT;
             const bool cok = crow >= 0 && crow < a.T && colok;
             unsigned char* const cbase = ring + cslot * G::SLOT;
             const bool ev = t_e >= t_lo;
@@ -1018,7 +1068,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
                 if (BNRED) {
 #pragma unroll
                     for (int i = 0; i < NM; ++i)
-                        if (i * KS / NM == s) ylt[(NM > KS) ? i - s * NM / KS : 0] = (ev || true) ? yl_tile(i, t_e) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                        if (i * KS / NM == s) ylt[(NM > KS) ? i - s * NM / KS : 0] = yl_tile(i, max(t_e, t_lo));      // (the dummy row in front of the strip reads the strip's first: in range and finite -- its statistics terms are masked to zero)
                 }
                 s16x8 b1[NT];
 #pragma unroll
@@ -1058,8 +1108,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             constexpr int CUR = decltype(CURc)::value;
             if (wide) multiply_p(std::true_type{}, CURc, t - 1, t + 2, slot_w, xa);
             else multiply_p(std::false_type{}, CURc, t - 1, t + 2, slot_w, xa);
-            if (bnd_r >= 0 && g == 3) xch[CUR][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? accp[CUR][3][0][3] : accp[CUR][1][0][3]) * sg;
-            if (bnd_l >= 0 && g == 0) xch[CUR][bnd_l >= 0 ? bnd_l : 0][1][q] = (wide ? accp[CUR][0][2][0] : accp[CUR][0][1][0]) * sg;
+            const float d2first = wide ? accp[CUR][0][2][0] : dterm2(std::false_type{}, accp[CUR][0][0], accp[CUR][0][1], accp[CUR][0][2], 0);
+            if (bnd_r >= 0 && g == 3) xch[CUR][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? accp[CUR][WNM - 1][0][3] : accp[CUR][1][0][3]) * sg;
+            if (bnd_l >= 0 && g == 0) xch[CUR][bnd_l >= 0 ? bnd_l : 0][1][q] = d2first * sg;
             __syncthreads();
             issue(t + 3, xa);
             slot_w = slot_w == R16_SLOTS - 1 ? 0 : slot_w + 1;
@@ -1080,7 +1131,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             unsigned ob = okbits;
             asm volatile("" : "+v"(ob));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < WNM; ++i) {
                 if (i < nm) {
                     const f32x4 ylt = BNRED ? yl_tile(i, t_hi - 1) : (f32x4){0.f, 0.f, 0.f, 0.f};
                     if (wide) { if (last) epi_tile(std::true_type{}, C1{}, i, t_hi - 1, xl, xr_, ob, ylt); else epi_tile(std::true_type{}, C0{}, i, t_hi - 1, xl, xr_, ob, ylt); }
@@ -1095,19 +1146,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     const int trace_first = (int)gridDim.x / 2;
     const int trace_wg = ((int)blockIdx.x >= trace_first && (int)blockIdx.x < trace_first + RW_TRACE_WGS) ? (int)blockIdx.x - trace_first : -1;
 #endif
-    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
+    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+    using IW = std::integral_constant<int, WNM>; using INt = std::integral_constant<int, NNT>;
     for (int t = t_lo; t < t_hi; ++t) {
 #ifdef RW_TRACE
         const int trace_it = t - t_lo - 40;
 #endif
         RW_STAMP(0);
         yl_fetch(t);
-        if (wide) multiply(I4{}, I3{}, t + 2, slot_w, xa);
-        else multiply(I2{}, I2{}, t + 2, slot_w, xa);
+        if (wide) multiply(IW{}, I3{}, t + 2, slot_w, xa);
+        else multiply(I2{}, INt{}, t + 2, slot_w, xa);
         RW_STAMP(1);
         // boundary rows for the neighbouring column ranges (lanes of 4-row group 3 / 0 hold them), as true values
-        if (bnd_r >= 0 && g == 3) xch[par][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? acc[3][0][3] : acc[1][0][3]) * sg;
-        if (bnd_l >= 0 && g == 0) xch[par][bnd_l >= 0 ? bnd_l : 0][1][q] = (wide ? acc[0][2][0] : acc[0][1][0]) * sg;
+        const float d2first = wide ? acc[0][2][0] : dterm2(std::false_type{}, acc[0][0], acc[0][1], acc[0][2], 0);
+        if (bnd_r >= 0 && g == 3) xch[par][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? acc[WNM - 1][0][3] : acc[1][0][3]) * sg;
+        if (bnd_l >= 0 && g == 0) xch[par][bnd_l >= 0 ? bnd_l : 0][1][q] = d2first * sg;
         __syncthreads();
         RW_STAMP(2);
         if (wide) epilogue(std::true_type{}, t, par);
@@ -1131,7 +1184,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     __syncthreads();
     if (tid < COUT) {
         float s = 0.f, s2 = 0.f, m = 0.f;
-        const int w0 = tid < 32 ? 2 * (tid >> 4) : 4, nw = tid < 32 ? 2 : 4, c = tid < 32 ? tid & 15 : tid - 32;
+        constexpr int CW = 16 * N::NWG;                      // channels of the wide groups: N::WSPLIT waves each; the narrow group: waves 4-7
+        const int w0 = tid < CW ? N::WSPLIT * (tid >> 4) : 4, nw = tid < CW ? N::WSPLIT : 4, c = tid < CW ? tid & 15 : tid - CW;
         for (int k = 0; k < nw; ++k) { s += red[w0 + k][c][0]; s2 += red[w0 + k][c][1]; m = fmaxf(m, red[w0 + k][c][2]); }
         if (a.stat_partial) {
             a.stat_partial[((long)blockIdx.x * COUT + tid) * 2 + 0] = s;
@@ -1146,7 +1200,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- launcher
-// "conv_rows" -- bit 0: the row-streaming kernels; bit 1: their second generation (conv3x3_rows16) where it exists (Cout = 40); bits 2 / 3: its
+// "conv_rows" -- bit 0: the row-streaming kernels; bit 1: their second generation (conv3x3_rows16: every Cin, Cout of 20 / 40); bits 2 / 3: its
 // form with two accumulator sets (epilogue under the next row's multiply) for the forward / data-gradient launches
 bool a2s_conv_rows_eligible(int F, int Cin) { return a2s_sw(A2S_SW_conv_rows) && F % 4 == 0 && (Cin == 20 || Cin == 40); }
 
@@ -1171,14 +1225,20 @@ size_t a2s_conv_rows_workspace_floats(int Cin) {
     return (size_t)9 * RwGeom<40>::KS * 2 * 1024 / 4 + RW_HDR + 64;     // (rows16: 9 tiles)
 }
 
+static long long g_rows16_c20_launches = 0;          // conv3x3_rows16<*, 20> launches of this process (a2s_debug_get("conv_rows16_c20_launches"): the tests' proof of the path)
+long a2s_conv_rows16_c20_launches(void) { return (long)__atomic_load_n(&g_rows16_c20_launches, __ATOMIC_RELAXED); }
+
 template <int CIN, int COUT>
 static int rows16_launch(hipStream_t st, const RowsArgs& a, bool affine, bool bnred, int nwork) {
     constexpr int NT = 512;
+    if (COUT == 20) __atomic_fetch_add(&g_rows16_c20_launches, 1LL, __ATOMIC_RELAXED);
     // the two-accumulator-set form (round 6): bit 2 the forward instances, bit 3 the data-gradient instance (24 spilled registers at 40 -> 40)
-    const int en = a2s_sw(A2S_SW_conv_rows);
-    if (affine && (en & 4)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false, true>), dim3(nwork), dim3(NT), 0, st, a);
+    // (20 -> 20 has one form only: a second accumulator set costs it the 128 registers at which two workgroups share a CU -- measured slower)
+    constexpr bool SETS2 = !(CIN == 20 && COUT == 20);
+    const int en = SETS2 ? a2s_sw(A2S_SW_conv_rows) : 0;
+    if (affine && (en & 4)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false, SETS2>), dim3(nwork), dim3(NT), 0, st, a);
     else if (affine) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false>), dim3(nwork), dim3(NT), 0, st, a);
-    else if (bnred && (en & 8)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true, true>), dim3(nwork), dim3(NT), 0, st, a);
+    else if (bnred && (en & 8)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true, SETS2>), dim3(nwork), dim3(NT), 0, st, a);
     else if (bnred) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true>), dim3(nwork), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, false>), dim3(nwork), dim3(NT), 0, st, a);
     A2S_CHECK_LAUNCH("conv3x3_rows16");
@@ -1204,7 +1264,8 @@ int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float*
                           const float* x_absmax) {
     A2S_REQUIRE(F % 4 == 0 && (Cin == 20 || Cin == 40) && (Cout == 20 || Cout == 40), "conv3x3_rows: unsupported shape F=%d Cin=%d Cout=%d", F, Cin, Cout);
     A2S_REQUIRE(!(in_scale && yl), "conv3x3_rows: input affine and BatchNorm-backward statistics are exclusive");
-    if (yl && Cin == 20 && Cout == 20 && out_absmax) {       // the one data-gradient instance that does not track max |g| in its epilogue: an extra pass
+    const bool gen2 = a2s_sw(A2S_SW_conv_rows) & 2;
+    if (yl && Cin == 20 && Cout == 20 && out_absmax && !gen2) {       // the one (first-generation) data-gradient instance that does not track max |g| in its epilogue: an extra pass
         const int rc = a2s_conv3x3_rows_impl(st, x, w, y, in_scale, in_shift, in_absmax, stat_partial, nullptr, B, T, F, Cin, Cout, flip, ws, yl, yl_mean, yl_invstd,
                                              yl_scale, yl_shift, x_absmax);
         return rc != A2S_OK ? rc : a2s_channel_absmax_impl(st, y, (long)B * T, Cout, F, out_absmax);
@@ -1228,12 +1289,12 @@ int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float*
     a.nwork = B * a.tilesF * a.nstrips;
     const bool affine = in_scale != nullptr, bnred = yl != nullptr;
 #define R16_CASE(CI, CO)                                                                                                     \
-    if (Cin == CI && Cout == CO && (a2s_sw(A2S_SW_conv_rows) & 2)) {                                                          \
-        hipLaunchKernelGGL((rows16_pack<CI, CO>), dim3(8), dim3(256), 0, st, w, flip, in_scale, in_shift, in_absmax, x_absmax, wimg, hdr, out_absmax); \
+    if (Cin == CI && Cout == CO && gen2) {                                                                                   \
+        hipLaunchKernelGGL((rows16_pack<CI, CO>), dim3(R16Geom<CO>::NTILES), dim3(256), 0, st, w, flip, in_scale, in_shift, in_absmax, x_absmax, wimg, hdr, out_absmax); \
         A2S_CHECK_LAUNCH("rows16_pack");                                                                                     \
         return rows16_launch<CI, CO>(st, a, affine, bnred, a.nwork);                                                         \
     }
-    R16_CASE(20, 40) R16_CASE(40, 40)
+    R16_CASE(20, 40) R16_CASE(40, 40) R16_CASE(20, 20) R16_CASE(40, 20)
 #undef R16_CASE
 #define RW_CASE(CI, CO)                                                                                                      \
     if (Cin == CI && Cout == CO) {                                                                                           \

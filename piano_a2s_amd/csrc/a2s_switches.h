@@ -14,7 +14,7 @@
 
 #define A2S_SWITCHES(X)                                                                                                                              \
     /* ConvStack: bit 0 the row-streaming kernels of a2s_conv_rows.hip, bit 1 their second generation (conv3x3_rows16) where it exists              \
-       (Cout = 40), bits 2 / 3 its form with two accumulator sets for the forward / data-gradient launches; 0 = the tiled kernels of a2s_conv.hip */ \
+       (Cout 20, 40), bits 2 / 3 its form with two accumulator sets for the forward / data-gradient launches; 0 = the tiled kernels of a2s_conv.hip */ \
     X(conv_rows, 7, COUNT, "A2S_CONV_ROWS")                                                                                                          \
     /* the weight gradient on the row-streaming kernels of a2s_conv_wrows.hip */                                                                     \
     X(wgrad_rows, 1, COUNT, "A2S_WGRAD_ROWS")                                                                                                        \

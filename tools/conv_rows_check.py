@@ -1,6 +1,9 @@
 """The row-streaming convolution (csrc/a2s_conv_rows.hip) against float64 on small shapes (forward with operand BatchNorm + batch statistics,
 data gradient with the BatchNorm-backward statistics epilogue, plain data gradient), then its launch durations at the training shapes next to
-the tiled kernels of round 2 (`conv_rows` = 0).  usage: python tools/conv_rows_check.py [B] [--no-check] [--no-time]"""
+the tiled kernels of round 2 (`conv_rows` = 0).  usage: python tools/conv_rows_check.py [B] [--no-check] [--no-time]
+--ab [--out FILE]: instead, the three 20-output-channel launches of the training step, one launch per HIP-event pair (packing pre-kernel
+included), alternating between the `conv_rows` settings (7 = rows16, 5 = the first-generation kernel for the same launch; 3 / 15 = rows16 with
+one accumulator set / with two sets for the data gradient as well): median and spread per launch and setting."""
 import os
 import sys
 
@@ -144,8 +147,74 @@ def bench(B):
         del x, y, yl
 
 
+def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
+    T, F = 1201, 480
+    lines = [f"B = {B}, T = {T}, F = {F}; {warm} warm-up + {iters} timed launches per setting, alternating; ms per launch (packing pre-kernel included)",
+             f"{'launch':34s} {'conv_rows':>9s} {'median':>8s} {'min':>8s} {'max':>8s} {'spread':>8s}"]
+    verdicts = []
+    for ci, co, mode, what in ((40, 20, "dgrad_ranged", "conv3 dgrad 40->20 bnstats+absmax"), (20, 20, "dgrad", "conv2 dgrad 20->20 bnstats"),
+                               (20, 20, "fwd", "conv2 fwd 20->20 affine+stats")):
+        fwd = mode == "fwd"
+        x = torch.randn(B, T, ci, F, device=dev) * (1.0 if fwd else 1e-4)
+        y = torch.empty(B, T, co, F, device=dev)
+        w = torch.randn((co, ci, 3, 3) if fwd else (ci, co, 3, 3), device=dev) * 0.05
+        scale, shift = torch.rand(ci, device=dev) + 0.5, torch.randn(ci, device=dev) * 0.1
+        cws = hip.conv_workspace(ci, dev)
+        in_amax = x.abs().amax(dim=(0, 1, 3)).contiguous()
+        out_amax = torch.zeros(co, device=dev)
+        xmax = hip.absmax(x)
+        yl = None if fwd else torch.randn(B, T, co, F, device=dev)
+        bn = [torch.randn(co, device=dev) * 0.1, torch.rand(co, device=dev) + 0.5, torch.rand(co, device=dev) + 0.5, torch.randn(co, device=dev) * 0.1]
+        partial = torch.empty(L.a2s_conv3x3_stat_blocks(B, T, F, ci), co, 2, device=dev)
+        if fwd:
+            fn = lambda: hip.conv3x3_forward(x, w, y, scale, shift, partial, cws, in_amax, out_amax)
+        elif mode == "dgrad":
+            fn = lambda: hip.check(L.a2s_conv3x3_dgrad_bnstats_scaled(hip.stream(), hip._p(x), hip._p(w), hip._p(y), hip._p(yl), hip._p(bn[0]), hip._p(bn[1]),
+                                                                      hip._p(bn[2]), hip._p(bn[3]), hip._p(partial), B, T, F, ci, co, hip._p(cws), hip._p(xmax)), "dgrad")
+        else:
+            fn = lambda: hip.check(L.a2s_conv3x3_dgrad_bnstats_ranged(hip.stream(), hip._p(x), hip._p(w), hip._p(y), hip._p(yl), hip._p(bn[0]), hip._p(bn[1]),
+                                                                      hip._p(bn[2]), hip._p(bn[3]), hip._p(partial), B, T, F, ci, co, hip._p(cws), hip._p(xmax),
+                                                                      hip._p(out_amax)), "dgrad ranged")
+        times = {r: [] for r in settings}
+        for k in range(warm + iters):
+            for rows in settings:
+                hip.check(L.a2s_debug_set(b"conv_rows", rows), "set")
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if k >= warm:
+                    times[rows].append(e0.elapsed_time(e1))
+        hip.check(L.a2s_debug_set(b"conv_rows", ROWS), "set")
+        stat = {}
+        for rows in settings:
+            t = sorted(times[rows])
+            stat[rows] = (t[len(t) // 2], t[0], t[-1])
+            lines.append(f"{what:34s} {rows:9d} {stat[rows][0]:8.3f} {t[0]:8.3f} {t[-1]:8.3f} {t[-1] - t[0]:8.3f}")
+            print(lines[-1], flush=True)
+        if 7 in stat and 5 in stat:
+            d = stat[5][0] - stat[7][0]
+            spread = max(stat[5][2] - stat[5][1], stat[7][2] - stat[7][1])
+            verdicts.append(f"{what}: rows16 (7) - first generation (5) = {-d:+.3f} ms, larger spread {spread:.3f} ms -> {'faster' if d > spread else 'slower' if -d > spread else 'no difference'}")
+        del x, y, yl
+    lines += verdicts
+    print("\n".join(verdicts), flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--ab" in sys.argv:
+        out = None
+        if "--out" in sys.argv:
+            out = sys.argv[sys.argv.index("--out") + 1]
+            args.remove(out)
+        ab(int(args[0]) if args else 256, out)
+        sys.exit(0)
     if "--no-check" not in sys.argv:
         check()
     if "--no-time" not in sys.argv:
