@@ -353,6 +353,11 @@ int a2s_attn_dk_accum(void* stream, const float* keys, const float* q_all, const
 /* q_all / ds_all rows: (step, group, clip) with `groups` fused bars per step (1 = plain); row_until (optional, groups*B ints):
  * the ds rows of (group, clip) are zero from step row_until[group*B + clip] on and are not read */
 int a2s_attn_dk_blocks(int B, int T);
+/* deferred encoder-output gradient of S steps: dEnc[b] (T x H2) += sum over the live (step, group) pairs of attw[row]^T dctx[row], same row
+ * conventions (attw_all rows of T, dctx_all rows of H2 floats, both dense); the rows of finished pairs are not read.  H2 must be 512: the
+ * caller takes a2s_gemm_f32 for every other width.  Fixed summation order (ascending pairs), no atomics. */
+int a2s_attn_denc_accum(void* stream, const float* attw_all, const float* dctx_all, float* dEnc, int B, int T, int S, int H2,
+                        const int* row_until, int groups);
 /* out[c] = alpha * sum_r x[r*ld+c] + beta*out[c]; with a workspace (>= 2*C floats, ideally 1024*C) long matrices are reduced in two
  * stages over many workgroups (fixed partition: deterministic). */
 int a2s_col_sum(void* stream, const float* x, long ld, float* out, long rows, int C, float alpha, float beta, float* workspace, size_t workspace_floats);

@@ -79,6 +79,7 @@ int a2s_debug_set(const char* key, int value) {
     if (!key) return A2S_ERR_ARG;
     const int id = a2s_switch_find(key);
     if (id >= 0) { a2s_switch_store(id, value); return A2S_OK; }
+    if (!strcmp(key, "attn_deferred_fast")) { a2s_attn_deferred_fast = value ? 1 : 0; return A2S_OK; }
     if (!strcmp(key, "gemm_tile")) { a2s_gemm_debug_tile_impl(value); return A2S_OK; }          // write-only
     snprintf(a2s_err_msg, sizeof(a2s_err_msg), "a2s_debug_set: unknown key %s", key);
     return A2S_ERR_ARG;
@@ -98,6 +99,9 @@ int a2s_debug_get(const char* key) {
     // read-only: launch counters (tests: proof of the path taken) and what the runtime reports for the current device
     if (!strcmp(key, "attn_pair_launches")) return (int)a2s_attn_pair_launches();
     if (!strcmp(key, "attn_pair_bwd_launches")) return (int)a2s_attn_pair_bwd_launches();
+    if (!strcmp(key, "attn_deferred_fast")) return a2s_attn_deferred_fast;
+    if (!strcmp(key, "attn_dk_ahead_launches")) return (int)a2s_attn_dk_ahead_launches();
+    if (!strcmp(key, "attn_denc_launches")) return (int)a2s_attn_denc_launches();
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
     if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
     if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
@@ -264,6 +268,10 @@ int a2s_attn_dk_accum(void* stream, const float* keys, const float* q_all, const
     return a2s_attn_dk_accum_impl(ST, keys, q_all, ds_all, v, dK, dv_partial, B, T, S, H, row_until, groups);
 }
 int a2s_attn_dk_blocks(int B, int T) { return B * ((T + 15) / 16); }
+int a2s_attn_denc_accum(void* stream, const float* attw_all, const float* dctx_all, float* dEnc, int B, int T, int S, int H2,
+                        const int* row_until, int groups) {
+    return a2s_attn_denc_accum_impl(ST, attw_all, dctx_all, dEnc, B, T, S, H2, row_until, groups);
+}
 int a2s_col_sum(void* stream, const float* x, long ld, float* out, long rows, int C, float alpha, float beta, float* workspace, size_t workspace_floats) {
     return a2s_col_sum_impl(ST, x, ld, out, rows, C, alpha, beta, workspace, workspace_floats);
 }

@@ -182,11 +182,197 @@ __global__ __launch_bounds__(256) void attn_dk_accum(const float* __restrict__ K
     }
 }
 
+// ---- the deferred products on kernels that walk only the LIVE (step, bar) pairs of a clip (switch attn_deferred_fast)
+// The live pairs of clip b among the candidates sg in [sg0, sg1), ascending, compacted into list[] by the first wave; *cnt receives their number.
+// (sg = step * groups + bar; live: row_until == NULL or step < row_until[bar * B + b].)  The caller's barriers order it against the readers.
+constexpr int LIVE_CH = 512;          // candidates per compaction round (the list's capacity)
+__device__ __forceinline__ void live_pairs(int* __restrict__ list, int* __restrict__ cnt, int sg0, int sg1, int b, int B,
+                                           const int* __restrict__ row_until, int groups) {
+    if (threadIdx.x >= 64) return;
+    int n = 0;
+    for (int base = sg0; base < sg1; base += 64) {
+        const int sg = base + (int)threadIdx.x;
+        bool live = sg < sg1;
+        if (live && row_until) live = sg / groups < row_until[(sg % groups) * B + b];
+        const unsigned long long m = __ballot(live);
+        if (live) list[n + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = sg;
+        n += __popcll(m);
+    }
+    if (threadIdx.x == 0) *cnt = n;
+}
+
+// attn_dk_accum with its loads ahead of their use: the same ownership, the same evaluations in the same order (dK and the dv partials are
+// bit-equal to attn_dk_accum's), but the live pairs are taken NS at a time -- while block n is evaluated, the q values (one register per pair:
+// thread j needs only q[row, j]) and the ds values (one per thread, published through a double-buffered LDS tile) of block n + 1 are in
+// flight.  One barrier per block of NS pairs instead of two per pair, and no load whose result the next instruction waits for.
+// Launched with 256 threads; H <= 256 (one thread per unit).
+#ifndef A2S_ATTN_DK_NS
+#define A2S_ATTN_DK_NS 8
+#endif
+template <int NS>
+__global__ __launch_bounds__(256) void attn_dk_accum_ahead(const float* __restrict__ Kmat, const float* __restrict__ q_all,
+                                                           const float* __restrict__ ds_all, const float* __restrict__ v,
+                                                           float* __restrict__ dK, float* __restrict__ dv_partial, int B, int T, int S,
+                                                           const int* __restrict__ row_until, int groups, int H) {
+    constexpr int TT = 16;
+    static_assert(NS * TT <= 256, "one ds value per thread");
+    const int tiles = (T + TT - 1) / TT;
+    const int b = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * TT;
+    const int tid = threadIdx.x, j = tid;
+    __shared__ int list[LIVE_CH];
+    __shared__ int cnt_s;
+    __shared__ float dss[2][NS * TT];
+    float kreg[TT], acc[TT];
+    float dvj = 0.f;
+#pragma unroll
+    for (int i = 0; i < TT; ++i) { kreg[i] = (j < H && t0 + i < T) ? Kmat[((long)b * T + t0 + i) * H + j] : 0.f; acc[i] = 0.f; }
+    const int nsg = S * groups, du = tid / TT, di = tid % TT;          // this thread stages ds of pair du of a block, frame t0 + di
+    int buf = 0;
+    for (int c0 = 0; c0 < nsg; c0 += LIVE_CH) {
+        __syncthreads();                                               // the previous round's list and ds tiles are read
+        live_pairs(list, &cnt_s, c0, min(nsg, c0 + LIVE_CH), b, B, row_until, groups);
+        __syncthreads();
+        const int cnt = cnt_s;
+        float qn[NS], dsn = 0.f;
+        auto fetch = [&](int p0) {
+#pragma unroll
+            for (int u = 0; u < NS; ++u) qn[u] = (p0 + u < cnt && j < H) ? q_all[((long)list[p0 + u] * B + b) * H + j] : 0.f;
+            dsn = (tid < NS * TT && p0 + du < cnt && t0 + di < T) ? ds_all[((long)list[p0 + du] * B + b) * T + t0 + di] : 0.f;
+        };
+        fetch(0);
+        for (int p0 = 0; p0 < cnt; p0 += NS) {
+            const int nv = min(NS, cnt - p0);
+            float qc[NS];
+#pragma unroll
+            for (int u = 0; u < NS; ++u) qc[u] = qn[u];
+            if (tid < NS * TT) dss[buf][tid] = dsn;
+            __syncthreads();                                           // (the tile written two blocks ago was read before the last barrier)
+            fetch(p0 + NS);
+            if (j < H) {
+#pragma unroll
+                for (int u = 0; u < NS; ++u) {
+                    if (u < nv) {                                      // uniform over the workgroup
+                        const float eq = exp2x_clamped(qc[u]);         // kreg holds the key image E_K = exp(2K)
+#pragma unroll
+                        for (int i = 0; i < TT; ++i) {
+                            const float e = tanh_ek(kreg[i], eq);
+                            acc[i] = fmaf(dss[buf][u * TT + i], 1.f - e * e, acc[i]);
+                            dvj = fmaf(dss[buf][u * TT + i], e, dvj);
+                        }
+                    }
+                }
+            }
+            buf ^= 1;
+        }
+    }
+    if (j < H) {
+        const float vj = v[j];
+#pragma unroll
+        for (int i = 0; i < TT; ++i)
+            if (t0 + i < T) dK[((long)b * T + t0 + i) * H + j] += vj * acc[i];
+        dv_partial[(long)blockIdx.x * H + j] = dvj;
+    }
+}
+
+int a2s_attn_deferred_fast = 1;          // a2s_debug_set / a2s_debug_get("attn_deferred_fast") (a2s_switches.h: the key beside the list)
+static long long g_attn_dk_ahead_launches = 0, g_attn_denc_launches = 0;      // a2s_debug_get("attn_dk_ahead_launches" / "attn_denc_launches"): the tests' proof of the path
+long a2s_attn_dk_ahead_launches(void) { return (long)__atomic_load_n(&g_attn_dk_ahead_launches, __ATOMIC_RELAXED); }
+long a2s_attn_denc_launches(void) { return (long)__atomic_load_n(&g_attn_denc_launches, __ATOMIC_RELAXED); }
+
+// Deferred encoder-output gradient of one (bar, staff): dEnc[b, t, :] += sum over the live (step, bar) pairs of attw[pair, b, t] * dctx[pair, b, :].
+// One workgroup per (clip, 64 frames) holds the 64 x 512 tile in accumulator registers: wave w owns columns 128 w .. 128 w + 127 as 4 x 8 tiles of
+// v_mfma_f32_16x16x4_f32 (A = attw: 16 consecutive frames of 4 pairs, B = dctx: 16 consecutive columns of the same 4 pairs), operands straight
+// from global memory into the lanes that use them (no LDS, no barrier inside the pair loop), KB k-steps loaded while the previous KB multiply.
+// The pairs are summed in ascending order (an fmaf chain per element), the tile is added into dEnc once; rows of finished pairs are not read.
+template <int KB>
+__global__ __launch_bounds__(256, 2) void attn_denc_accum(const float* __restrict__ attw_all, const float* __restrict__ dctx_all,
+                                                       float* __restrict__ dEnc, int B, int T, int S, const int* __restrict__ row_until, int groups) {
+    constexpr int H2 = 512, FT = 64, RT = FT / 16, CT = 8;
+    const int tiles = (T + FT - 1) / FT;
+    const int b = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * FT;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lk = lane >> 4, lc = lane & 15;
+    const int col0 = wave * (16 * CT);
+    __shared__ int list[LIVE_CH];
+    __shared__ int cnt_s;
+    f32x4 acc[RT][CT];
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[i][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int nsg = S * groups;
+    for (int c0 = 0; c0 < nsg; c0 += LIVE_CH) {
+        __syncthreads();
+        live_pairs(list, &cnt_s, c0, min(nsg, c0 + LIVE_CH), b, B, row_until, groups);
+        __syncthreads();
+        const int cnt = cnt_s;
+        float an[KB][RT], bn[KB][CT];
+        auto fetch = [&](int p0) {                                     // k-step s of the group: pairs p0 + 4 s .. + 3, this lane's is + lk
+#pragma unroll
+            for (int s = 0; s < KB; ++s) {
+                const int p = p0 + 4 * s + lk;
+                const bool ok = p < cnt;                               // beyond the list: a zero pair
+                const long row = ok ? (long)list[p] * B + b : 0;
+#pragma unroll
+                for (int i = 0; i < RT; ++i) an[s][i] = (ok && t0 + 16 * i + lc < T) ? attw_all[row * T + t0 + 16 * i + lc] : 0.f;
+#pragma unroll
+                for (int c = 0; c < CT; ++c) bn[s][c] = ok ? dctx_all[row * H2 + col0 + 16 * c + lc] : 0.f;
+            }
+        };
+        fetch(0);
+        for (int p0 = 0; p0 < cnt; p0 += 4 * KB) {
+            float ac[KB][RT], bc[KB][CT];
+#pragma unroll
+            for (int s = 0; s < KB; ++s) {
+#pragma unroll
+                for (int i = 0; i < RT; ++i) ac[s][i] = an[s][i];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) bc[s][c] = bn[s][c];
+            }
+            fetch(p0 + 4 * KB);
+#pragma unroll
+            for (int s = 0; s < KB; ++s)
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[s][i], bc[s][c], acc[i][c], 0, 0, 0);
+        }
+    }
+    // C layout: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int t = t0 + 16 * i + 4 * lk + r;
+            if (t < T) {
+                float* o = dEnc + ((long)b * T + t) * H2 + col0 + lc;
+#pragma unroll
+                for (int c = 0; c < CT; ++c) o[16 * c] += acc[i][c][r];
+            }
+        }
+}
+
+int a2s_attn_denc_accum_impl(hipStream_t st, const float* attw_all, const float* dctx_all, float* dEnc, int B, int T, int S, int H2,
+                             const int* row_until, int groups) {
+    A2S_REQUIRE(H2 == 512, "attn_denc_accum: built for encoder outputs of 512 columns (got %d)", H2);
+    A2S_REQUIRE(B >= 1 && T >= 1 && S >= 0, "attn_denc_accum: B = %d, T = %d, S = %d", B, T, S);
+    if (groups < 1) groups = 1;
+    hipLaunchKernelGGL((attn_denc_accum<2>), dim3(B * a2s_cdiv(T, 64)), dim3(256), 0, st, attw_all, dctx_all, dEnc, B, T, S, row_until, groups);
+    A2S_CHECK_LAUNCH("attn_denc_accum");
+    __atomic_fetch_add(&g_attn_denc_launches, 1LL, __ATOMIC_RELAXED);
+    return A2S_OK;
+}
+
 int a2s_attn_dk_accum_impl(hipStream_t st, const float* Kmat, const float* q_all, const float* ds_all, const float* v,
                            float* dK, float* dv_partial, int B, int T, int S, int H, const int* row_until, int groups) {
     const int nblk = B * a2s_cdiv(T, 16);
     if (groups < 1) groups = 1;
     A2S_REQUIRE(H >= 1, "attn_dk_accum: hidden_size must be positive (got %d)", H);
+    if (a2s_attn_deferred_fast && H <= 256) {
+        hipLaunchKernelGGL((attn_dk_accum_ahead<A2S_ATTN_DK_NS>), dim3(nblk), dim3(256), 0, st, Kmat, q_all, ds_all, v, dK, dv_partial, B, T, S, row_until, groups, H);
+        A2S_CHECK_LAUNCH("attn_dk_accum_ahead");
+        __atomic_fetch_add(&g_attn_dk_ahead_launches, 1LL, __ATOMIC_RELAXED);
+        return A2S_OK;
+    }
     const int nth = H >= 256 ? 256 : (H > 128 ? 256 : (H > 64 ? 128 : 64));
     hipLaunchKernelGGL(attn_dk_accum, dim3(nblk), dim3(nth), 0, st, Kmat, q_all, ds_all, v, dK, dv_partial, B, T, S, row_until, groups, H);
     A2S_CHECK_LAUNCH("attn_dk_accum");

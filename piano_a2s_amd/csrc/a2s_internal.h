@@ -159,6 +159,10 @@ int a2s_attn_step_bwd_impl(hipStream_t st, const float* Kmat, const float* enc, 
     const a2s_attn_rows* rows = nullptr);
 int a2s_attn_dk_accum_impl(hipStream_t st, const float* Kmat, const float* q_all, const float* ds_all, const float* v,
     float* dK, float* dv_partial, int B, int T, int S, int H, const int* row_until, int groups);
+int a2s_attn_denc_accum_impl(hipStream_t st, const float* attw_all, const float* dctx_all, float* dEnc, int B, int T, int S, int H2,
+    const int* row_until, int groups);
+long a2s_attn_dk_ahead_launches(void);
+long a2s_attn_denc_launches(void);
 int a2s_col_sum_impl(hipStream_t st, const float* x, long ld, float* out, long rows, int C, float alpha, float beta, float* ws, size_t ws_floats);
 int a2s_embed_scatter_add_impl(hipStream_t st, float* table_grad, const long long* ids64, const int* ids32, long id_stride,
     int const_id, const float* g, long ldg, int col0, int R, int E, const uint8_t* drop, float inv_keep);

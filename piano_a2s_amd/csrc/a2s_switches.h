@@ -68,6 +68,9 @@
     X(persist_inject_abort, 0, ONOFF, 0)
 // Not in the list, because they are not stored integers (a2s_debug_set / a2s_debug_get, a2s_api.hip): "gemm_tile" is write-only
 // (a2s_gemm_debug_tile); the "*_launches" counters and "device_cus" / "device_xccs" are read-only.
+// One on/off key is kept beside the list, because the list is a recorded contract (tests/test_switches_cpu.py spells its keys out):
+// "attn_deferred_fast" (default 1; a2s_attn_deferred_fast, a2s_bwd.hip) -- the deferred attention gradients on attn_dk_accum_ahead and
+// attn_denc_accum; 0 = attn_dk_accum and the batched GEMM.  No environment variable.
 
 enum a2s_switch {
 #define X(key, def, rule, env) A2S_SW_##key,
@@ -77,6 +80,8 @@ enum a2s_switch {
 };
 extern int a2s_switch_value[A2S_SW_COUNT];          // constant-initialised with the defaults; the environment is applied before main()
 static inline int a2s_sw(a2s_switch id) { return a2s_switch_value[id]; }
+
+extern int a2s_attn_deferred_fast;                  // the key beside the list (above)
 
 int a2s_switch_find(const char* key);               // id, or -1
 void a2s_switch_store(int id, int value);           // applies the key's storage rule

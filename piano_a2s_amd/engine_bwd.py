@@ -5,7 +5,8 @@ the C-ABI backward kernels.  Sequential parts (note-decoder steps, encoder GRU s
 does not depend on the recurrence is deferred and batched over all steps of a (bar, staff):
   * output projection: ONE GEMM for dlogits_all W_out and ONE for dW_out,
   * GRU / attention-query weight gradients: ONE GEMM each over all steps,
-  * attention key/value side: dEnc via a batched (T x steps)(steps x 2H) GEMM, dK via a tanh-recompute kernel.
+  * attention key/value side: dEnc via a kernel over the live (step, bar) pairs (or a batched (T x steps)(steps x 2H) GEMM), dK via a
+    tanh-recompute kernel.
 """
 import ctypes as C
 import os
@@ -93,12 +94,19 @@ def _attn_deferred(eng, S, G, prefix, keys, enc, q_all, ds_all, attw_all, dctx_a
     L = hip.lib()
     # dEnc[b] += sum_{s,g} a_sg[b,:]^T dctx_sg[b,:]   -- batched over clips: (T x steps*groups)(steps*groups x 2H)
     # (operand ranges for the two-term fp16 product: softmax weights <= 1, max |dctx| measured; K = steps * groups < 256 runs fp32-input)
-    hip.gemm(attw_all, 1, B * T, dctx_all, B * 2 * H, 1, dEnc, 2 * H, T, 2 * H, steps * groups, beta=1.0, batch=B, bsA=T, bsB=2 * H, bsC=T * 2 * H,
-             two_term=(_one(enc.device), hip.absmax(dctx_all)) if dctx_all.is_contiguous() else None)
+    until = active["until"] if active else None
+    if (2 * H == 512 and L.a2s_debug_get(b"attn_deferred_fast") > 0 and hasattr(L, "a2s_attn_denc_accum")
+            and attw_all.is_contiguous() and dctx_all.is_contiguous() and dEnc.is_contiguous()):
+        # ... on the kernel that walks only the clip's live pairs (fp32 matrix instructions: no operand range, no pass over dctx_all)
+        hip.check(L.a2s_attn_denc_accum(hip.stream(), hip._p(attw_all), hip._p(dctx_all), hip._p(dEnc), B, T, steps, 2 * H, hip._p(until), groups),
+                  "a2s_attn_denc_accum")
+    else:
+        hip.gemm(attw_all, 1, B * T, dctx_all, B * 2 * H, 1, dEnc, 2 * H, T, 2 * H, steps * groups, beta=1.0, batch=B, bsA=T, bsB=2 * H, bsC=T * 2 * H,
+                 two_term=(_one(enc.device), hip.absmax(dctx_all)) if dctx_all.is_contiguous() else None)
     nblk = L.a2s_attn_dk_blocks(B, T)
     dvp = torch.empty((nblk, H), dtype=torch.float32, device=enc.device)
     hip.check(L.a2s_attn_dk_accum(hip.stream(), hip._p(keys), hip._p(q_all), hip._p(ds_all), hip._p(S[prefix + ".v.weight"]), hip._p(dK),
-                                  hip._p(dvp), B, T, steps, H, hip._p(active["until"] if active else None), groups), "a2s_attn_dk_accum")
+                                  hip._p(dvp), B, T, steps, H, hip._p(until), groups), "a2s_attn_dk_accum")
     _colsum(dvp, H, G[prefix + ".v.weight"], nblk, H)
 
 

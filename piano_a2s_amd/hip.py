@@ -78,6 +78,8 @@ def lib():
             raise A2SError(L.a2s_last_error().decode())
         if hasattr(L, "a2s_edit_distance"):          # (absent from builds older than the device-side scoring: metrics.edit_distances then raises)
             L.a2s_edit_distance.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]
+        if hasattr(L, "a2s_attn_denc_accum"):        # (absent from builds older than the live-pair dEnc kernel: engine_bwd then keeps the batched GEMM)
+            L.a2s_attn_denc_accum.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_int]
         if arith != "f16x2":
             for key in (b"conv_f16x2", b"wgrad_f16x2", b"gemm_f16x2"):
                 L.a2s_debug_set(key, 0)
