@@ -310,6 +310,31 @@ int a2s_beam_step(void* stream, const a2s_beam_args* beam, const float* logits, 
                   float* q, int q_cols, int* n_done, int* steps_exec, int B, int V, int E, int t, int max_steps, int eos_id);
 int a2s_beam_backtrack(void* stream, const a2s_beam_args* beam, float* probs, long probs_bstride, const int* steps_exec, int B, int V, int max_steps, int eos_id);
 int a2s_beam_launches(void);
+/* ---- audio alignment from the attention weights (csrc/a2s_align.hip).  Frame t of the encoder outputs is t * hop_length /
+ * sample_rate seconds of audio, and every bar step and note step forms softmax weights over the T frames.  a2s_attn_align_rows reduces R rows of
+ * such weights (attw, row stride ldw >= T floats: what the attention entry points write through `attw`) to peak = the lowest frame index among the
+ * row's maxima (int32), weight = attw[peak] bit for bit, and centroid = sum_t t * attw[t] in fp32 (not renormalised); row r's results go to
+ * peak_out / weight_out / centroid_out[r * out_stride], so that a decode step writes one column of an (R, max_steps) array.  A row of zeros (its
+ * attention was skipped) gives (0, 0, 0).  One wave per row.  Null pointers, R < 0, T < 1, ldw < T or out_stride < 1: A2S_ERR_ARG, nothing is
+ * launched; R = 0 returns 0 and launches nothing.  a2s_align_launches: launches so far (proof of the path).
+ * a2s_note_decoder_fwd_align: a2s_note_decoder_fwd that also records, per step t and row, where the row attended to.  It takes GREEDY calls
+ * (args->gt NULL; with align->next_state the constrained decoder of a2s_note_decoder_fwd_grammar) and TEACHER-FORCED calls (args->gt and
+ * args->tf_flags given, args->poll 0; a grammar is then an argument error) -- the forced alignment of a known score; neither may carry the training
+ * buffers (gates, attw, drop) or the row bookkeeping (n_active, row_list, m_active, clip_order, row_until): A2S_ERR_ARG otherwise, nothing is
+ * launched.  Always the launch-per-step loop (mid-size kernels at H = 256, library-style products otherwise; never the persistent or the few-row
+ * decoders; args->use_graph is ignored): every step's attention writes its weights to align->attw_step, a2s_attn_align_rows follows on the same
+ * stream and writes column t.  Everything else of a step, and so every output of a2s_note_decoder_fwd, is unchanged.  Columns of steps the call
+ * never runs are left untouched: the caller pre-fills peak -1, weight 0, centroid -1. */
+typedef struct a2s_align_args {
+    float* attw_step;                        /* device, (R, T) floats: the weights of ONE step, the same slot every step */
+    int* peak; float* weight; float* centroid;     /* device, (R, max_steps) each: row r, step t at r * out_stride + t */
+    long out_stride;                         /* >= args->steps */
+    const signed char* next_state; int n_states;   /* the grammar's table as in a2s_note_decoder_fwd_grammar; NULL / 0: none */
+    int* row_state;                          /* device, R ints (with a grammar) */
+} a2s_align_args;
+int a2s_attn_align_rows(void* stream, const float* attw, long ldw, int R, int T, int* peak_out, float* weight_out, float* centroid_out, long out_stride);
+int a2s_note_decoder_fwd_align(void* stream, const a2s_note_dec_args* args, const a2s_align_args* align, int* steps_done);
+int a2s_align_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -79,12 +79,15 @@ class _Transcribe(torch.autograd.Function):
             eng.kern_grammar = module._kern_grammar()
         if inference:
             eng.beam_size, eng.beam_length_penalty = module.beam_size, module.beam_length_penalty
+        eng.alignment = bool(module.alignment) and not module.training
         module.last_decoded = None
         module.last_beam_scores = None
+        module.last_alignment = None
         outs = eng.forward(S, spectrogram, inference=inference, ground_truth=ground_truth, teacher_forcing_ratio=tf_ratio,
                            training=module.training, rng=random, dropout=True)
         module.last_decoded = eng.decoded
         module.last_beam_scores = eng.beam_scores
+        module.last_alignment = eng.alignment_out
         ctx.eng, ctx.S, ctx.names, ctx.can_backward = eng, S, names, module.training
         if not need_grad:
             eng.saved = None          # nothing to keep alive
@@ -112,6 +115,14 @@ class ScoreTranscription(nn.Module):
     beam_size = 1
     beam_length_penalty = 0.0
     last_beam_scores = None
+    # True: every forward in evaluation mode (inference, or teacher-forced with ground truth: the forced alignment of a known score) also reports where
+    # in the audio each bar and each note token lies (csrc/a2s_align.hip): `last_alignment` = {"bar": {...}, "up": {...},
+    # "lo": {...}}, each with `peak` (int32: the encoder frame with the largest attention weight), `weight` (that weight; a flat row marks a token
+    # the model placed nowhere in particular) and `centroid` (sum_t t * a[t], in frames), of shape (B, bars) / (B, bars, max_length); frame t is
+    # t * hop_length / sample_rate seconds.  Where no step ran: peak -1, weight 0, centroid -1.  False (default): `last_alignment` is None and the
+    # decoders run exactly as without the option.  A forward in training mode does not align (`last_alignment` is None).
+    alignment = False
+    last_alignment = None
 
     def _kern_grammar(self):
         if getattr(self, "_grammar", None) is None:

@@ -229,6 +229,14 @@ int a2s_beam_backtrack(void* stream, const a2s_beam_args* beam, float* probs, lo
     return a2s_beam_backtrack_impl(ST, a);
 }
 int a2s_beam_launches(void) { return a2s_beam_launches_impl(); }
+int a2s_attn_align_rows(void* stream, const float* attw, long ldw, int R, int T, int* peak_out, float* weight_out, float* centroid_out, long out_stride) {
+    return a2s_attn_align_rows_impl(ST, attw, ldw, R, T, peak_out, weight_out, centroid_out, out_stride);
+}
+int a2s_note_decoder_fwd_align(void* stream, const a2s_note_dec_args* args, const a2s_align_args* align, int* steps_done) {
+    if (!args || !align) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_align: null args"); return A2S_ERR_ARG; }
+    return a2s_note_decoder_fwd_align_impl(ST, *args, *align, steps_done);
+}
+int a2s_align_launches(void) { return a2s_align_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

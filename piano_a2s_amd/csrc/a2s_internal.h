@@ -201,6 +201,13 @@ int a2s_grammar_argmax_rows_impl(hipStream_t st, const float* x, long ldx, float
 int a2s_grammar_step_finalize_impl(hipStream_t st, const StepFinArgs& a, const a2s_grammar_ref& g);
 int a2s_grammar_launches_impl(void);
 
+// ---- a2s_align.hip
+// n_done / n_rows_total (the decode loop's greedy calls, else null / 0): the launch is a no-op once every row has shown <eos>, as the step's attention
+int a2s_attn_align_rows_impl(hipStream_t st, const float* attw, long ldw, int R, int T, int* peak_out, float* weight_out, float* centroid_out,
+    long out_stride, const int* n_done = nullptr, int n_rows_total = 0);
+int a2s_align_launches_impl(void);
+int a2s_note_decoder_fwd_align_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_align_args& g, int* steps_done);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -518,7 +518,7 @@ static int enqueue_query(hipStream_t st, const NoteDecArgs& a, int si, int sv) {
 // of slot sv must already be there (enqueue_query / the previous step), this step leaves the next one's in slot sv_next (!last).
 static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int so, int sv, int t, const int* t_base, int tf,
                              bool fused = false, int sv_next = 0, bool last = false, const AttnPairStep* pair = nullptr,
-                             const a2s_grammar_ref* grammar = nullptr, const a2s_beam_args* beam = nullptr) {
+                             const a2s_grammar_ref* grammar = nullptr, const a2s_beam_args* beam = nullptr, const a2s_align_args* align = nullptr) {
     const int H2 = 2 * a.H, ldx = a.E + H2;
     if (fused) {
         float* xs = a.x + (long)si * a.R * ldx;
@@ -553,6 +553,8 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     const a2s_attn_rows rows_b = {nullptr, nullptr, nullptr, a.n_clips, a.n_clips, t};
     if (beam) rows = &rows_b;
     const int* attn_done = (a.gt || (beam && beam->K > 1)) ? nullptr : a.n_done;
+    // alignment (a2s_align.hip): the step's weights go to the one-step slot, attn_align_rows reduces them into column t behind the attention launch
+    float* attw_s = align ? align->attw_step : (a.attw ? a.attw + (long)sv * a.R * a.T : nullptr);
     float* q_left = nullptr;                  // the next step's query, where this step leaves it behind (a beam re-parents it with the state)
     if (note_step_mid(a, t_base)) {
         // round 6 (a2s_step.hip): the query of slot sv is already there (enqueue_query / the previous step, as on the few-row path); behind the
@@ -560,9 +562,9 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
         // the rows still running
         // (pair: the sweep of this step has been launched for both staves at once -- only this staff's combine is left)
         rc = pair ? attn_pair_combine(st, a, si, sv, *pair)
-                  : a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2,
-                                           a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, attn_done, a.R, a.attn_ws, rows);
+                  : a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, attw_s, a.R, a.T, a.H, attn_done, a.R, a.attn_ws, rows);
         if (rc) return rc;
+        if (align) { rc = a2s_attn_align_rows_impl(st, attw_s, a.T, a.R, a.T, align->peak + t, align->weight + t, align->centroid + t, align->out_stride, attn_done, a.R); if (rc) return rc; }
         const int nrows = note_step_rows(a, t);
         rc = a2s_note_step_mid_gru(st, a, si, so, sv, last ? -1 : sv_next, nrows, nrows < a.R ? a.row_list : nullptr);
         if (rc) return rc;
@@ -575,10 +577,10 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     rc = a2s_gemm_impl(st, gM, 3 * H2, H2, 1.f, hp, H2, 1, a.w_hh, 1, H2, 0.f, a.gh, 3 * H2, a.b_hh, 0, gB, gS * H2, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
     if (rc) return rc;
     // attention -> ctx into x[si][:, E:] and o[sv][:, 2H:]
-    rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2,
-                                a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, attn_done, a.R, a.attn_ws,
+    rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, attw_s, a.R, a.T, a.H, attn_done, a.R, a.attn_ws,
                                 rows);
     if (rc) return rc;
+    if (align) { rc = a2s_attn_align_rows_impl(st, attw_s, a.T, a.R, a.T, align->peak + t, align->weight + t, align->centroid + t, align->out_stride, attn_done, a.R); if (rc) return rc; }
     // gi = x W_ih^T + b_ih
     rc = a2s_gemm_impl(st, gM, 3 * H2, ldx, 1.f, xs, ldx, 1, a.w_ih, 1, ldx, 0.f, a.gi, 3 * H2, a.b_ih, 0, gB, gS * ldx, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
     if (rc) return rc;
@@ -707,6 +709,40 @@ int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, cons
     A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_grammar: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
     A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_grammar: null bookkeeping or output buffers");
     return note_decoder_fwd_loop(st, a, steps_done, &g);
+}
+
+// Decoding with the audio alignment of every step: the launch-per-step loop of note_decoder_fwd_loop -- greedy,
+// greedy under a grammar, or teacher-forced in evaluation mode -- with the step's attention weights kept for one step and reduced into column t of
+// the alignment arrays.  Never the persistent, few-row or graph paths: their attention does not write the weights of an inference step.
+int a2s_note_decoder_fwd_align_impl(hipStream_t st, const NoteDecArgs& a, const a2s_align_args& g, int* steps_done) {
+    A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list && !a.m_active && !a.clip_order && !a.row_until,
+                "note_decoder_fwd_align: inference only (training buffers or row bookkeeping given)");
+    A2S_REQUIRE(!(a.gt && (g.next_state || g.n_states || g.row_state)), "note_decoder_fwd_align: a grammar constrains greedy decoding only (ground truth given)");
+    A2S_REQUIRE(a.gt ? (a.tf_flags && a.poll == 0) : !a.tf_flags_dev, "note_decoder_fwd_align: a teacher-forced call needs tf_flags and poll = 0, a greedy call no device flags");
+    A2S_REQUIRE(a.R > 0 && a.T >= 1 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs && a.h && a.x && a.q && a.o,
+                "note_decoder_fwd_align: null bookkeeping or output buffers");
+    A2S_REQUIRE(g.attw_step && g.peak && g.weight && g.centroid && g.out_stride >= a.steps && g.out_stride >= 1,
+                "note_decoder_fwd_align: needs the one-step weights scratch, the three outputs and a row stride >= steps (got %ld for %d steps)", g.out_stride, a.steps);
+    const bool with_grammar = g.next_state || g.n_states || g.row_state;
+    const a2s_grammar_ref gr = {g.next_state, g.n_states, g.row_state};
+    A2S_REQUIRE(!with_grammar || a2s_grammar_ref_ok(gr, a.R, a.V), "note_decoder_fwd_align: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
+    const bool mid = note_step_mid(a, nullptr);
+    int s = 0;
+    for (; s < a.steps; ++s) {
+        if (mid && s == 0) { const int rc = enqueue_query(st, a, 0, 0); if (rc) return rc; }       // every later query is left behind by the previous step
+        const int rc = enqueue_note_step(st, a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, false, s + 1, s + 1 == a.steps, nullptr,
+                                         with_grammar ? &gr : nullptr, nullptr, &g);
+        if (rc) return rc;
+        if (!a.gt && a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
+            int done = 0;
+            hipError_t e = hipMemcpyAsync(&done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_align poll: %s", hipGetErrorString(e));
+            if (done >= a.R) { ++s; break; }
+        }
+    }
+    if (steps_done) *steps_done = s;
+    return A2S_OK;
 }
 
 // Beam search over one greedy call: K slots per clip as extra rows, the launch-per-step loop with the beam

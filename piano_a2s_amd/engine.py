@@ -330,6 +330,13 @@ class Engine:
         self.beam_size = 1
         self.beam_length_penalty = 0.0
         self.beam_scores = None
+        # audio alignment from the attention weights (csrc/a2s_align.hip).  False (default): nothing of it is allocated, enqueued
+        # or read.  True (not in training mode): every note-decoder call runs the launch-per-step loop of a2s_note_decoder_fwd_align, one plain call
+        # per bar and staff (no persistent group, no graph replay), and after the forward `alignment_out` = {"bar": {...}, "up": {...}, "lo": {...}}, each
+        # with `peak` int32 (the frame with the largest attention weight), `weight` (that weight) and `centroid` (sum_t t * a[t], in frames) float32, of
+        # shape (B, bars) for "bar" and (B, bars, max_length) for the staves; where no step ran: peak -1, weight 0, centroid -1
+        self.alignment = False
+        self.alignment_out = None
         # Synchronised BatchNorm (what SpeechBrain's DDP wrapping gives the reference): batch statistics over the
         # GLOBAL minibatch -- per-channel (sum, sum of squares, count) are all-reduced between the ranks.  Off by default:
         # per-rank statistics (plain DDP semantics).  Needs an initialised process group.
@@ -526,10 +533,26 @@ class Engine:
             if grammar.vocab_size != V:
                 raise hip.A2SError(f"Engine.kern_grammar is a table over {grammar.vocab_size} symbols, the decoder's vocabulary has {V}")
             persist = False
+        align = bool(self.alignment) and not training
+        if align:
+            if active is not None or defer_launch:
+                raise hip.A2SError("alignment decodes bar by bar: no fused bars, no pair loop")
+            persist, graph = False, False
         if gt_bar is None and not training and self._beam_slots():
             if active is not None or defer_launch:
                 raise hip.A2SError("beam search decodes bar by bar: no fused bars, no pair loop")
-            return self._decode_staff_beam(S, prefix, keys, enc, h0, max_steps, probs_bar, n, B, T, grammar, self._beam_slots())
+            ids_, lengths_, saved = self._decode_staff_beam(S, prefix, keys, enc, h0, max_steps, probs_bar, n, B, T, grammar, self._beam_slots())
+            if align:
+                # a beam re-parents its rows every step: the winners are aligned by ONE teacher-forced call over the B winning rows from the same h0, their
+                # ids as ground truth and every step forced, into scratch log-probabilities (about 1 / K of the beam call; no history in a2s_beam.hip)
+                # (as many steps as the reference's loop takes over these ids: until every winner has shown <eos> -- the beam itself may have run on for its losers)
+                gt_ids = ids_.long()
+                n_forced = plan_note_steps(gt_ids.cpu(), max_steps)[0]
+                scratch = torch.zeros((B, max_steps, V), dtype=torch.float32, device=dev)
+                forced = self._decode_staff(S, prefix, keys, enc, h0, max_steps, scratch, gt_ids, n_forced, [1] * n_forced, False, 0.0, B, T,
+                                            attn_ws=attn_ws, gemm_ws=gemm_ws)[2]
+                saved["align"], saved["align_forced"] = forced["align"], forced
+            return ids_, lengths_, saved
         t_base = torch.zeros(1, dtype=torch.int32, device=dev) if graph else None
         # (with row_list the tail steps write only the rows still running; a2s_note_decoder_fwd zero-fills these buffers itself -- from C,
         # where a memset that has to wait for room in a busy stream's queue does not hold the interpreter lock)
@@ -609,6 +632,18 @@ class Engine:
         if defer_launch:                      # _decode_pair: the arguments are ready, the caller launches both staves with one call
             return a, finish
         done = C.c_int(0)
+        if align:
+            g, at = hip.align_buffers(B, max_steps, T, dev)
+            row_state = None
+            if grammar is not None:
+                row_state = torch.full((B,), grammar.start, dtype=torch.int32, device=dev)
+                g.next_state, g.n_states, g.row_state = grammar.device_table(dev).data_ptr(), grammar.n_states, row_state.data_ptr()
+            hip.check(L.a2s_note_decoder_fwd_align(hip.stream(), C.byref(a), C.byref(g), C.byref(done)), "a2s_note_decoder_fwd_align")
+            ids_, lengths_, saved = finish(done.value)
+            saved["align"] = at
+            if row_state is not None:
+                saved["row_state"] = row_state
+            return ids_, lengths_, saved
         if grammar is not None:
             row_state = torch.full((B,), grammar.start, dtype=torch.int32, device=dev)
             hip.check(L.a2s_note_decoder_fwd_grammar(hip.stream(), C.byref(a), hip._p(grammar.device_table(dev)), grammar.n_states, hip._p(row_state),
@@ -713,6 +748,10 @@ class Engine:
         B, _, T, F = spectrogram.shape
         dev = spectrogram.device
         drop_on = training and dropout
+        align = bool(self.alignment)
+        if align and training:
+            raise ValueError("Engine.alignment is an inference / evaluation feature: not with training=True")
+        self.alignment_out = None
 
         gt_cpu = None
         if ground_truth is not None:
@@ -808,7 +847,7 @@ class Engine:
         ldxb = tokw + 2 * H
         # beam search (csrc/a2s_beam.hip) runs the launch-per-step loop only: no graph replay, no persistent decoder
         beam = gt_cpu is None and not training and self._beam_slots() > 0
-        greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH) and not beam
+        greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH) and not beam and not align
         constrained = (self.kern_grammar is not None or beam) and gt_cpu is None and not training     # (the persistent decoder's epilogue holds its own argmax)
         # the two staves of a segment run on two streams, each issued by its own host thread -- also in greedy decoding, where each
         # thread polls the done counter of its own stream (the hipGraph variant captures on one created stream and stays sequential)
@@ -847,7 +886,7 @@ class Engine:
             # per step, and the step from 514 to 540 ms (profiles/r04_dec_persist_beside_bulk.txt).
             alone = len(clip_groups) == 1 or _PERSIST_BESIDE
             persist_g = (Bg <= 8 and gidx == len(clip_groups) - 1 and alone and H == 256 and E == 16 and (plan is not None or (inference and not greedy_graph))
-                         and hip.lib().a2s_debug_get(b"dec_persist") != 0 and not constrained)
+                         and hip.lib().a2s_debug_get(b"dec_persist") != 0 and not constrained and not align)
             concurrent_g = concurrent and staves_concurrent(gidx, len(clip_groups)) and not persist_g
             streams = staff_streams(dev, gidx) if concurrent_g else None
 
@@ -947,6 +986,11 @@ class Engine:
                                        cfg["num_keys"], hip._p(token), C.c_long(tokw), 4 * Sz + te, Bg, ke, C.c_void_p(0), hip.f32(1.0)), "embed key")
 
             bar_saved, seg_saved = [], []
+            # alignment of the bar-level attention: one column per bar (steps of bars never reached keep the fills)
+            bar_align = None
+            if align:
+                bar_align = dict(peak=torch.full((Bg, bars), -1, dtype=torch.int32, device=dev), weight=torch.zeros((Bg, bars), dtype=torch.float32, device=dev),
+                                 centroid=torch.full((Bg, bars), -1.0, dtype=torch.float32, device=dev))
             max_rows = Bg * max(len(sg) for sg in segments)
             # per-staff scratch (split-T attention partials, split-K slabs): the two staves run concurrently on two streams
             attn_ws = [hip.attn_workspace(Bg, T, H, dev, groups=max_rows // Bg) for _ in range(2)]
@@ -965,7 +1009,7 @@ class Engine:
                 qb = self._empty(Bg, H, dev=dev)
                 Wa = S["decoder.attn.attn.weight"]
                 hip.gemm(hidden, 2 * H, 1, Wa, 1, 4 * H, qb, H, Bg, H, 2 * H, bias=S["decoder.attn.attn.bias"])
-                attw = self._empty(Bg, T, dev=dev) if training else None
+                attw = self._empty(Bg, T, dev=dev) if (training or align) else None
                 # 5 calls per forward.  Round 5: on the split-T kernels when the group is large (their combine writes the context with 4-byte stores, so
                 # the odd stride of the bar-level GRU input row [token(141) | ctx] does not matter to them): 0.85 -> ~0.2 ms per call at 248 clips, in series
                 # with the group's decode; small groups keep the one-workgroup-per-clip kernel
@@ -974,6 +1018,8 @@ class Engine:
                                               hip._p(S["decoder.attn.v.weight"]), C.c_void_p(xbar.data_ptr() + 4 * tokw), C.c_long(ldxb),
                                               C.c_void_p(headin.data_ptr() + 4 * 2 * H), C.c_long(4 * H), hip._p(attw), Bg, T, H,
                                               C.c_void_p(0), 0, hip._p(bar_ws)), "a2s_attn_step_fwd")
+                if align:
+                    hip.attn_align_rows(attw, bar_align["peak"][:, bar], bar_align["weight"][:, bar], bar_align["centroid"][:, bar])
                 gi = hip.linear(xbar, S["decoder.gru.weight_ih_l0"], S["decoder.gru.bias_ih_l0"])
                 gh = hip.linear(hidden, S["decoder.gru.weight_hh_l0"], S["decoder.gru.bias_hh_l0"])
                 hnew = self._empty(Bg, 2 * H, dev=dev)
@@ -1096,7 +1142,7 @@ class Engine:
                 _trace(f"g{gidx} seg {seg_i} joined")
                 token, rec["tok_rec"], rec["next_ids"] = next_token(last, teacher_force, last_rows, rec["heads"])
                 rec["teacher_force"] = teacher_force
-            gs = dict(range=(b0, b1), bars=bar_saved, segments=seg_saved, sos_rec=sos_rec, keys=keys_g, enc=enc_g,
+            gs = dict(range=(b0, b1), bars=bar_saved, segments=seg_saved, sos_rec=sos_rec, keys=keys_g, enc=enc_g, bar_align=bar_align,
                       outs=(ts_out_g, key_out_g, up_out_g, lo_out_g), gt=(ground_truth is not None and (up_g, lo_g)) or None)
             hook = getattr(self, "group_hook", None)
             if hook is not None:
@@ -1128,6 +1174,12 @@ class Engine:
         self.beam_scores = None
         if beam:
             self.beam_scores = {k: torch.stack([sg["staff"][k][2]["beam"]["score_out"] for sg in group_saved[0]["segments"]], dim=1) for k in ("up", "lo")}
+        if align:
+            # (alignment decodes bar by bar in one clip group: one segment per bar)
+            segs = group_saved[0]["segments"]
+            self.alignment_out = {"bar": group_saved[0]["bar_align"]}
+            for k in ("up", "lo"):
+                self.alignment_out[k] = {f: torch.stack([sg["staff"][k][2]["align"][f] for sg in segs], dim=1) for f in ("peak", "weight", "centroid")}
         self.saved = dict(conv=conv_saved, enc=enc_saved, keys=keys, groups=group_saved, enc_out=enc,
                           bars=group_saved[0]["bars"], segments=group_saved[0]["segments"], sos_rec=group_saved[0]["sos_rec"],
                           training=training, concurrent=concurrent, outs=(ts_out, key_out, up_out, lo_out), bar_major=bar_major,

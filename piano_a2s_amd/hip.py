@@ -43,6 +43,12 @@ class BeamArgs(C.Structure):
                                   "ids_out", "lengths_out", "score_out")]
 
 
+class AlignArgs(C.Structure):
+    """Mirror of `a2s_align_args` (include/a2s.h) -- same members, same order."""
+    _fields_ = [("attw_step", C.c_void_p), ("peak", C.c_void_p), ("weight", C.c_void_p), ("centroid", C.c_void_p), ("out_stride", C.c_long),
+                ("next_state", C.c_void_p), ("n_states", C.c_int), ("row_state", C.c_void_p)]
+
+
 class NoteDecBwdArgs(C.Structure):
     """Mirror of `a2s_note_dec_bwd_args` (include/a2s.h) -- same members, same order."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -288,6 +294,41 @@ def beam_backtrack(g, probs, steps_exec, B, V, max_steps, eos_id):
 def beam_launches():
     """Beam step epilogues the library has launched in this process (a2s_beam_launches)."""
     return int(lib().a2s_beam_launches())
+
+
+def attn_align_rows(attw, peak, weight, centroid, T=None, R=None):
+    """a2s_attn_align_rows: rows of attention weights attw (R, >= T) float32 -> per row the peak frame (int32), its weight and the centroid
+    sum_t t * attw[t] (float32), written to element 0 of row r of peak / weight / centroid (1-D of R elements, or one column of an (R, steps) array:
+    the stride of dimension 0 is the output stride the three must share)."""
+    R = attw.shape[0] if R is None else R
+    T = attw.shape[1] if T is None else T
+    if attw.dtype != torch.float32 or peak.dtype != torch.int32 or weight.dtype != torch.float32 or centroid.dtype != torch.float32:
+        raise A2SError("attn_align_rows: expects float32 weights, an int32 peak and float32 weight / centroid outputs")
+    stride = peak.stride(0) if peak.dim() else 1
+    if any((o.stride(0) if o.dim() else 1) != stride or (o.shape[0] if o.dim() else 1) < R for o in (peak, weight, centroid)):
+        raise A2SError("attn_align_rows: the three outputs need R rows and one common row stride")
+    check(lib().a2s_attn_align_rows(stream(), _p(attw), C.c_long(attw.stride(0) if attw.dim() > 1 else T), R, T, _p(peak), _p(weight), _p(centroid), C.c_long(stride)),
+          "a2s_attn_align_rows")
+
+
+def align_launches():
+    """attn_align_rows launches of this process (a2s_align_launches)."""
+    return int(lib().a2s_align_launches())
+
+
+def align_buffers(R, max_steps, T, device):
+    """The outputs of one alignment call (a2s_align_args) over R rows: -> (AlignArgs, dict of the tensors it points to), pre-filled with what a step
+    that never runs keeps: peak -1, weight 0, centroid -1."""
+    t = dict(attw_step=torch.zeros((R, T), dtype=torch.float32, device=device),
+             peak=torch.full((R, max_steps), -1, dtype=torch.int32, device=device),
+             weight=torch.zeros((R, max_steps), dtype=torch.float32, device=device),
+             centroid=torch.full((R, max_steps), -1.0, dtype=torch.float32, device=device))
+    g = AlignArgs()
+    for name in ("attw_step", "peak", "weight", "centroid"):
+        setattr(g, name, t[name].data_ptr())
+    g.out_stride = max_steps
+    g.next_state, g.n_states, g.row_state = None, 0, None
+    return g, t
 
 
 def check(rc, what):

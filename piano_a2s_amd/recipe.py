@@ -75,8 +75,23 @@ class ASR(sb.Brain):
             raise ValueError(f"--beam_size needs a transcription module that decodes by beam search; {type(model).__name__} has no `beam_size` attribute")
         model.beam_size, model.beam_length_penalty = K, float(getattr(self.hparams, "beam_length_penalty", 0.0))
 
+    def _alignment(self):
+        """--alignment=true (an optional override as --constrained_decoding): VALID / TEST also record where in the audio every decoded bar and token lies."""
+        v = getattr(self.hparams, "alignment", False)
+        return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
+    def _set_alignment(self):
+        if not self._alignment():
+            return
+        model = self.modules.transcription
+        model = getattr(model, "module", model)                      # (a DistributedDataParallel wrapper)
+        if not hasattr(model, "alignment"):
+            raise ValueError(f"--alignment needs a transcription module that reports the attention alignment; {type(model).__name__} has no `alignment` attribute")
+        model.alignment = True                                       # (takes effect in evaluation mode only: a training forward does not align)
+
     def _set_constrained_decoding(self):
         self._set_beam()
+        self._set_alignment()
         if not self._constrained():
             return
         model = self.modules.transcription
@@ -120,8 +135,21 @@ class ASR(sb.Brain):
             up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
         ts_ids, key_ids = ts_o.argmax(-1).cpu().numpy(), key_o.argmax(-1).cpu().numpy()
         up_t, lo_t, ts_t, key_t = up_t.cpu().numpy(), lo_t.cpu().numpy(), ts_t.cpu().numpy(), key_t.cpu().numpy()
+        al = None
+        if self._alignment():
+            model = self.modules.transcription
+            al = {k: {f: t.cpu().numpy() for f, t in v.items()} for k, v in getattr(model, "module", model).last_alignment.items()}
         for b, name in enumerate(names):
             cid = self._clip_id(name, versions[b])
+            if al is not None:
+                # per bar one centroid (in frames), per staff and bar one per KEPT token: trimmed exactly as metrics.unpad trims the ids
+                kept = {k: [len(metrics.unpad(r)) for r in ids[b]] for k, ids in (("up", up_ids), ("lo", lo_ids))}
+                rec = {"frames_per_second": self.hparams.sample_rate / self.hparams.hop_length,
+                       "bar": al["bar"]["centroid"][b].tolist(), "bar_weight": al["bar"]["weight"][b].tolist()}
+                for key, k in (("upper", "up"), ("lower", "lo")):
+                    rec[key] = [al[k]["centroid"][b, i, :n].tolist() for i, n in enumerate(kept[k])]
+                    rec[key + "_weight"] = [al[k]["weight"][b, i, :n].tolist() for i, n in enumerate(kept[k])]
+                self.alignment_records[cid] = rec
             self.upper_pred[cid] = [metrics.unpad(r).tolist() for r in up_ids[b]]
             self.upper_target[cid] = [metrics.unpad(r).tolist() for r in up_t[b]]
             self.lower_pred[cid] = [metrics.unpad(r).tolist() for r in lo_ids[b]]
@@ -195,6 +223,7 @@ class ASR(sb.Brain):
         if stage != sb.Stage.TRAIN:
             self.upper_pred, self.upper_target, self.lower_pred, self.lower_target = {}, {}, {}, {}
             self.key_pred, self.key_target, self.time_sig_pred, self.time_sig_target = {}, {}, {}, {}
+            self.alignment_records = {}
             for split in ("valid", "test"):
                 mkdirs(os.path.join(self.hparams.output_folder, "results", split))
         self.time_sig_list = load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -236,6 +265,8 @@ class ASR(sb.Brain):
                     for i in range(len(self.upper_pred[cid]))]
             record = {"pred": pred, "wer_upper": wer_up_d[cid], "wer_lower": wer_lo_d[cid], "key_f1": key_f1_d[cid], "time_f1": time_f1_d[cid]}
             record.update(self._clip_record(cid, split))
+            if cid in self.alignment_records:
+                record["alignment"] = self.alignment_records[cid]
             save(record, os.path.join(self.hparams.output_folder, "results", split, f"{cid}.json"))
 
     def _clip_record(self, cid, split):

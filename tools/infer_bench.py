@@ -11,7 +11,10 @@ weights with <eos> bias so decoding terminates at data-dependent steps.  Prints 
     infer_bench.py --compare OUT.json --beam [--batches 256,8] [--repeats 3]
                                         the same for beam search (Engine.beam_size), all under the kern grammar: constrained
                                         greedy on the launch-per-step loop (the like-for-like baseline, run twice per round: its spread against
-                                        itself is the margin of every comparison), the beam loop forced at K = 1, K = 2 and K = 4"""
+                                        itself is the margin of every comparison), the beam loop forced at K = 1, K = 2 and K = 4
+    infer_bench.py --compare OUT.json --align [--batches 256,8] [--repeats 3]
+                                        the same for the audio alignment (Engine.alignment): greedy as shipped (twice per round), greedy
+                                        forced onto the launch-per-step loop, and greedy with alignment"""
 import argparse
 import json
 import os
@@ -31,6 +34,7 @@ ap.add_argument("--constrained", action="store_true")
 ap.add_argument("--stepwise", action="store_true")
 ap.add_argument("--compare", metavar="OUT.json")
 ap.add_argument("--beam", action="store_true")
+ap.add_argument("--align", action="store_true")
 ap.add_argument("--batches", default="256,8")
 ap.add_argument("--repeats", type=int, default=3)
 args = ap.parse_args()
@@ -48,13 +52,15 @@ def set_stepwise(on):
 
 
 def forward(x, variant):
-    """One timed forward of `variant` ("greedy", "stepwise", "constrained", "constrained_again", "beam1", "beam2" or "beam4") -> the record of the run."""
+    """One timed forward of `variant` ("greedy", "greedy_again", "stepwise", "align", "constrained", "constrained_again", "beam1", "beam2" or "beam4") -> the
+    record of the run."""
     set_stepwise(variant == "stepwise")
     eng = engine.Engine(cfg)
+    eng.alignment = variant == "align"
     eng.kern_grammar = GRAMMAR if variant.startswith(("constrained", "beam")) else None
     eng.beam_size = int(variant[4:]) if variant.startswith("beam") else 1
     engine._BEAM_FORCE = variant == "beam1"                 # one slot through the beam loop: what the loop itself costs
-    n0, g0, b0 = L.a2s_launch_count(), hip.grammar_launches(), hip.beam_launches()
+    n0, g0, b0, a0 = L.a2s_launch_count(), hip.grammar_launches(), hip.beam_launches(), hip.align_launches()
     torch.cuda.synchronize(); t0 = time.time()
     try:
         with torch.no_grad():
@@ -78,14 +84,17 @@ def forward(x, variant):
             "us_per_executed_step": round(1e6 * dt / max(steps, 1), 2),
             # every launch of the forward (ConvStack, encoder and bar level included) over the decode steps it launched
             "launches_per_launched_step": round((L.a2s_launch_count() - n0) / max(launched, 1), 2),
-            "grammar_epilogues": hip.grammar_launches() - g0, "beam_epilogues": hip.beam_launches() - b0, "persistent_calls": sum(c.get("persist_ws") is not None for c in calls),
+            "grammar_epilogues": hip.grammar_launches() - g0, "beam_epilogues": hip.beam_launches() - b0, "align_launches": hip.align_launches() - a0, "persistent_calls": sum(c.get("persist_ws") is not None for c in calls),
             "well_formed_bar_share": round(legal_share(rows, GRAMMAR), 4)}
 
 
 if args.compare:
     variants = ("constrained", "constrained_again", "beam1", "beam2", "beam4") if args.beam else ("greedy", "stepwise", "constrained")
+    if args.align:
+        variants = ("greedy", "greedy_again", "stepwise", "align")
     what = ("constrained greedy on the launch-per-step loop (twice: its spread against itself) / the beam loop at K = 1 (forced), 2 and 4, all under the "
-            "kern grammar" if args.beam else "greedy as shipped / forced onto the launch-per-step loop / under the kern grammar")
+            "kern grammar" if args.beam else "greedy as shipped (twice: its spread against itself) / forced onto the launch-per-step loop / with the audio alignment"
+            if args.align else "greedy as shipped / forced onto the launch-per-step loop / under the kern grammar")
     summary = {"what": f"tools/infer_bench.py --compare: {what}; one process, variants alternating, median of the timed forwards", "repeats": args.repeats,
                "batches": {}}
     for B in [int(b) for b in args.batches.split(",")]:
