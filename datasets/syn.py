@@ -6,6 +6,7 @@
 (spectrogram (1,T,F) f32, time_sig (bars,), key (bars,), upper (bars,U), upper_len (bars,), lower (bars,L), lower_len (bars,),
 name, version).  Tensors are built on the host and moved by the trainer one batch at a time (the reference moves every item).
 ``SyntheticClips`` yields seeded random clips of the same contract without any files (benchmarks, smoke runs).
+``RenderedClips`` yields seeded clips whose audio is the sound of their score: a render program in the first slot, synthesised on the GPU.
 """
 import os
 
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from piano_a2s_amd import synthetic
+from piano_a2s_amd import scoregen, synthetic
 from piano_a2s_amd.spec import EOS, PAD
 from utilities import load
 
@@ -110,3 +111,40 @@ class SyntheticWaveClips(SyntheticClips):
         item = super().__getitem__(idx)
         wave = synthetic.make_waveforms(1, self.seed + idx, seconds=(self.frames - 1) / 100.0)[0]
         return (wave,) + item[1:]
+
+
+class RenderedClips(Dataset):
+    """`n` seeded clips of the rendered synthetic corpus (piano_a2s_amd.scoregen): a well-formed **kern score and, in the first
+    slot of the 9-tuple, the (1 + rows, 8) int32 render program of its note events -- the recipe synthesises the batch's waveforms on the GPU
+    (piano_a2s_amd.render) and runs them through the GPU VQT.  `rows` is fixed per dataset, so the default collate stacks the programs."""
+
+    def __init__(self, cfg, n, seed=1234, frames=1201, rows=None):
+        self.cfg, self.n, self.seed, self.frames = cfg, n, seed, frames
+        self.rows = scoregen.MAX_EVENTS if rows is None else rows
+
+    def __len__(self):
+        return self.n
+
+    def clip(self, idx):
+        return scoregen.make_clip(self.cfg, self.seed + idx, frames=self.frames, max_events=self.rows)
+
+    def __getitem__(self, idx):
+        clip = self.clip(idx)
+        U, L = self.cfg["max_length"]
+        bars = self.cfg["max_bars"]
+        ts = torch.full((bars,), clip["ts"], dtype=torch.long)
+        key = torch.full((bars,), clip["key"], dtype=torch.long)
+        upper = torch.stack([pad_measure(ids, U) for ids in clip["ids"]["upper"]])
+        lower = torch.stack([pad_measure(ids, L) for ids in clip["ids"]["lower"]])
+        up_len = torch.tensor([len(ids) for ids in clip["ids"]["upper"]])
+        lo_len = torch.tensor([len(ids) for ids in clip["ids"]["lower"]])
+        program = torch.from_numpy(scoregen.pack_program(clip, rows=self.rows))
+        return program, ts, key, upper, up_len, lower, lo_len, f"ren{self.seed}_{idx}~rendered", 0
+
+    def onsets(self, idx):
+        """The true onset times of clip `idx` in seconds: {"bar": [start of every bar], "upper" | "lower": [[one per token] per bar]} -- a token's time
+        is the onset of its time slice (alignment evaluation)."""
+        clip = self.clip(idx)
+        out = scoregen.token_onsets(clip)
+        out["bar"] = [row[0] / scoregen.SR for row in clip["slice_onsets"]["upper"]]
+        return out

@@ -3,12 +3,12 @@
 
 As the reference's finetune.py (:230-294): starts from the pre-training checkpoints by copying ``<pretrain>/save`` into the new
 output folder and resetting their recorded WER so that the first fine-tuned epoch is kept; fixed teacher-forcing ratio; the test
-split doubles as validation split.  ``--constrained_decoding=true`` and ``--beam_size=K [--beam_length_penalty=A]`` as in pretrain.py."""
+split doubles as validation split.  ``--constrained_decoding=true``, ``--beam_size=K [--beam_length_penalty=A]`` and ``--synthetic_scores=rendered`` as in pretrain.py."""
 import os
 import shutil
 import sys
 
-from piano_a2s_amd.recipe import ASR, sb, write_run_summary
+from piano_a2s_amd.recipe import ASR, sb, synthetic_sets, write_run_summary
 from utilities import load, save
 
 try:
@@ -46,13 +46,7 @@ def main(argv):
 
     n_syn = int(hparams.get("synthetic_clips", 0) or 0)
     if n_syn:
-        from datasets.syn import SyntheticClips
-        cfg = hparams["transcription"].cfg
-        syn = dict(frames=int(hparams.get("synthetic_frames") or hparams["max_frame_num"]))
-        if hparams.get("synthetic_lengths"):
-            syn.update(upper_range=tuple(hparams["synthetic_lengths"][0]), lower_range=tuple(hparams["synthetic_lengths"][1]))
-        train_set = SyntheticClips(cfg, n_syn, seed=hparams["seed"], **syn)
-        valid_set = test_set = SyntheticClips(cfg, max(1, n_syn // 8), seed=hparams["seed"] + 10_000, **syn)
+        train_set, valid_set, test_set = synthetic_sets(hparams, n_syn, test_offset=None, online_vqt=False)
     else:
         from datasets.asap import ASAPDataset
         train_set = ASAPDataset(hparams, "train", run_opts["device"])

@@ -335,6 +335,24 @@ typedef struct a2s_align_args {
 int a2s_attn_align_rows(void* stream, const float* attw, long ldw, int R, int T, int* peak_out, float* weight_out, float* centroid_out, long out_stride);
 int a2s_note_decoder_fwd_align(void* stream, const a2s_note_dec_args* args, const a2s_align_args* align, int* steps_done);
 int a2s_align_launches(void);
+
+/* ---- note synthesiser of the rendered synthetic corpus (csrc/a2s_render.hip).  a2s_render_notes writes the 16 kHz waveforms of B
+ * clips from their render programs: `programs` = device, B * rows_per_clip rows of 8 int32 (floats bit-cast), 16-byte aligned; per clip
+ *     row 0      [n_samples, n_rows, attack, rel_len, rel_rate f32, gain f32, noise_level f32, noise_seed u32]
+ *     rows 1 ..  [onset >= 0, length, inc1 u32 = rint(f0 / 16000 * 2^32), amp f32, decay f32 per sample, g f32, n_harm 1 .. 16, 0]
+ * (rows behind min(n_rows, rows_per_clip - 1), and rows with length <= 0, onset >= n_samples or onset < 0, are padding and skipped whatever else they
+ * hold).  Sample n of clip b goes to wave[b * wave_bstride + n], n in [0, n_samples):
+ *     gain * sum_rows(ascending) amp * env(m) * sum_{h = 1 .. n_harm, h * inc1 < 2^31} g^(h-1) * sin(2 pi x_h(m))  +  noise_level * u(n)
+ *     m = n - onset in [0, length + rel_len),  x_h(m) = ((uint32)(m * h * inc1) >> 8) * 2^-24,
+ *     env(m) = min(1, (m + 1) / attack) * exp(-m * decay) * (m >= length ? exp(-(m - length) * rel_rate) : 1),
+ *     u(n) = (hash32(noise_seed + n * 0x9E3779B9) >> 8) * 2^-23 - 1;  hash32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ * `n_samples` is the caller's (the library reads no device memory back and does not synchronise): the same for every clip of the call; a clip whose
+ * header says less gets zeros behind its own length.  One thread forms a sample's whole sum in a fixed order: the output is bit-identical from run to
+ * run and does not depend on the other clips.  Nothing outside [0, n_samples) of a clip's row of `wave` is written.  Null pointers, B < 0 or > 65535,
+ * rows_per_clip < 1, n_samples < 1, wave_bstride < n_samples, misaligned programs: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches
+ * nothing.  One launch per call; a2s_render_launches: launches so far (proof of the path). */
+int a2s_render_notes(void* stream, const int* programs, int rows_per_clip, int n_samples, float* wave, long wave_bstride, int B);
+int a2s_render_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -237,6 +237,10 @@ int a2s_note_decoder_fwd_align(void* stream, const a2s_note_dec_args* args, cons
     return a2s_note_decoder_fwd_align_impl(ST, *args, *align, steps_done);
 }
 int a2s_align_launches(void) { return a2s_align_launches_impl(); }
+int a2s_render_notes(void* stream, const int* programs, int rows_per_clip, int n_samples, float* wave, long wave_bstride, int B) {
+    return a2s_render_notes_impl(ST, programs, rows_per_clip, n_samples, wave, wave_bstride, B);
+}
+int a2s_render_launches(void) { return a2s_render_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

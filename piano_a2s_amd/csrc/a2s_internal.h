@@ -208,6 +208,10 @@ int a2s_attn_align_rows_impl(hipStream_t st, const float* attw, long ldw, int R,
 int a2s_align_launches_impl(void);
 int a2s_note_decoder_fwd_align_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_align_args& g, int* steps_done);
 
+// ---- a2s_render.hip
+int a2s_render_notes_impl(hipStream_t st, const int* programs, int rows_per_clip, int n_samples, float* wave, long wave_bstride, int B);
+int a2s_render_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

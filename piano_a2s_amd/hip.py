@@ -316,6 +316,27 @@ def align_launches():
     return int(lib().a2s_align_launches())
 
 
+def render_notes(programs, n_samples, wave=None):
+    """a2s_render_notes: programs (B, 1 + E, 8) int32 on the device (scoregen.pack_program) -> the (B, n_samples) float32 waveforms (written into `wave`,
+    a 2-D float32 tensor of at least n_samples columns with unit column stride, when given)."""
+    if programs.dim() != 3 or programs.shape[2] != 8 or programs.dtype != torch.int32 or not programs.is_contiguous():
+        raise A2SError("render_notes: expects contiguous int32 programs of shape (B, 1 + E, 8)")
+    B = programs.shape[0]
+    if wave is None:
+        wave = torch.empty((B, n_samples), dtype=torch.float32, device=programs.device)
+    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[0] < B or wave.shape[1] < n_samples or wave.stride(1) != 1 or wave.device != programs.device:
+        raise A2SError("render_notes: the output needs B rows of at least n_samples float32 with unit stride on the programs' device")
+    if B == 0:
+        return wave                           # (an empty tensor has no data pointer to pass: nothing to launch, as a2s_render_notes with B = 0)
+    check(lib().a2s_render_notes(stream(), _p(programs), programs.shape[1], int(n_samples), _p(wave), C.c_long(wave.stride(0)), B), "a2s_render_notes")
+    return wave
+
+
+def render_launches():
+    """Synthesiser launches of this process (a2s_render_launches)."""
+    return int(lib().a2s_render_launches())
+
+
 def align_buffers(R, max_steps, T, device):
     """The outputs of one alignment call (a2s_align_args) over R rows: -> (AlignArgs, dict of the tensors it points to), pre-filled with what a step
     that never runs keeps: peak -1, weight 0, centroid -1."""

@@ -29,14 +29,48 @@ _VQT = {}
 
 def _features(batch, device):
     """Online front-end: when the loader yields raw 16 kHz waveforms (B, N) instead of cached spectrograms
-    (B, 1, T, F), the VQT runs on the GPU in front of the model (piano_a2s_amd.vqt; the reference caches librosa features offline)."""
+    (B, 1, T, F), the VQT runs on the GPU in front of the model (piano_a2s_amd.vqt; the reference caches librosa features offline).  When it yields
+    render programs (B, 1 + E, 8) int32, the waveforms are synthesised on the GPU first (piano_a2s_amd.render)."""
+    rendered = torch.is_tensor(batch[0]) and batch[0].dim() == 3 and batch[0].dtype == torch.int32
+    if rendered:
+        # rendered synthetic corpus (datasets.syn.RenderedClips): render programs (B, 1 + E, 8) -> waveforms, synthesised on the GPU; the clip length
+        # is taken from the headers while the programs are still on the host (nothing is read back from the device)
+        from piano_a2s_amd.render import program_samples, render
+        n_samples = program_samples(batch[0])
     batch = _to_device(batch, device)
+    if rendered:
+        batch[0] = render(batch[0], n_samples)
     if torch.is_tensor(batch[0]) and batch[0].dim() == 2:
         from piano_a2s_amd.vqt import VQT
         if device not in _VQT:
             _VQT[device] = VQT(torch.device(device))
         batch[0] = _VQT[device](batch[0])
     return batch
+
+
+def synthetic_sets(hparams, n_syn, test_offset=20_000, online_vqt=True):
+    """--synthetic_clips=N: the (train, valid, test) sets of N / N // 8 / N // 8 seeded clips at disjoint seed offsets.  --synthetic_scores=rendered
+    (an optional override, like --synthetic_frames): clips whose audio is the GPU-synthesised sound of their score (datasets.syn.RenderedClips);
+    without it the random clips (--online_vqt, where the caller honours it: with random waveforms) as before.  Rendered clips take neither
+    --synthetic_lengths (their bars are as long as the drawn score; --max_length caps them) nor --online_vqt (they always go through the GPU VQT): both
+    are ignored with them.  test_offset None: the test set is the
+    validation set (finetune.py)."""
+    from datasets.syn import RenderedClips, SyntheticClips, SyntheticWaveClips
+    cfg = hparams["transcription"].cfg
+    syn = dict(frames=int(hparams.get("synthetic_frames") or hparams["max_frame_num"]))
+    scores = str(hparams.get("synthetic_scores") or "random").strip().lower()
+    if scores == "rendered":
+        cls = RenderedClips
+    elif scores == "random":
+        cls = SyntheticWaveClips if online_vqt and hparams.get("online_vqt") else SyntheticClips
+        if hparams.get("synthetic_lengths"):
+            syn.update(upper_range=tuple(hparams["synthetic_lengths"][0]), lower_range=tuple(hparams["synthetic_lengths"][1]))
+    else:
+        raise ValueError(f"--synthetic_scores must be 'random' or 'rendered' (got {scores!r})")
+    train_set = cls(cfg, n_syn, seed=hparams["seed"], **syn)
+    valid_set = cls(cfg, max(1, n_syn // 8), seed=hparams["seed"] + 10_000, **syn)
+    test_set = valid_set if test_offset is None else cls(cfg, max(1, n_syn // 8), seed=hparams["seed"] + test_offset, **syn)
+    return train_set, valid_set, test_set
 
 
 class ASR(sb.Brain):

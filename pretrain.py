@@ -3,11 +3,12 @@
 ``torchrun --nproc_per_node=N pretrain.py hparams/pretrain.yaml ...`` (one process per GPU, RCCL).
 
 Same command line, yaml keys and recipe hooks as the reference's pretrain.py (:251-305); the recipe class lives in
-piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic clips instead of a rendered corpus.  Optional overrides of the
+piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic clips instead of a rendered corpus; with
+``--synthetic_scores=rendered`` their audio is the sound of their (well-formed) score, synthesised on the GPU.  Optional overrides of the
 VALID / TEST decoder: ``--constrained_decoding=true`` (kern grammar), ``--beam_size=K [--beam_length_penalty=A]`` (beam search, K in 1 .. 4)."""
 import sys
 
-from piano_a2s_amd.recipe import ASR, sb, write_run_summary
+from piano_a2s_amd.recipe import ASR, sb, synthetic_sets, write_run_summary
 
 try:
     from hyperpyyaml import load_hyperpyyaml
@@ -24,16 +25,7 @@ def main(argv):
 
     n_syn = int(hparams.get("synthetic_clips", 0) or 0)
     if n_syn:
-        from datasets.syn import SyntheticClips, SyntheticWaveClips
-        if hparams.get("online_vqt"):                      # raw waveforms -> GPU VQT -> model (instead of cached spectrograms)
-            SyntheticClips = SyntheticWaveClips
-        cfg = hparams["transcription"].cfg
-        syn = dict(frames=int(hparams.get("synthetic_frames") or hparams["max_frame_num"]))
-        if hparams.get("synthetic_lengths"):
-            syn.update(upper_range=tuple(hparams["synthetic_lengths"][0]), lower_range=tuple(hparams["synthetic_lengths"][1]))
-        train_set = SyntheticClips(cfg, n_syn, seed=hparams["seed"], **syn)
-        valid_set = SyntheticClips(cfg, max(1, n_syn // 8), seed=hparams["seed"] + 10_000, **syn)
-        test_set = SyntheticClips(cfg, max(1, n_syn // 8), seed=hparams["seed"] + 20_000, **syn)
+        train_set, valid_set, test_set = synthetic_sets(hparams, n_syn)
     else:
         from datasets.syn import TestDataset, TrainDataset
         test_versions = range(4) if hparams["midi_syn"] == "epr" else [0]      # score + 3 composers' renderings for "epr"

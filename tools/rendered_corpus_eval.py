@@ -1,0 +1,157 @@
+"""Is the rendered synthetic corpus learnable, and what do the decoders make of it?  (needs the GPU.)
+
+    python tools/rendered_corpus_eval.py --model small|full --steps N [--batch B] [--frames F] [--eval_clips M] [--out profiles/rendered_corpus.json]
+
+1. trains on rendered clips (datasets.syn.RenderedClips, fresh clips every step) for N fused optimizer steps -- once with every clip's own audio and
+   once, as the control, from the same initial weights with the audio permuted among the clips of each batch (uninformative audio);
+2. on held-out rendered clips reports per-staff WER and key / time-signature F1 of greedy, grammar-constrained and beam (K = 2, 4) decoding with the
+   share of well-formed bars, for both models;
+3. reports the mean absolute difference between the forced-alignment centroids (teacher-forced forward over the true score) and the true onsets;
+4. writes the JSON.
+No threshold is applied to anything: the file records what the run shows."""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _batches(ds, batch, workers):
+    from torch.utils.data import DataLoader
+    return DataLoader(ds, batch_size=batch, shuffle=False, num_workers=workers, drop_last=True)
+
+
+def _features(batch, dev, front, permute=False):
+    from piano_a2s_amd.render import render
+    x = front(render(batch[0].to(dev)))
+    if permute:
+        x = torch.roll(x, 1, dims=0)                                       # clip b hears clip b - 1
+    return [x] + [t.to(dev) for t in batch[1:7]]
+
+
+def _train(model, ds, args, dev, front, permute):
+    from piano_a2s_amd import train
+    model.train()
+    step = train.TrainStep(model)
+    rng = random.Random(args.seed)
+    curve, t0 = [], time.perf_counter()
+    for k, batch in enumerate(_batches(ds, args.batch, args.workers)):
+        terms = step(_features(batch, dev, front, permute), args.teacher_forcing, rng=rng)
+        if k % args.log_every == 0 or k == args.steps - 1:
+            t = terms[:, 0].tolist()
+            curve.append({"step": k, "time_sig": t[0], "key": t[1], "upper": t[2], "lower": t[3], "loss": sum(t)})
+            print(f"{'control' if permute else 'matched'} step {k}: loss {sum(t):.4f} (ts {t[0]:.3f} key {t[1]:.3f} up {t[2]:.3f} lo {t[3]:.3f})", flush=True)
+    torch.cuda.synchronize()
+    return curve, time.perf_counter() - t0
+
+
+def _unpad_rows(ids):
+    from piano_a2s_amd import metrics
+    return [metrics.unpad(r).tolist() for r in ids]
+
+
+def _decode(model, ds, args, dev, front, permute, constrained, K):
+    from data_processing.humdrum import LabelsMultiple
+    from piano_a2s_amd import kern_grammar, metrics
+    inv = LabelsMultiple(extended=True).labels_map_inv
+    model.eval()
+    model.constrained_decoding, model.beam_size, model.alignment = constrained, K, False
+    pred = {k: {} for k in ("up", "lo", "key", "ts")}
+    target = {k: {} for k in ("up", "lo", "key", "ts")}
+    with torch.no_grad():
+        for batch in _batches(ds, args.eval_batch, 0):
+            f = _features(batch, dev, front, permute)
+            ts_o, key_o, up_o, lo_o = model(f[0], inference=True)
+            if constrained or K >= 2:
+                up_ids, lo_ids = model.last_decoded["up"][0].cpu().numpy(), model.last_decoded["lo"][0].cpu().numpy()
+            else:
+                up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
+            for b, name in enumerate(batch[7]):
+                pred["up"][name], target["up"][name] = _unpad_rows(up_ids[b]), _unpad_rows(batch[3][b].numpy())
+                pred["lo"][name], target["lo"][name] = _unpad_rows(lo_ids[b]), _unpad_rows(batch[5][b].numpy())
+                pred["key"][name], target["key"][name] = key_o[b].argmax(-1).cpu().tolist(), batch[2][b].tolist()
+                pred["ts"][name], target["ts"][name] = ts_o[b].argmax(-1).cpu().tolist(), batch[1][b].tolist()
+    model.constrained_decoding, model.beam_size = False, 1
+    return {"WER_upper": metrics.corpus_wer(pred["up"], target["up"], inv)[0], "WER_lower": metrics.corpus_wer(pred["lo"], target["lo"], inv)[0],
+            "key_f1": metrics.corpus_f1(pred["key"], target["key"])[0], "time_f1": metrics.corpus_f1(pred["ts"], target["ts"])[0],
+            "legal_share_upper": kern_grammar.legal_share(pred["up"]), "legal_share_lower": kern_grammar.legal_share(pred["lo"])}
+
+
+def _alignment_error(model, ds, args, dev, front):
+    """Forced alignment of the true score (teacher-forced forward in evaluation mode) against the true onsets: mean |centroid - onset| in seconds."""
+    model.eval()
+    model.alignment = True
+    err = {"bar": [], "upper": [], "lower": []}
+    idx = 0
+    with torch.no_grad():
+        for batch in _batches(ds, args.eval_batch, 0):
+            f = _features(batch, dev, front)
+            model(f[0], inference=False, ground_truth=f[1:7], teacher_forcing_ratio=1.0)
+            al = {k: v["centroid"].cpu().numpy() for k, v in model.last_alignment.items()}
+            for b in range(len(batch[7])):
+                on = ds.onsets(idx)
+                idx += 1
+                err["bar"] += [abs(al["bar"][b, i] / 100.0 - t) for i, t in enumerate(on["bar"]) if al["bar"][b, i] >= 0]
+                for key, k in (("upper", "up"), ("lower", "lo")):
+                    err[key] += [abs(al[k][b, i, j] / 100.0 - t) for i, row in enumerate(on[key]) for j, t in enumerate(row) if al[k][b, i, j] >= 0]
+    model.alignment = False
+    return {k: (float(np.mean(v)) if v else None) for k, v in err.items()} | {"tokens": len(err["upper"]) + len(err["lower"])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("small", "full"), default="small")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--eval_batch", type=int, default=16)
+    ap.add_argument("--eval_clips", type=int, default=32)
+    ap.add_argument("--frames", type=int, default=1201)
+    ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--teacher_forcing", type=float, default=1.0)
+    ap.add_argument("--log_every", type=int, default=10)
+    ap.add_argument("--no_control", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import models
+    from datasets.syn import RenderedClips
+    from piano_a2s_amd import hip, spec
+    from piano_a2s_amd.vqt import VQT
+    dev = torch.device("cuda:0")
+    cfg = spec.default_cfg() if args.model == "full" else spec.default_cfg(hidden_size=64, conv_feature_size=64)
+    front = VQT(dev)
+    train_set = RenderedClips(cfg, args.steps * args.batch, seed=args.seed, frames=args.frames)
+    held_out = RenderedClips(cfg, args.eval_clips, seed=args.seed + 10_000_000, frames=args.frames)
+    res = {"model": args.model, "cfg": {k: cfg[k] for k in ("hidden_size", "conv_feature_size", "max_length", "max_bars")}, "steps": args.steps,
+           "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "runs": {}}
+    torch.manual_seed(args.seed)
+    init = {k: v.clone() for k, v in models.ScoreTranscription(**cfg).state_dict().items()}
+    for name, permute in (("matched", False),) + (() if args.no_control else (("control_permuted_audio", True),)):
+        model = models.ScoreTranscription(**cfg)
+        model.load_state_dict(init)
+        model = model.to(dev)
+        curve, seconds = _train(model, train_set, args, dev, front, permute)
+        run = {"loss_curve": curve, "train_seconds": seconds, "decoding": {}}
+        for tag, constrained, K in (("greedy", False, 1), ("constrained", True, 1), ("beam2", False, 2), ("beam4", False, 4)):
+            run["decoding"][tag] = _decode(model, held_out, args, dev, front, permute, constrained, K)
+            print(name, tag, json.dumps(run["decoding"][tag]), flush=True)
+        if not permute:
+            run["forced_alignment_abs_error_s"] = _alignment_error(model, held_out, args, dev, front)
+            print(name, "alignment", json.dumps(run["forced_alignment_abs_error_s"]), flush=True)
+        res["runs"][name] = run
+    res["render_launches"] = hip.render_launches()
+    print(json.dumps({k: v for k, v in res.items() if k != "runs"}))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
