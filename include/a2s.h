@@ -88,6 +88,19 @@ int a2s_linear_wgrad(void* stream, int M, int N, int K, const float* dz, long ld
                      const float* shift, int period, const float* dz_absmax, const float* y_absmax, float* workspace, size_t workspace_bytes);
 size_t a2s_linear_wgrad_ws_bytes(int M, int K);
 int a2s_linear_wgrad_eligible(int M, int N, int K, int period);
+/* The same kernel for any product over a tall reduction index (M = B*T rows; the encoder GRU's weight gradients, the attention key products):
+ *   transposed = 0:  G[n][k] += sum_m P[m][n] A[m][k]   (G: Np x K, leading dimension ldg)
+ *   transposed = 1:  G[k][n] += sum_m P[m][n] A[m][k]   (G: K x Np)
+ *   bias (may be NULL):  bias[k] += sum_m A[m][k]
+ * P (M x Np, leading dimension ldp, Np % 256 == 0) is packed once into fp16 term planes, A (M x K, leading dimension lda, K % 128 == 0) is streamed
+ * from memory exactly once when Np == 256; a column offset into a wider tensor is part of the pointer.  Every base address 16-byte aligned, lda % 4 == 0,
+ * ldg % 4 == 0, M >= 64.  p_absmax / a_absmax: device scalars bounding |P| / |A|.  workspace: a2s_tallk_wgrad_ws_bytes(M, Np, K) bytes.
+ * Deterministic: fixed-order reduction over the row ranges, for G and for bias.  a2s_tallk_wgrad_eligible says whether a shape qualifies and the
+ * switch "tallk_wgrad" (a2s_debug_set) is on; otherwise call a2s_gemm_f32_affine_scaled and a2s_col_sum. */
+int a2s_tallk_wgrad(void* stream, int M, int Np, int K, const float* P, long ldp, const float* A, long lda, float* G, long ldg, int transposed, float* bias,
+                    const float* p_absmax, const float* a_absmax, float* workspace, size_t workspace_bytes);
+size_t a2s_tallk_wgrad_ws_bytes(int M, int Np, int K);
+int a2s_tallk_wgrad_eligible(int M, int Np, int K, long ldp, long lda, long ldg, int transposed);
 size_t a2s_linear_dgrad_ws_bytes(int N, int K);
 int a2s_linear_dgrad_blocks(int M);
 int a2s_linear_dgrad_eligible(int M, int N, int K, int period);
@@ -441,6 +454,13 @@ int a2s_note_decoder_bwd_pair(void* stream_upper, void* stream_lower, const a2s_
 int a2s_gru_seq_bwd(void* stream, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
                     long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
                     float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes);
+/* ... which also hands out the operand ranges of the deferred weight-gradient products: ranges_out (DEVICE, 2 floats) <- max |dgi_all|,
+ * max |dgh_shift|, bit-equal to a2s_absmax of the two tensors, when the call ran as one persistent launch; *ranges_valid (HOST) <- 1 then, 0
+ * otherwise (the launch-per-step kernels do not produce them: measure the tensors with a2s_absmax). */
+int a2s_gru_seq_bwd_ranged(void* stream, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
+                           long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
+                           float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes,
+                           float* ranges_out, int* ranges_valid);
 /* BPTT of the packed staff-embedding bi-GRU; grads: DEVICE array of 8 pointers (same order as gru_w) */
 int a2s_staff_emb_bwd(void* stream, const float* note_emb, const float* const* gru_w, float* const* grads, float* note_emb_grad,
                       const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,

@@ -60,6 +60,14 @@ int a2s_linear_wgrad(void* stream, int M, int N, int K, const float* dz, long ld
 }
 size_t a2s_linear_wgrad_ws_bytes(int M, int K) { return a2s_linear_wgrad_ws_bytes_impl(M, K); }
 int a2s_linear_wgrad_eligible(int M, int N, int K, int period) { return a2s_linear_wgrad_ok(M, N, K, 256, 4, 4, period, nullptr, nullptr, nullptr) ? 1 : 0; }
+int a2s_tallk_wgrad(void* stream, int M, int Np, int K, const float* P, long ldp, const float* A, long lda, float* G, long ldg, int transposed, float* bias,
+                    const float* p_absmax, const float* a_absmax, float* workspace, size_t workspace_bytes) {
+    return a2s_tallk_wgrad_impl(ST, M, Np, K, P, ldp, A, lda, G, ldg, transposed, bias, p_absmax, a_absmax, workspace, workspace_bytes);
+}
+size_t a2s_tallk_wgrad_ws_bytes(int M, int Np, int K) { return a2s_tallk_wgrad_ws_bytes_impl(M, Np, K); }
+int a2s_tallk_wgrad_eligible(int M, int Np, int K, long ldp, long lda, long ldg, int transposed) {
+    return a2s_tallk_wgrad_ok(M, Np, K, ldp, lda, ldg, transposed, nullptr, nullptr, nullptr, nullptr) ? 1 : 0;
+}
 int a2s_linear_fwd_eligible(int M, int N, int K, int period) { return a2s_linear_fwd_ok(M, N, K, 4, 4, period, nullptr, nullptr, nullptr) ? 1 : 0; }
 int a2s_linear_dgrad_blocks(int M) { return a2s_linear_dgrad_blocks_impl(M); }
 int a2s_linear_dgrad_eligible(int M, int N, int K, int period) {
@@ -80,6 +88,8 @@ int a2s_debug_set(const char* key, int value) {
     const int id = a2s_switch_find(key);
     if (id >= 0) { a2s_switch_store(id, value); return A2S_OK; }
     if (!strcmp(key, "attn_deferred_fast")) { a2s_attn_deferred_fast = value ? 1 : 0; return A2S_OK; }
+    if (!strcmp(key, "tallk_wgrad")) { a2s_tallk_wgrad_on = value ? 1 : 0; return A2S_OK; }
+    if (!strcmp(key, "tallk_wgrad_max_splits")) { a2s_tallk_wgrad_max_splits = value > 0 ? value : 0; return A2S_OK; }
     if (!strcmp(key, "gemm_tile")) { a2s_gemm_debug_tile_impl(value); return A2S_OK; }          // write-only
     snprintf(a2s_err_msg, sizeof(a2s_err_msg), "a2s_debug_set: unknown key %s", key);
     return A2S_ERR_ARG;
@@ -100,6 +110,9 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "attn_pair_launches")) return (int)a2s_attn_pair_launches();
     if (!strcmp(key, "attn_pair_bwd_launches")) return (int)a2s_attn_pair_bwd_launches();
     if (!strcmp(key, "attn_deferred_fast")) return a2s_attn_deferred_fast;
+    if (!strcmp(key, "tallk_wgrad")) return a2s_tallk_wgrad_on;
+    if (!strcmp(key, "tallk_wgrad_max_splits")) return a2s_tallk_wgrad_max_splits;
+    if (!strcmp(key, "tallk_wgrad_launches")) return (int)a2s_tallk_wgrad_launches();
     if (!strcmp(key, "attn_dk_ahead_launches")) return (int)a2s_attn_dk_ahead_launches();
     if (!strcmp(key, "attn_denc_launches")) return (int)a2s_attn_denc_launches();
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
@@ -305,7 +318,15 @@ int a2s_gru_seq_bwd(void* stream, const float* dout, long do_bstride, long do_ts
                     const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first,
                     float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes) {
     return a2s_gru_seq_bwd_impl(ST, dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, w_hh, dhn, dgi_all, dgh_shift,
-                                dgh_first, dhbuf, dgh_tmp, B, T, H, reverse, workspace, workspace_bytes);
+                                dgh_first, dhbuf, dgh_tmp, B, T, H, reverse, workspace, workspace_bytes, nullptr, nullptr);
+}
+int a2s_gru_seq_bwd_ranged(void* stream, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
+                           const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first,
+                           float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes,
+                           float* ranges_out, int* ranges_valid) {
+    if (!ranges_out || !ranges_valid) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "gru_seq_bwd_ranged: null ranges_out / ranges_valid"); return A2S_ERR_ARG; }
+    return a2s_gru_seq_bwd_impl(ST, dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, w_hh, dhn, dgi_all, dgh_shift,
+                                dgh_first, dhbuf, dgh_tmp, B, T, H, reverse, workspace, workspace_bytes, ranges_out, ranges_valid);
 }
 int a2s_staff_emb_bwd(void* stream, const float* note_emb, const float* const* gru_w, float* const* grads, float* note_emb_grad,
                       const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,

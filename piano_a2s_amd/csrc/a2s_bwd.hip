@@ -640,6 +640,8 @@ int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
 //   dgi_all (B,T,3H) <- per-step input-projection gradients (caller: dW_ih, db_ih, dX via GEMMs)
 //   dgh_shift (B,T,3H) <- dgh of the step whose h_prev is out[:,t]  (row (b,t) pairs with out[b,t]: dW_hh = dgh_shift^T out)
 //   dgh_first (B,3H)   <- dgh of the first processed step (h_prev = 0): only contributes to db_hh
+//   ranges_out (2 floats, may be null) <- max |dgi_all|, max |dgh_shift| where the persistent launch ran (it holds every element it writes in a
+//   register); *ranges_valid says whether it did -- the launch-per-step kernels do not produce them, and the caller then measures the tensors.
 
 // out[c][r] = in[r][c]  (rows x cols -> cols x rows); small parameter matrices only
 __global__ void transpose_f32(const float* __restrict__ in, float* __restrict__ out, int rows, int cols) {
@@ -651,8 +653,10 @@ __global__ void transpose_f32(const float* __restrict__ in, float* __restrict__ 
 
 int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
                          long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
-                         float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes) {
+                         float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes,
+                         float* ranges_out, int* ranges_valid) {
     A2S_REQUIRE(dout && out && gates && w_hh && dgi_all && dgh_shift && dgh_first && dhbuf && dgh_tmp, "gru_seq_bwd: null tensor");
+    if (ranges_valid) *ranges_valid = 0;
     hipError_t e;
     if (dhn) e = hipMemcpyAsync(dhbuf, dhn, sizeof(float) * B * H, hipMemcpyDeviceToDevice, st);
     else e = hipMemsetAsync(dhbuf, 0, sizeof(float) * B * H, st);
@@ -667,9 +671,12 @@ int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, lon
         A2S_CHECK_LAUNCH("transpose_f32");
     }
     // one persistent launch for all T steps (a2s_persist.hip); its granule buffers live behind W_hh^T in the workspace
-    if (fused && a2s_gru_seq_bwd_persist_ok(B, T, H, ws, ws_bytes, sizeof(float) * 3 * (size_t)H * H))
-        return a2s_gru_seq_bwd_persist_impl(st, dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, ws, dhn, dgi_all, dgh_shift, dgh_first, B, T, H,
-                                            reverse, ws, sizeof(float) * 3 * (size_t)H * H, ws_bytes);
+    if (fused && a2s_gru_seq_bwd_persist_ok(B, T, H, ws, ws_bytes, sizeof(float) * 3 * (size_t)H * H)) {
+        const int rc = a2s_gru_seq_bwd_persist_impl(st, dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, ws, dhn, dgi_all, dgh_shift, dgh_first,
+                                                    B, T, H, reverse, ws, sizeof(float) * 3 * (size_t)H * H, ws_bytes, ranges_out);
+        if (rc == A2S_OK && ranges_out && ranges_valid) *ranges_valid = 1;
+        return rc;
+    }
     if (fused && ws_bytes >= sizeof(float) * (3 * (size_t)H * H + 3 * (size_t)B * H) && (3 * H * H) % 4 == 0) {
         // ONE launch per step: the carry product of step s with the gate backward of step s-1 on its accumulators
         // (gru_bptt_step_fused); the two dgh scratch buffers alternate (this launch reads one as its A operand and writes the other)

@@ -46,6 +46,13 @@ size_t a2s_linear_wgrad_ws_bytes_impl(int M, int K);
 bool a2s_linear_wgrad_ok(int M, int N, int K, long ldz, long lda, long ldg, int period, const void* dz, const void* A, const void* G);
 int a2s_linear_wgrad_impl(hipStream_t st, int M, int N, int K, const float* dz, long ldz, const float* A, long lda, float* G, long ldg, const float* a_scale,
     const float* a_shift, int period, const float* dz_absmax, const float* a_absmax, float* ws, size_t ws_bytes);
+extern int a2s_tallk_wgrad_on;                      // the key "tallk_wgrad" beside the switch list (a2s_switches.h)
+extern int a2s_tallk_wgrad_max_splits;              // "tallk_wgrad_max_splits" (test aid)
+long a2s_tallk_wgrad_launches(void);
+size_t a2s_tallk_wgrad_ws_bytes_impl(int M, int Np, int K);
+bool a2s_tallk_wgrad_ok(int M, int Np, int K, long ldp, long lda, long ldg, int transposed, const void* P, const void* A, const void* G, const void* bias);
+int a2s_tallk_wgrad_impl(hipStream_t st, int M, int Np, int K, const float* P, long ldp, const float* A, long lda, float* G, long ldg, int transposed,
+    float* bias, const float* p_absmax, const float* a_absmax, float* ws, size_t ws_bytes);
 
 // ---- a2s_conv.hip
 int a2s_act_bound_impl(hipStream_t st, const float* scale, const float* shift, const float* absmax, int C, float* out);
@@ -172,7 +179,8 @@ int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
     const int* pair_rank, const int* pair_n_active);
 int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
     long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
-    float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
+    float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes,
+    float* ranges_out, int* ranges_valid);
 int a2s_staff_emb_bwd_impl(hipStream_t st, const float* note_emb, const float* const* w, float* const* grads_dev, float* note_emb_grad,
     const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,
     const float* dout, long lddo, int col0, const float* hsave, int R, int maxlen, int E, int S);
@@ -252,7 +260,7 @@ int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bs
 bool a2s_gru_seq_bwd_persist_ok(int B, int T, int H, float* ws, size_t ws_bytes, size_t ws_used);
 int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
     const float* gates, const float* w_hh_t, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first, int B, int T,
-    int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes);
+    int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes, float* ranges_out);
 
 // ---- a2s_dec_persist.hip
 int a2s_dec_persist_launches(void);

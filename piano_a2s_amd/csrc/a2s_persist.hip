@@ -250,7 +250,8 @@ struct GruPersistBwd {
     const float* dhn;                                   // (B, H) or null
     float* dgi_all; float* dgh_shift; float* dgh_first; // (B, T, 3H), (B, T, 3H), (B, 3H)
     u64* gx;                                            // 2 x RB tiles of 16 x 3H granules (granule_index order), zeroed before the launch
-    unsigned* abort_flag;
+    unsigned* abort_flag;                               // header, zeroed before the launch: [0] abort code, [1] diagnostic count, [2] / [3] range words:
+                                                        // the bit patterns of max |dgi_all| and max |dgh_shift| over what this launch wrote (rows < B)
     unsigned* xcc;                                      // RB x 16 words, zeroed before the launch
     int B, T, reverse, nrb;
     unsigned* latch; unsigned dbg;
@@ -278,6 +279,7 @@ __global__ __launch_bounds__(256, 2) void gru_seq_bwd_persist(GruPersistBwd a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) carry[r] = (wave == 0 && a.dhn) ? a.dhn[(long)min(row0 + lk * 4 + r, R - 1) * H + j] : 0.f;
     bool dead = false;
+    float mgi = 0.f, mgh = 0.f;                          // wave 0: running max |.| of what it writes to dgi_all / dgh_shift (the deferred products' operand ranges)
     for (int s = T - 1; s >= 0; --s) {
         const int t = a.reverse ? T - 1 - s : s;
         const int tp = a.reverse ? t + 1 : t - 1;        // time index whose output was h_prev of this step (invalid when s == 0)
@@ -347,11 +349,19 @@ __global__ __launch_bounds__(256, 2) void gru_seq_bwd_persist(GruPersistBwd a) {
                 if (row < R) {
                     float* gi = a.dgi_all + ((long)row * T + t) * 3 * H;
                     gi[j] = dr; gi[H + j] = dz; gi[2 * H + j] = dn;
+                    const float mrz = fmaxf(fabsf(dr), fabsf(dz));
+                    mgi = fmaxf(mgi, fmaxf(mrz, fabsf(dn)));
+                    if (s > 0) mgh = fmaxf(mgh, fmaxf(mrz, fabsf(dnr)));
                     if (s > 0) { float* g2 = a.dgh_shift + ((long)row * T + tp) * 3 * H; g2[j] = dr; g2[H + j] = dz; g2[2 * H + j] = dnr; }
                     else { float* g1 = a.dgh_first + (long)row * 3 * H; g1[j] = dr; g1[H + j] = dz; g1[2 * H + j] = dnr; }
                 }
             }
         }
+    }
+    if (wave == 0) {                                     // non-negative floats order like their bit patterns
+        const float m1 = wave_max(mgi), m2 = wave_max(mgh);
+        if (lane == 0 && m1 > 0.f) atomicMax(a.abort_flag + 2, __float_as_uint(m1));
+        if (lane == 0 && m2 > 0.f) atomicMax(a.abort_flag + 3, __float_as_uint(m2));
     }
     if (wave == 0 && (dead || aborted(a.abort_flag))) {   // poison what the deferred weight-gradient products read
 #pragma unroll
@@ -437,7 +447,7 @@ bool a2s_gru_seq_bwd_persist_ok(int B, int T, int H, float* ws, size_t ws_bytes,
 // ws_off: bytes at the start of the workspace the caller keeps (W_hh^T)
 int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
                                  const float* gates, const float* w_hh_t, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first, int B, int T,
-                                 int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes) {
+                                 int H, int reverse, float* ws, size_t ws_off, size_t ws_bytes, float* ranges_out) {
     const size_t need = a2s_gru_persist_ws_bytes(B, H, 1);
     A2S_REQUIRE(need && ws_bytes >= ws_off + need, "gru_seq_bwd_persist: workspace too small");
     char* base = reinterpret_cast<char*>(ws) + ws_off;
@@ -450,5 +460,9 @@ int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstr
                     g_abort_latch, a2s_persist_dbg()};
     hipLaunchKernelGGL(gru_seq_bwd_persist<256>, dim3((H / 16) * nrb), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_seq_bwd_persist");
+    if (ranges_out) {        // out of the header: the next launch on this workspace zeroes it, while the deferred products may still be waiting to run
+        e = hipMemcpyAsync(ranges_out, base + 2 * sizeof(unsigned), 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "gru_seq_bwd_persist range words: %s", hipGetErrorString(e));
+    }
     return A2S_OK;
 }

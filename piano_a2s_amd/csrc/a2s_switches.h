@@ -68,9 +68,12 @@
     X(persist_inject_abort, 0, ONOFF, 0)
 // Not in the list, because they are not stored integers (a2s_debug_set / a2s_debug_get, a2s_api.hip): "gemm_tile" is write-only
 // (a2s_gemm_debug_tile); the "*_launches" counters and "device_cus" / "device_xccs" are read-only.
-// One on/off key is kept beside the list, because the list is a recorded contract (tests/test_switches_cpu.py spells its keys out):
+// Two on/off keys are kept beside the list, because the list is a recorded contract (tests/test_switches_cpu.py spells its keys out):
 // "attn_deferred_fast" (default 1; a2s_attn_deferred_fast, a2s_bwd.hip) -- the deferred attention gradients on attn_dk_accum_ahead and
 // attn_denc_accum; 0 = attn_dk_accum and the batched GEMM.  No environment variable.
+// "tallk_wgrad" (default 1; a2s_tallk_wgrad_on, a2s_linear.hip) -- the encoder GRU's weight gradients and the attention key products on
+// a2s_tallk_wgrad (a2s_tallk_wgrad_eligible answers 0 while it is off); 0 = the generic split-K GEMM and the column-sum passes.  No environment variable.
+// Its test aid "tallk_wgrad_max_splits" (default 0 = no cap) bounds the kernel's split over the rows, so that a small shape runs long row ranges.
 
 enum a2s_switch {
 #define X(key, def, rule, env) A2S_SW_##key,

@@ -541,10 +541,12 @@ class Backward:
         enc_amax = hip.absmax(enc) if self.two_term else None
         for p, dKp in dK.items():
             Wn = p + ".attn.attn.weight"
-            sk = L.a2s_gemm_pick_splitk(H, H2, B * T, 1)
             dk_amax = hip.absmax(dKp) if self.two_term else None
-            hip.gemm(dKp, 1, H, enc2d, H2, 1, G[Wn], 4 * H, H, H2, B * T, beta=1.0, splitk=sk, c_off=H2,
-                     two_term=(dk_amax, enc_amax) if self.two_term else None)
+            # (tall-K kernel: dK packed, enc streamed once, the result into columns 2H.. of the 4H-wide matrix; csrc/a2s_linear.hip)
+            if not hip.tallk_wgrad(dKp, 0, H, enc2d, 0, H2, G[Wn], H2, 4 * H, B * T, H, H2, dk_amax, enc_amax):
+                sk = L.a2s_gemm_pick_splitk(H, H2, B * T, 1)
+                hip.gemm(dKp, 1, H, enc2d, H2, 1, G[Wn], 4 * H, H, H2, B * T, beta=1.0, splitk=sk, c_off=H2,
+                         two_term=(dk_amax, enc_amax) if self.two_term else None)
             hip.gemm(dKp, H, 1, S[Wn], 4 * H, 1, dEnc, H2, B * T, H2, H, beta=1.0, b_off=H2,
                      two_term=(dk_amax, hip.absmax(S[Wn])) if self.two_term else None)
         if late_join is not None:
@@ -666,11 +668,20 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
             dgi = torch.empty((B, T, 3 * H), device=dev)
             dghs = torch.empty((B, T, 3 * H), device=dev)
             dgh_first, dhbuf, dgh_tmp = torch.empty((B, 3 * H), device=dev), torch.empty((2, B, H), device=dev), torch.empty((B, 3 * H), device=dev)
-            hip.check(L.a2s_gru_seq_bwd(hip.stream(), _ptr(dout, d * H), C.c_long(T * 2 * H), C.c_long(2 * H), _ptr(out, d * H), C.c_long(T * 2 * H),
-                                        C.c_long(2 * H), hip._p(ls["dirs"][d]["gates"]), hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]),
-                                        hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]),
-                                        C.c_size_t(gws[d].numel() * 4)), "a2s_gru_seq_bwd")
-            return (dgi, dghs, dgh_first, dhbuf, dgh_tmp)
+            # max |dgi|, max |dghs| (the operand ranges of dX and of the deferred weight gradients) come out of the persistent BPTT launch, which
+            # holds every element in a register; the launch-per-step kernels do not produce them (valid = 0): the tensors are measured then
+            ranges, valid = torch.empty(2, device=dev), C.c_int(0)
+            if two_term and L.a2s_debug_get(b"tallk_wgrad") > 0:
+                hip.check(L.a2s_gru_seq_bwd_ranged(hip.stream(), _ptr(dout, d * H), C.c_long(T * 2 * H), C.c_long(2 * H), _ptr(out, d * H), C.c_long(T * 2 * H),
+                                                   C.c_long(2 * H), hip._p(ls["dirs"][d]["gates"]), hip._p(S[f"encoder.gru.weight_hh_{sfx}"]),
+                                                   hip._p(dhn[2 * layer + d]), hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d,
+                                                   hip._p(gws[d]), C.c_size_t(gws[d].numel() * 4), hip._p(ranges), C.byref(valid)), "a2s_gru_seq_bwd_ranged")
+            else:
+                hip.check(L.a2s_gru_seq_bwd(hip.stream(), _ptr(dout, d * H), C.c_long(T * 2 * H), C.c_long(2 * H), _ptr(out, d * H), C.c_long(T * 2 * H),
+                                            C.c_long(2 * H), hip._p(ls["dirs"][d]["gates"]), hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]),
+                                            hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]),
+                                            C.c_size_t(gws[d].numel() * 4)), "a2s_gru_seq_bwd")
+            return (dgi, dghs, dgh_first, dhbuf, dgh_tmp, ranges if valid.value else None)
 
         res = fork_on_streams(dev, streams, [lambda d=d, sfx=sfx: direction(d, sfx) for d, sfx in enumerate((f"l{layer}", f"l{layer}_reverse"))])()
         dgi_amax = []
@@ -678,7 +689,8 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
         for d, sfx in enumerate((f"l{layer}", f"l{layer}_reverse")):
             dgi2 = res[d][0].view(B * T, 3 * H)
             Wih = S[f"encoder.gru.weight_ih_{sfx}"]
-            tt = (hip.absmax(dgi2), hip.absmax(Wih)) if two_term else None        # measured ranges: the two-term fp16 split
+            ranges = res[d][5]
+            tt = (ranges[0:1] if ranges is not None else hip.absmax(dgi2), hip.absmax(Wih)) if two_term else None        # ranges: the two-term fp16 split
             dgi_amax.append(tt[0] if tt else None)
             if L.a2s_debug_get(b"gemm_bf16x3") > 0:      # k-contiguous weight copy (<= 1.5 MB): both operands on the GEMM's split-operand path
                 hip.gemm(dgi2, 3 * H, 1, Wih.t().contiguous(), 1, 3 * H, dX, I, B * T, I, 3 * H, beta=0.0 if d == 0 else 1.0, two_term=tt)
@@ -690,20 +702,28 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
         ev.record()
         wg.wait_event(ev)
         for d, sfx in enumerate((f"l{layer}", f"l{layer}_reverse")):
-            dgi, dghs, dgh_first = res[d][:3]
+            dgi, dghs, dgh_first, ranges = res[d][0], res[d][1], res[d][2], res[d][5]
             # (everything the weight-gradient stream reads that was allocated on another stream -- the operand-range scalars included: freed by
             # this function's return, their blocks would be handed to the next small allocation of the main stream while these GEMMs still run)
-            for t in (dgi, dghs, dgh_first, dgi_amax[d], in_amax):
+            for t in (dgi, dghs, dgh_first, dgi_amax[d], in_amax, ranges):
                 if t is not None:
                     t.record_stream(wg)
             with torch.cuda.stream(wg):
                 dgi2, dghs2 = dgi.view(B * T, 3 * H), dghs.view(B * T, 3 * H)
-                _linear_bwd(inp, S[f"encoder.gru.weight_ih_{sfx}"], dgi2, G, f"encoder.gru.weight_ih_{sfx}", f"encoder.gru.bias_ih_{sfx}",
-                            dy_amax=dgi_amax[d], x_bound=(in_amax if layer == 0 else hip.one(dev)) if two_term else None)
-                sk = L.a2s_gemm_pick_splitk(3 * H, H, B * T, 1)
-                hip.gemm(dghs2, 1, 3 * H, out, 2 * H, 1, G[f"encoder.gru.weight_hh_{sfx}"], H, 3 * H, H, B * T, beta=1.0, splitk=sk, b_off=d * H,
-                         two_term=(hip.absmax(dghs2), hip.one(dev)) if two_term else None)
-                _colsum(dghs2, 3 * H, G[f"encoder.gru.bias_hh_{sfx}"], B * T, 3 * H)
+                # Tall-K kernel (csrc/a2s_linear.hip): the GRADIENT is the streamed operand -- read once, its column sums (the bias gradient) taken
+                # on the way -- the layer's input / output is packed, and the result lands transposed, in the parameter's (3H, I) layout.
+                x_bound = ((in_amax if layer == 0 else hip.one(dev)) if two_term else None)
+                if not hip.tallk_wgrad(inp, 0, I, dgi2, 0, 3 * H, G[f"encoder.gru.weight_ih_{sfx}"], 0, I, B * T, I, 3 * H, x_bound, dgi_amax[d],
+                                       transposed=True, bias=G[f"encoder.gru.bias_ih_{sfx}"]):
+                    _linear_bwd(inp, S[f"encoder.gru.weight_ih_{sfx}"], dgi2, G, f"encoder.gru.weight_ih_{sfx}", f"encoder.gru.bias_ih_{sfx}",
+                                dy_amax=dgi_amax[d], x_bound=x_bound)
+                dghs_amax = (ranges[1:2] if ranges is not None else hip.absmax(dghs2)) if two_term else None
+                if not hip.tallk_wgrad(out, d * H, 2 * H, dghs2, 0, 3 * H, G[f"encoder.gru.weight_hh_{sfx}"], 0, H, B * T, H, 3 * H,
+                                       hip.one(dev) if two_term else None, dghs_amax, transposed=True, bias=G[f"encoder.gru.bias_hh_{sfx}"]):
+                    sk = L.a2s_gemm_pick_splitk(3 * H, H, B * T, 1)
+                    hip.gemm(dghs2, 1, 3 * H, out, 2 * H, 1, G[f"encoder.gru.weight_hh_{sfx}"], H, 3 * H, H, B * T, beta=1.0, splitk=sk, b_off=d * H,
+                             two_term=(dghs_amax, hip.one(dev)) if two_term else None)
+                    _colsum(dghs2, 3 * H, G[f"encoder.gru.bias_hh_{sfx}"], B * T, 3 * H)
                 _colsum(dgh_first, 3 * H, G[f"encoder.gru.bias_hh_{sfx}"], B, 3 * H)
         dout = dX.view(B, T, I)
     if wait_weight_grads:

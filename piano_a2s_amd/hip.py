@@ -2,6 +2,7 @@
 call fails, this raises -- the product path never silently runs anything else."""
 import ctypes as C
 import os
+import threading
 
 import torch
 
@@ -75,7 +76,7 @@ def lib():
         L = C.CDLL(LIB)
         L.a2s_last_error.restype = C.c_char_p
         L.a2s_launch_count.restype = C.c_longlong
-        for fn in ("a2s_note_step_workspace_floats", "a2s_note_decoder_persist_ws_bytes", "a2s_note_decoder_bwd_persist_ws_bytes", "a2s_linear_dgrad_ws_bytes", "a2s_linear_wgrad_ws_bytes", "a2s_gemm_workspace_bytes", "a2s_bn_bwd_partial_floats", "a2s_conv3x3_wgrad_workspace_bytes", "a2s_attn_workspace_floats", "a2s_attn_workspace_floats_fused",
+        for fn in ("a2s_note_step_workspace_floats", "a2s_note_decoder_persist_ws_bytes", "a2s_note_decoder_bwd_persist_ws_bytes", "a2s_linear_dgrad_ws_bytes", "a2s_linear_wgrad_ws_bytes", "a2s_tallk_wgrad_ws_bytes", "a2s_gemm_workspace_bytes", "a2s_bn_bwd_partial_floats", "a2s_conv3x3_wgrad_workspace_bytes", "a2s_attn_workspace_floats", "a2s_attn_workspace_floats_fused",
                    "a2s_conv3x3_workspace_floats"):
             getattr(L, fn).restype = C.c_size_t
         # the library has read the variables that override a switch's default itself (csrc/a2s_switches.h: the documented fallbacks of INTEGRATION.md)
@@ -86,6 +87,8 @@ def lib():
             L.a2s_edit_distance.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]
         if hasattr(L, "a2s_attn_denc_accum"):        # (absent from builds older than the live-pair dEnc kernel: engine_bwd then keeps the batched GEMM)
             L.a2s_attn_denc_accum.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_int]
+        if hasattr(L, "a2s_tallk_wgrad_eligible"):   # (absent from builds older than the tall-K entry point: A2S_LIB, tools/lib_ab.sh)
+            L.a2s_tallk_wgrad_eligible.argtypes = [C.c_int] * 3 + [C.c_long] * 3 + [C.c_int]
         if arith != "f16x2":
             for key in (b"conv_f16x2", b"wgrad_f16x2", b"gemm_f16x2"):
                 L.a2s_debug_set(key, 0)
@@ -514,6 +517,31 @@ def linear_wgrad(dz, x2d, x_affine, dz_absmax, x_bound, G):
     ws = torch.empty(nb // 4, dtype=torch.float32, device=x2d.device)
     check(L.a2s_linear_wgrad(stream(), M, N, K, _p(dz), C.c_long(N), _p(x2d), C.c_long(K), _p(G), C.c_long(K), _p(x_affine[0]), _p(x_affine[1]), x_affine[2],
                              _p(dz_absmax), _p(x_bound), _p(ws), C.c_size_t(nb)), "a2s_linear_wgrad")
+    return True
+
+
+_TALLK_WS = {}
+
+
+def tallk_wgrad(P, p_off, ldp, A, a_off, lda, G, g_off, ldg, M, Np, K, p_absmax, a_absmax, transposed=False, bias=None):
+    """G (+)= P^T A over M rows on the tall-K kernel of csrc/a2s_linear.hip (a2s_tallk_wgrad): P (M, Np) is packed, A (M, K) streamed once; *_off
+    are element offsets into the tensors, ld* their row strides.  transposed: the result lands as G[k][n].  bias: bias[k] += column sums of A.
+    Returns False when the shape does not qualify or the switch "tallk_wgrad" is off -- the caller then runs the generic split-K GEMM.
+    The workspace (operand planes + slabs) is kept per (device, stream, host thread): steady-state steps allocate nothing."""
+    L = lib()
+    if not hasattr(L, "a2s_tallk_wgrad_eligible"):
+        return False
+    pp, pa, pg = P.data_ptr() + 4 * p_off, A.data_ptr() + 4 * a_off, G.data_ptr() + 4 * g_off
+    if (p_absmax is None or a_absmax is None or (pp | pa | pg | (bias.data_ptr() if bias is not None else 0)) % 16
+            or not L.a2s_tallk_wgrad_eligible(M, Np, K, ldp, lda, ldg, int(transposed))):
+        return False
+    nb = L.a2s_tallk_wgrad_ws_bytes(M, Np, K)
+    key = (A.device, torch.cuda.current_stream().cuda_stream, threading.get_ident())
+    ws = _TALLK_WS.get(key)
+    if ws is None or ws.numel() * 4 < nb:
+        ws = _TALLK_WS[key] = torch.empty((nb + 3) // 4, dtype=torch.float32, device=A.device)
+    check(L.a2s_tallk_wgrad(stream(), M, Np, K, C.c_void_p(pp), C.c_long(ldp), C.c_void_p(pa), C.c_long(lda), C.c_void_p(pg), C.c_long(ldg), int(transposed),
+                            _p(bias), _p(p_absmax), _p(a_absmax), _p(ws), C.c_size_t(ws.numel() * 4)), "a2s_tallk_wgrad")
     return True
 
 
