@@ -348,8 +348,7 @@ class Engine:
         same batch shape (Engine.check_counts), so no device-to-host read stalls the forward pass five times per step."""
         import torch.distributed as dist
         sums = torch.empty(2 * C_, dtype=torch.float32, device=partial.device)
-        hip.check(hip.lib().a2s_col_sum(hip.stream(), hip._p(partial), C.c_long(2 * C_), hip._p(sums), C.c_long(nblocks), 2 * C_,
-                                        hip.f32(1.0), hip.f32(0.0), C.c_void_p(0), C.c_size_t(0)), "a2s_col_sum (bn stats)")
+        hip.check(hip.lib().a2s_col_sum(hip.stream(), hip._p(partial), 2 * C_, hip._p(sums), nblocks, 2 * C_, 1.0, 0.0, None, 0), "a2s_col_sum (bn stats)")
         dist.all_reduce(sums)
         return sums, float(count) * dist.get_world_size()
 
@@ -381,10 +380,9 @@ class Engine:
             partial, count = self._global_stats(partial, nblocks, C_, count)
             nblocks = 1
         self.bn_counts[name] = count
-        hip.check(L.a2s_bn_finalize(hip.stream(), hip._p(partial), nblocks, C_, C.c_double(count), hip._p(S[name + ".weight"]),
-                                    hip._p(S[name + ".bias"]), hip._p(S[name + ".running_mean"]), hip._p(S[name + ".running_var"]),
-                                    hip._p(S[name + ".num_batches_tracked"]), hip._p(mean), hip._p(invstd), hip._p(scale),
-                                    hip._p(shift), hip.f32(1e-5), hip.f32(0.1), 1 if training else 0), "a2s_bn_finalize")
+        hip.check(L.a2s_bn_finalize(hip.stream(), hip._p(partial), nblocks, C_, count, hip._p(S[name + ".weight"]), hip._p(S[name + ".bias"]),
+                                    hip._p(S[name + ".running_mean"]), hip._p(S[name + ".running_var"]), hip._p(S[name + ".num_batches_tracked"]), hip._p(mean),
+                                    hip._p(invstd), hip._p(scale), hip._p(shift), 1e-5, 0.1, 1 if training else 0), "a2s_bn_finalize")
         return mean, invstd, scale, shift
 
     # ------------------------------------------------------------------ ConvStack
@@ -428,11 +426,11 @@ class Engine:
         partial = None
         if training:
             partial = self._empty(nblk, Cf, 2, dev=dev)
-            hip.check(L.a2s_col_stats(hip.stream(), hip._p(z), hip._p(partial), C.c_long(rows), Cf, rpb), "a2s_col_stats")
+            hip.check(L.a2s_col_stats(hip.stream(), hip._p(z), hip._p(partial), rows, Cf, rpb), "a2s_col_stats")
         mean, invstd, scale, shift = self._bn(S, "convstack.out_bn", partial, nblk, Cf, float(rows), training)
         out = self._empty(rows, Cf, dev=dev)
-        hip.check(L.a2s_bn1d_relu_dropout(hip.stream(), hip._p(z), hip._p(out), hip._p(scale), hip._p(shift), hip._p(drop_mask),
-                                          hip.f32(1.0 / 0.8), C.c_long(out.numel()), Cf), "a2s_bn1d_relu_dropout")
+        hip.check(L.a2s_bn1d_relu_dropout(hip.stream(), hip._p(z), hip._p(out), hip._p(scale), hip._p(shift), hip._p(drop_mask), 1.0 / 0.8, out.numel(), Cf),
+                  "a2s_bn1d_relu_dropout")
         saved.update(a4=a4, z=z, out_bn=(mean, invstd, scale, shift), drop=drop_mask)
         return out.view(B, T, Cf), saved
 
@@ -460,11 +458,9 @@ class Engine:
                 gh = self._empty(B, 3 * H, dev=dev)
                 hn = self._empty(B, H, dev=dev)
                 gates = self._empty(T, B, 4 * H, dev=dev) if training else None
-                hip.check(L.a2s_gru_seq_fwd(hip.stream(), hip._p(gi), C.c_long(T * 3 * H), C.c_long(3 * H),
-                                            hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(S[f"encoder.gru.bias_hh_{sfx}"]),
-                                            C.c_void_p(out.data_ptr() + 4 * d * H), C.c_long(T * 2 * H), C.c_long(2 * H),
-                                            hip._p(hbuf), hip._p(gh), hip._p(gates), hip._p(hn), B, T, H, d, hip._p(gws[d]),
-                                            C.c_size_t(gws[d].numel() * 4)), "a2s_gru_seq_fwd")
+                hip.check(L.a2s_gru_seq_fwd(hip.stream(), hip._p(gi), T * 3 * H, 3 * H, hip._p(S[f"encoder.gru.weight_hh_{sfx}"]),
+                                            hip._p(S[f"encoder.gru.bias_hh_{sfx}"]), C.c_void_p(out.data_ptr() + 4 * d * H), T * 2 * H, 2 * H, hip._p(hbuf), hip._p(gh),
+                                            hip._p(gates), hip._p(hn), B, T, H, d, hip._p(gws[d]), gws[d].numel() * 4), "a2s_gru_seq_fwd")
                 return {"gi": gi, "gates": gates, "hn": hn, "scratch": (hbuf, gh)}
 
             join = fork_on_streams(dev, streams, [lambda d=d, sfx=sfx: direction(d, sfx, gis[d])
@@ -506,10 +502,9 @@ class Engine:
         R = out.shape[0]
         E, Sz = self.cfg["note_emb_size"], self.cfg["staff_emb_size"]
         hsave = torch.empty((R, 2, maxlen, Sz), dtype=torch.float32, device=out.device) if record is not None else None
-        hip.check(L.a2s_staff_emb_fwd(hip.stream(), hip._p(S["decoder.note_emb.weight"]), arr,
-                                      hip._p(ids) if ids_are_i64 else C.c_void_p(0), C.c_void_p(0) if ids_are_i64 else hip._p(ids),
-                                      C.c_long(id_bstride), hip._p(lengths), C.c_long(len_stride), hip._p(out), C.c_long(out.stride(0)),
-                                      col0, hip._p(hsave), R, maxlen, E, Sz), "a2s_staff_emb_fwd")
+        hip.check(L.a2s_staff_emb_fwd(hip.stream(), hip._p(S["decoder.note_emb.weight"]), arr, hip._p(ids) if ids_are_i64 else None,
+                                      None if ids_are_i64 else hip._p(ids), id_bstride, hip._p(lengths), len_stride, hip._p(out), out.stride(0), col0, hip._p(hsave), R,
+                                      maxlen, E, Sz), "a2s_staff_emb_fwd")
         if record is not None:
             record.append(dict(ids=ids, lengths=lengths, len_stride=len_stride, col0=col0, maxlen=maxlen, id_bstride=id_bstride,
                                i64=ids_are_i64, hsave=hsave))
@@ -574,9 +569,8 @@ class Engine:
         if drop is None and training and drop_p > 0:
             drop = (torch.rand((n + 1, B, E), device=dev) >= drop_p).to(torch.uint8)
         # SOS token embedding -> x[0][:, :E]
-        hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S[prefix + ".embedding.weight"]), C.c_void_p(0), C.c_void_p(0), C.c_long(0), SOS,
-                                   hip._p(x), C.c_long(ldx), 0, B, E, hip._p(drop), hip.f32(1.0 / (1.0 - drop_p) if drop is not None else 1.0)),
-                  "a2s_embed_rows")
+        hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S[prefix + ".embedding.weight"]), None, None, 0, SOS, hip._p(x), ldx, 0, B, E, hip._p(drop),
+                                   1.0 / (1.0 - drop_p) if drop is not None else 1.0), "a2s_embed_rows")
         flags = (C.c_uint8 * max(n, 1))(*([int(f) for f in tf_flags] if tf_flags is not None else [0] * n))
         a = hip.NoteDecArgs()
         for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_b", S[prefix + ".attn.attn.bias"]),
@@ -679,8 +673,7 @@ class Engine:
         logits = self._empty(R, V, dev=dev)
         n_done = torch.zeros(1, dtype=torch.int32, device=dev)
         steps_exec = torch.zeros(1, dtype=torch.int32, device=dev)
-        hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S[prefix + ".embedding.weight"]), C.c_void_p(0), C.c_void_p(0), C.c_long(0), SOS,
-                                   hip._p(x), C.c_long(ldx), 0, R, E, C.c_void_p(0), hip.f32(1.0)), "a2s_embed_rows")
+        hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S[prefix + ".embedding.weight"]), None, None, 0, SOS, hip._p(x), ldx, 0, R, E, None, 1.0), "a2s_embed_rows")
         # scratch of the call's own: the K rows of a clip share one attention sweep (fused rows), which the bar-by-bar workspaces are not sized for
         attn_ws = hip.attn_workspace(B, T, H, dev, groups=K)
         gemm_ws = hip.gemm_workspace(R, dev)
@@ -980,10 +973,10 @@ class Engine:
             sos_rec = [] if training else None
             self._staff_token(S, sos_ids, two, 1, token, 0, 2, 2, True, sos_rec)
             token[:, 2 * Sz:4 * Sz].copy_(token[:, :2 * Sz])
-            hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S["decoder.time_sig_emb.weight"]), C.c_void_p(0), C.c_void_p(0), C.c_long(0),
-                                       cfg["num_time_sig"], hip._p(token), C.c_long(tokw), 4 * Sz, Bg, te, C.c_void_p(0), hip.f32(1.0)), "embed ts")
-            hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S["decoder.key_emb.weight"]), C.c_void_p(0), C.c_void_p(0), C.c_long(0),
-                                       cfg["num_keys"], hip._p(token), C.c_long(tokw), 4 * Sz + te, Bg, ke, C.c_void_p(0), hip.f32(1.0)), "embed key")
+            hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S["decoder.time_sig_emb.weight"]), None, None, 0, cfg["num_time_sig"], hip._p(token), tokw, 4 * Sz, Bg, te,
+                                       None, 1.0), "embed ts")
+            hip.check(L.a2s_embed_rows(hip.stream(), hip._p(S["decoder.key_emb.weight"]), None, None, 0, cfg["num_keys"], hip._p(token), tokw, 4 * Sz + te, Bg, ke, None,
+                                       1.0), "embed key")
 
             bar_saved, seg_saved = [], []
             # alignment of the bar-level attention: one column per bar (steps of bars never reached keep the fills)
@@ -1014,18 +1007,16 @@ class Engine:
                 # the odd stride of the bar-level GRU input row [token(141) | ctx] does not matter to them): 0.85 -> ~0.2 ms per call at 248 clips, in series
                 # with the group's decode; small groups keep the one-workgroup-per-clip kernel
                 bar_ws = bar_attn_workspace(dev, gidx, Bg, T, H)
-                hip.check(L.a2s_attn_step_fwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(qb), C.c_long(H),
-                                              hip._p(S["decoder.attn.v.weight"]), C.c_void_p(xbar.data_ptr() + 4 * tokw), C.c_long(ldxb),
-                                              C.c_void_p(headin.data_ptr() + 4 * 2 * H), C.c_long(4 * H), hip._p(attw), Bg, T, H,
-                                              C.c_void_p(0), 0, hip._p(bar_ws)), "a2s_attn_step_fwd")
+                hip.check(L.a2s_attn_step_fwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(qb), H, hip._p(S["decoder.attn.v.weight"]),
+                                              C.c_void_p(xbar.data_ptr() + 4 * tokw), ldxb, C.c_void_p(headin.data_ptr() + 4 * 2 * H), 4 * H, hip._p(attw), Bg, T, H,
+                                              None, 0, hip._p(bar_ws)), "a2s_attn_step_fwd")
                 if align:
                     hip.attn_align_rows(attw, bar_align["peak"][:, bar], bar_align["weight"][:, bar], bar_align["centroid"][:, bar])
                 gi = hip.linear(xbar, S["decoder.gru.weight_ih_l0"], S["decoder.gru.bias_ih_l0"])
                 gh = hip.linear(hidden, S["decoder.gru.weight_hh_l0"], S["decoder.gru.bias_hh_l0"])
                 hnew = self._empty(Bg, 2 * H, dev=dev)
                 gates = self._empty(Bg, 8 * H, dev=dev) if training else None
-                hip.check(L.a2s_gru_gates_fwd(hip.stream(), hip._p(gi), C.c_long(6 * H), hip._p(gh), C.c_long(6 * H), hip._p(hidden),
-                                              C.c_long(2 * H), hip._p(hnew), C.c_long(2 * H), hip._p(headin), C.c_long(4 * H),
+                hip.check(L.a2s_gru_gates_fwd(hip.stream(), hip._p(gi), 6 * H, hip._p(gh), 6 * H, hip._p(hidden), 2 * H, hip._p(hnew), 2 * H, hip._p(headin), 4 * H,
                                               hip._p(gates), Bg, 2 * H), "a2s_gru_gates_fwd")
                 return dict(xbar=xbar, headin=headin, qb=qb, attw=attw, gates=gates, hprev=hidden, hnew=hnew, keep=keep)
 
@@ -1036,8 +1027,8 @@ class Engine:
                     t2 = hip.linear(t1, S[f"decoder.{hname}.2.weight"], S[f"decoder.{hname}.2.bias"], act=1)
                     lg = hip.linear(t2, S[f"decoder.{hname}.4.weight"], S[f"decoder.{hname}.4.bias"])
                     am = torch.empty(Bg, dtype=torch.int32, device=dev)
-                    hip.check(L.a2s_log_softmax_rows(hip.stream(), hip._p(lg), C.c_long(nc), C.c_void_p(out_t.data_ptr() + 4 * bar * nc),
-                                                     C.c_long(bars * nc), hip._p(am), Bg, nc), "a2s_log_softmax_rows")
+                    hip.check(L.a2s_log_softmax_rows(hip.stream(), hip._p(lg), nc, C.c_void_p(out_t.data_ptr() + 4 * bar * nc), bars * nc, hip._p(am), Bg, nc),
+                              "a2s_log_softmax_rows")
                     heads[hname] = (t1, t2, lg, am)
                 return heads
 
@@ -1057,9 +1048,8 @@ class Engine:
                     self._staff_token(S, staff["lo"][0], staff["lo"][1], 1, token, 2 * Sz, Lo, Lo, False, tok_rec)
                     ts_ids, key_ids, i64, stride = heads["time_sig_out"][3], heads["key_out"][3], False, 1
                 for table, ids_, col, width in ((S["decoder.time_sig_emb.weight"], ts_ids, 4 * Sz, te), (S["decoder.key_emb.weight"], key_ids, 4 * Sz + te, ke)):
-                    hip.check(L.a2s_embed_rows(hip.stream(), hip._p(table), hip._p(ids_) if i64 else C.c_void_p(0),
-                                               C.c_void_p(0) if i64 else hip._p(ids_), C.c_long(stride), 0, hip._p(token), C.c_long(tokw), col, Bg,
-                                               width, C.c_void_p(0), hip.f32(1.0)), "embed next token")
+                    hip.check(L.a2s_embed_rows(hip.stream(), hip._p(table), hip._p(ids_) if i64 else None, None if i64 else hip._p(ids_), stride, 0, hip._p(token), tokw,
+                                               col, Bg, width, None, 1.0), "embed next token")
                 return token, tok_rec, (ts_ids, key_ids, i64, stride)
 
             for seg_i, seg in enumerate(segments):

@@ -17,8 +17,6 @@ import torch
 from . import hip
 from .spec import SOS, VOCAB_SIZE
 
-NULL = C.c_void_p(0)
-
 
 def _os_env(name, default):
     return os.environ.get(name, default)
@@ -40,8 +38,8 @@ def _colsum(x, ld, out, rows, ncol, x_off=0, out_off=0, beta=1.0):
         ws = _COLSUM_WS.get(key)
         if ws is None or ws.numel() < 1024 * ncol:
             ws = _COLSUM_WS[key] = torch.empty(1024 * max(ncol, 2048), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().a2s_col_sum(hip.stream(), _ptr(x, x_off), C.c_long(ld), _ptr(out, out_off), C.c_long(rows), ncol,
-                                    hip.f32(1.0), hip.f32(beta), hip._p(ws), C.c_size_t(ws.numel() if ws is not None else 0)), "a2s_col_sum")
+    hip.check(hip.lib().a2s_col_sum(hip.stream(), _ptr(x, x_off), ld, _ptr(out, out_off), rows, ncol, 1.0, beta, hip._p(ws), ws.numel() if ws is not None else 0),
+              "a2s_col_sum")
 
 
 def _linear_bwd(x, W, dy, G, wname, bname, dx=None, dx_beta=0.0, x_affine=None, dy_amax=None, x_bound=None):
@@ -82,9 +80,8 @@ def _staff_token_bwd(eng, S, G, rec, dtok):
     E, Sz = eng.cfg["note_emb_size"], eng.cfg["staff_emb_size"]
     ids = rec["ids"]
     hip.check(L.a2s_staff_emb_bwd(hip.stream(), hip._p(S["decoder.note_emb.weight"]), warr, hip._p(gptrs), hip._p(G["decoder.note_emb.weight"]),
-                                  hip._p(ids) if rec["i64"] else NULL, NULL if rec["i64"] else hip._p(ids), C.c_long(rec["id_bstride"]),
-                                  hip._p(rec["lengths"]), C.c_long(rec["len_stride"]), hip._p(dtok), C.c_long(dtok.stride(0)), rec["col0"],
-                                  hip._p(rec["hsave"]), dtok.shape[0], rec["maxlen"], E, Sz), "a2s_staff_emb_bwd")
+                                  hip._p(ids) if rec["i64"] else None, None if rec["i64"] else hip._p(ids), rec["id_bstride"], hip._p(rec["lengths"]), rec["len_stride"],
+                                  hip._p(dtok), dtok.stride(0), rec["col0"], hip._p(rec["hsave"]), dtok.shape[0], rec["maxlen"], E, Sz), "a2s_staff_emb_bwd")
     return gptrs     # keep alive until the caller returns
 
 
@@ -129,8 +126,8 @@ def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc,
     R = n * B
     # (a) dlogits for all executed steps, step-major (n, B, V)
     dlog = torch.empty((n, B, V), dtype=torch.float32, device=dev)
-    hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), hip._p(dprobs_bar), hip._p(probs_bar), C.c_long(probs_bar.stride(0)), n, hip._p(dlog),
-                                         R, V, B, 1), "a2s_log_softmax_bwd_rows")
+    hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), hip._p(dprobs_bar), hip._p(probs_bar), probs_bar.stride(0), n, hip._p(dlog), R, V, B, 1),
+              "a2s_log_softmax_bwd_rows")
     # (b) output projection, all steps at once: do_all = dlog W_out ; dW_out += dlog^T o ; db_out += colsum
     o2d, dlog2d = sv["o"].view(R, 2 * H2), dlog.view(R, V)
     do_all = torch.empty((n, B, 2 * H2), dtype=torch.float32, device=dev)
@@ -235,9 +232,8 @@ def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc,
             dx_w, ld_w = dx.view(R, ldx)[:, :E].index_select(0, live), E
             if drop is not None:
                 drop = drop.reshape(-1, E)[:R].index_select(0, live)
-        hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(G[prefix + ".embedding.weight"]), NULL, hip._p(tok), C.c_long(1), 0, hip._p(dx_w),
-                                          C.c_long(ld_w), 0, Rw, E, hip._p(drop), hip.f32(1.0 / (1.0 - sv["drop_p"]) if drop is not None else 1.0)),
-                  "a2s_embed_scatter_add")
+        hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(G[prefix + ".embedding.weight"]), None, hip._p(tok), 1, 0, hip._p(dx_w), ld_w, 0, Rw, E, hip._p(drop),
+                                          1.0 / (1.0 - sv["drop_p"]) if drop is not None else 1.0), "a2s_embed_scatter_add")
 
     def after_launch():
         if late is not None:
@@ -419,22 +415,22 @@ class Backward:
                     _staff_token_bwd(eng, S, Gg, rec, d_token_next)
                 ts_ids, key_ids, i64, stride = b["next_ids"]
                 for table, ids_, col, width in (("decoder.time_sig_emb.weight", ts_ids, 4 * Sz, te), ("decoder.key_emb.weight", key_ids, 4 * Sz + te, ke)):
-                    hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(Gg[table]), hip._p(ids_) if i64 else NULL, NULL if i64 else hip._p(ids_),
-                                                      C.c_long(stride), 0, hip._p(d_token_next), C.c_long(tokw), col, Bg, width, NULL, hip.f32(1.0)), "scatter ts/key")
+                    hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(Gg[table]), hip._p(ids_) if i64 else None, None if i64 else hip._p(ids_), stride, 0,
+                                                      hip._p(d_token_next), tokw, col, Bg, width, None, 1.0), "scatter ts/key")
             # ---- (2) heads: log_softmax + 3-layer MLP on headin = [bar_summary | ctx]
             d_headin = torch.zeros((Bg, 4 * H), dtype=torch.float32, device=dev)
             for hname, dout, out_t, nc in (("time_sig_out", dts_g, ts_out_g, cfg["num_time_sig"]), ("key_out", dkey_g, key_out_g, cfg["num_keys"])):
                 t1, t2, lg, _ = b["heads"][hname]
                 dlg = torch.empty((Bg, nc), dtype=torch.float32, device=dev)
-                hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), _ptr(dout, bar * nc), _ptr(out_t, bar * nc), C.c_long(bars * nc), 1, hip._p(dlg),
-                                                     Bg, nc, Bg, 0), "lsm bwd head")
+                hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), _ptr(dout, bar * nc), _ptr(out_t, bar * nc), bars * nc, 1, hip._p(dlg), Bg, nc, Bg, 0),
+                          "lsm bwd head")
                 p = f"decoder.{hname}"
                 dt2 = torch.empty_like(t2)
                 _linear_bwd(t2, S[p + ".4.weight"], dlg, Gg, p + ".4.weight", p + ".4.bias", dx=dt2)
-                hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(dt2), hip._p(t2), hip._p(dt2), C.c_long(dt2.numel()), 1), "relu bwd")
+                hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(dt2), hip._p(t2), hip._p(dt2), dt2.numel(), 1), "relu bwd")
                 dt1 = torch.empty_like(t1)
                 _linear_bwd(t1, S[p + ".2.weight"], dt2, Gg, p + ".2.weight", p + ".2.bias", dx=dt1)
-                hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(dt1), hip._p(t1), hip._p(dt1), C.c_long(dt1.numel()), 1), "relu bwd")
+                hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(dt1), hip._p(t1), hip._p(dt1), dt1.numel(), 1), "relu bwd")
                 _linear_bwd(b["headin"], S[p + ".0.weight"], dt1, Gg, p + ".0.weight", p + ".0.bias", dx=d_headin, dx_beta=1.0)
             # ---- (3) note decoders: both start from bar_summary
             d_hnew = torch.zeros((Bg, H2), dtype=torch.float32, device=dev)
@@ -451,9 +447,8 @@ class Backward:
             ldxb = tokw + H2
             dgi, dgh = torch.empty((Bg, 3 * H2), device=dev), torch.empty((Bg, 3 * H2), device=dev)
             dhp = torch.empty((Bg, H2), device=dev)
-            hip.check(L.a2s_gru_gates_bwd(hip.stream(), hip._p(d_hnew), C.c_long(H2), NULL, C.c_long(0), hip._p(b["gates"]), hip._p(b["hprev"]), C.c_long(H2),
-                                          hip._p(dgi), C.c_long(3 * H2), hip._p(dgh), C.c_long(3 * H2), NULL, C.c_long(0), hip._p(dhp), C.c_long(H2), Bg, H2),
-                      "gates bwd bar")
+            hip.check(L.a2s_gru_gates_bwd(hip.stream(), hip._p(d_hnew), H2, None, 0, hip._p(b["gates"]), hip._p(b["hprev"]), H2, hip._p(dgi), 3 * H2, hip._p(dgh),
+                                          3 * H2, None, 0, hip._p(dhp), H2, Bg, H2), "gates bwd bar")
             d_xbar = torch.empty((Bg, ldxb), device=dev)
             _linear_bwd(b["xbar"], S["decoder.gru.weight_ih_l0"], dgi, Gg, "decoder.gru.weight_ih_l0", "decoder.gru.bias_ih_l0", dx=d_xbar)
             _linear_bwd(b["hprev"], S["decoder.gru.weight_hh_l0"], dgh, Gg, "decoder.gru.weight_hh_l0", "decoder.gru.bias_hh_l0", dx=dhp, dx_beta=1.0)
@@ -465,13 +460,13 @@ class Backward:
                 # split-T kernels (round 5: 1.3 -> ~0.25 ms per bar at 248 clips): they load the saved context and its gradient 16 bytes at a time, so
                 # the two odd-stride column blocks of the bar-level GRU input row are copied out first (0.5 MB each)
                 ctx_c, dctx_c = b["xbar"][:, tokw:].contiguous(), d_xbar[:, tokw:].contiguous()
-                hip.check(L.a2s_attn_step_bwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(b["qb"]), C.c_long(H), hip._p(S["decoder.attn.v.weight"]),
-                                              hip._p(b["attw"]), hip._p(ctx_c), C.c_long(H2), hip._p(dctx_c), C.c_long(H2), _ptr(d_headin, H2),
-                                              C.c_long(4 * H), hip._p(dctx), C.c_long(H2), hip._p(dq), C.c_long(H), hip._p(ds), Bg, T, H, hip._p(bar_ws)), "attn bwd bar")
+                hip.check(L.a2s_attn_step_bwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(b["qb"]), H, hip._p(S["decoder.attn.v.weight"]),
+                                              hip._p(b["attw"]), hip._p(ctx_c), H2, hip._p(dctx_c), H2, _ptr(d_headin, H2), 4 * H, hip._p(dctx), H2, hip._p(dq), H,
+                                              hip._p(ds), Bg, T, H, hip._p(bar_ws)), "attn bwd bar")
             else:
-                hip.check(L.a2s_attn_step_bwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(b["qb"]), C.c_long(H), hip._p(S["decoder.attn.v.weight"]),
-                                              hip._p(b["attw"]), _ptr(b["xbar"], tokw), C.c_long(ldxb), _ptr(d_xbar, tokw), C.c_long(ldxb), _ptr(d_headin, H2),
-                                              C.c_long(4 * H), hip._p(dctx), C.c_long(H2), hip._p(dq), C.c_long(H), hip._p(ds), Bg, T, H, NULL), "attn bwd bar")
+                hip.check(L.a2s_attn_step_bwd(hip.stream(), hip._p(keys_g["decoder"]), hip._p(enc_g), hip._p(b["qb"]), H, hip._p(S["decoder.attn.v.weight"]),
+                                              hip._p(b["attw"]), _ptr(b["xbar"], tokw), ldxb, _ptr(d_xbar, tokw), ldxb, _ptr(d_headin, H2), 4 * H, hip._p(dctx), H2,
+                                              hip._p(dq), H, hip._p(ds), Bg, T, H, None), "attn bwd bar")
             Wa = S["decoder.attn.attn.weight"]
             hip.gemm(dq, H, 1, Wa, 4 * H, 1, dhp, H2, Bg, H2, H, beta=1.0)                              # d hprev += dq W_h
             hip.gemm(dq, 1, H, b["hprev"], H2, 1, Gg["decoder.attn.attn.weight"], 4 * H, H, H2, Bg, beta=1.0)   # dW_h += dq^T hprev
@@ -490,8 +485,8 @@ class Backward:
         d_sos[:, :2 * Sz] += d_sos[:, 2 * Sz:4 * Sz]
         _staff_token_bwd(eng, S, Gg, gs["sos_rec"][0], d_sos)
         for table, cid, col, width in (("decoder.time_sig_emb.weight", cfg["num_time_sig"], 4 * Sz, te), ("decoder.key_emb.weight", cfg["num_keys"], 4 * Sz + te, ke)):
-            hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(Gg[table]), NULL, NULL, C.c_long(0), cid, hip._p(d_token_next), C.c_long(tokw), col, Bg, width,
-                                              NULL, hip.f32(1.0)), "scatter sos ts/key")
+            hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(Gg[table]), None, None, 0, cid, hip._p(d_token_next), tokw, col, Bg, width, None, 1.0),
+                      "scatter sos ts/key")
         d_hidden[b0:b1].copy_(d_hid_carry)
         for ev in deferred_done:                      # the staves' weight / key / encoder-output gradients are complete past this point
             torch.cuda.current_stream().wait_event(ev)
@@ -642,7 +637,7 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
     W = S["encoder.fc.weight"]
     # bridge: hidden = tanh(pre); pre_l = fc([hf_l ; hr_l])
     dpre = torch.empty_like(d_hidden)
-    hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(d_hidden), hip._p(es["hidden"]), hip._p(dpre), C.c_long(dpre.numel()), 2), "tanh bwd")
+    hip.check(L.a2s_ew_act_bwd(hip.stream(), hip._p(d_hidden), hip._p(es["hidden"]), hip._p(dpre), dpre.numel(), 2), "tanh bwd")
     dhn = []
     for l in (0, 1):
         for half, hfin in enumerate((es["finals"][2 * l], es["finals"][2 * l + 1])):
@@ -672,15 +667,14 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
             # holds every element in a register; the launch-per-step kernels do not produce them (valid = 0): the tensors are measured then
             ranges, valid = torch.empty(2, device=dev), C.c_int(0)
             if two_term and L.a2s_debug_get(b"tallk_wgrad") > 0:
-                hip.check(L.a2s_gru_seq_bwd_ranged(hip.stream(), _ptr(dout, d * H), C.c_long(T * 2 * H), C.c_long(2 * H), _ptr(out, d * H), C.c_long(T * 2 * H),
-                                                   C.c_long(2 * H), hip._p(ls["dirs"][d]["gates"]), hip._p(S[f"encoder.gru.weight_hh_{sfx}"]),
-                                                   hip._p(dhn[2 * layer + d]), hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d,
-                                                   hip._p(gws[d]), C.c_size_t(gws[d].numel() * 4), hip._p(ranges), C.byref(valid)), "a2s_gru_seq_bwd_ranged")
+                hip.check(L.a2s_gru_seq_bwd_ranged(hip.stream(), _ptr(dout, d * H), T * 2 * H, 2 * H, _ptr(out, d * H), T * 2 * H, 2 * H, hip._p(ls["dirs"][d]["gates"]),
+                                                   hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]), hip._p(dgi), hip._p(dghs), hip._p(dgh_first),
+                                                   hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]), gws[d].numel() * 4, hip._p(ranges), C.byref(valid)),
+                          "a2s_gru_seq_bwd_ranged")
             else:
-                hip.check(L.a2s_gru_seq_bwd(hip.stream(), _ptr(dout, d * H), C.c_long(T * 2 * H), C.c_long(2 * H), _ptr(out, d * H), C.c_long(T * 2 * H),
-                                            C.c_long(2 * H), hip._p(ls["dirs"][d]["gates"]), hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]),
-                                            hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]),
-                                            C.c_size_t(gws[d].numel() * 4)), "a2s_gru_seq_bwd")
+                hip.check(L.a2s_gru_seq_bwd(hip.stream(), _ptr(dout, d * H), T * 2 * H, 2 * H, _ptr(out, d * H), T * 2 * H, 2 * H, hip._p(ls["dirs"][d]["gates"]),
+                                            hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]), hip._p(dgi), hip._p(dghs), hip._p(dgh_first),
+                                            hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]), gws[d].numel() * 4), "a2s_gru_seq_bwd")
             return (dgi, dghs, dgh_first, dhbuf, dgh_tmp, ranges if valid.value else None)
 
         res = fork_on_streams(dev, streams, [lambda d=d, sfx=sfx: direction(d, sfx) for d, sfx in enumerate((f"l{layer}", f"l{layer}_reverse"))])()
@@ -759,9 +753,9 @@ def _linear_dgrad_generic(L, dev, rows, F, Cf, dz, Wout, da, y4, bn4, dz_amax, w
         wb, s_bk, s_bn = Wt, 1, Cf
     else:
         wb, s_bk, s_bn = Wout, 40 * F, 1
-    hip.check(L.a2s_gemm_f32_bnstats_scaled(hip.stream(), rows, 40 * F, Cf, hip._p(dz), C.c_long(Cf), C.c_long(1), hip._p(wb), C.c_long(s_bk), C.c_long(s_bn),
-                                            hip._p(da), C.c_long(40 * F), hip._p(y4), hip._p(bn4[0]), hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F,
-                                            hip._p(part), hip._p(dz_amax), hip._p(w_amax)), "a2s_gemm_f32_bnstats_scaled")
+    hip.check(L.a2s_gemm_f32_bnstats_scaled(hip.stream(), rows, 40 * F, Cf, hip._p(dz), Cf, 1, hip._p(wb), s_bk, s_bn, hip._p(da), 40 * F, hip._p(y4), hip._p(bn4[0]),
+                                            hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F, hip._p(part), hip._p(dz_amax), hip._p(w_amax)),
+              "a2s_gemm_f32_bnstats_scaled")
     return part, nblk
 
 
@@ -785,32 +779,31 @@ def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
             glob = local.clone()
             dist.all_reduce(glob)
             c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_c12_from_sums(hip.stream(), hip._p(local), hip._p(glob), C.c_double(eng.bn_counts[name]), hip._p(G[name + ".weight"]),
-                                                 hip._p(G[name + ".bias"]), hip._p(c12), C_), "a2s_bn_bwd_c12_from_sums")
+            hip.check(L.a2s_bn_bwd_c12_from_sums(hip.stream(), hip._p(local), hip._p(glob), eng.bn_counts[name], hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]),
+                                                 hip._p(c12), C_), "a2s_bn_bwd_c12_from_sums")
             return c12
         if partial is not None and not eng.sync_bn:
             c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
             hip.check(L.a2s_bn_bwd_from_partial_amax(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift),
-                                                     hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), NULL if stats_only else hip._p(g),
-                                                     hip._p(partial[0]), partial[1], hip._p(c12), C.c_long(n_rows), C_, F_, hip._p(amax)),
-                      "a2s_bn_bwd_from_partial")
+                                                     hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), None if stats_only else hip._p(g), hip._p(partial[0]),
+                                                     partial[1], hip._p(c12), n_rows, C_, F_, hip._p(amax)), "a2s_bn_bwd_from_partial")
             return c12 if stats_only else g
-        part = torch.empty(L.a2s_bn_bwd_partial_floats(C.c_long(n_rows), C_, F_), dtype=torch.float32, device=dev)
+        part = torch.empty(L.a2s_bn_bwd_partial_floats(n_rows, C_, F_), dtype=torch.float32, device=dev)
         c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
         if eng.sync_bn:                                       # statistics of the global minibatch (see Engine.__init__)
             import torch.distributed as dist
             local = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_stats(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask),
-                                         hip.f32(1.0 / 0.8), hip._p(part), hip._p(local), C.c_long(n_rows), C_, F_), "a2s_bn_bwd_stats")
+            hip.check(L.a2s_bn_bwd_stats(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
+                                         hip._p(part), hip._p(local), n_rows, C_, F_), "a2s_bn_bwd_stats")
             glob = local.clone()
             dist.all_reduce(glob)
-            hip.check(L.a2s_bn_bwd_apply(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask),
-                                         hip.f32(1.0 / 0.8), hip._p(local), hip._p(glob), C.c_double(eng.bn_counts[name]), hip._p(G[name + ".weight"]),
-                                         hip._p(G[name + ".bias"]), hip._p(g), hip._p(c12), C.c_long(n_rows), C_, F_), "a2s_bn_bwd_apply")
+            hip.check(L.a2s_bn_bwd_apply(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
+                                         hip._p(local), hip._p(glob), eng.bn_counts[name], hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), hip._p(g),
+                                         hip._p(c12), n_rows, C_, F_), "a2s_bn_bwd_apply")
             return g
-        hip.check(L.a2s_bn_bwd_amax(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), hip.f32(1.0 / 0.8),
-                                    hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), NULL if stats_only else hip._p(g), hip._p(part), hip._p(c12),
-                                    C.c_long(n_rows), C_, F_, hip._p(amax)), "a2s_bn_bwd")
+        hip.check(L.a2s_bn_bwd_amax(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
+                                    hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), None if stats_only else hip._p(g), hip._p(part), hip._p(c12), n_rows, C_, F_,
+                                    hip._p(amax)), "a2s_bn_bwd")
         return c12 if stats_only else g                       # in place: g now holds dx
 
     # dropout + ReLU + BatchNorm1d over the (B*T, Cf) Linear output
@@ -864,9 +857,9 @@ def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
                 nb = L.a2s_linear_dgrad_ws_bytes(40 * F, Cf)
                 lws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
                 g_amax = torch.zeros(1, dtype=torch.float32, device=dev)          # max |da|: the range of the BatchNorm backward fused into conv4's weight gradient
-                hip.check(L.a2s_linear_dgrad_bnstats(hip.stream(), rows, 40 * F, Cf, hip._p(dz), C.c_long(Cf), hip._p(Wt), hip._p(da), C.c_long(40 * F), hip._p(y4),
-                                                     hip._p(bn4[0]), hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F, hip._p(part), hip._p(dz_amax), hip._p(w_amax),
-                                                     hip._p(lws), C.c_size_t(nb), hip._p(g_amax)), "a2s_linear_dgrad_bnstats")
+                hip.check(L.a2s_linear_dgrad_bnstats(hip.stream(), rows, 40 * F, Cf, hip._p(dz), Cf, hip._p(Wt), hip._p(da), 40 * F, hip._p(y4), hip._p(bn4[0]),
+                                                     hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F, hip._p(part), hip._p(dz_amax), hip._p(w_amax), hip._p(lws), nb,
+                                                     hip._p(g_amax)), "a2s_linear_dgrad_bnstats")
                 g_partial = (part, nblk)
             else:
                 g_partial = _linear_dgrad_generic(L, dev, rows, F, Cf, dz, Wout, da, y4, bn4, dz_amax, w_amax)
@@ -900,10 +893,10 @@ def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
             bn_i = cs["bn"][i - 1]
             c12 = bn_bwd(g, y, bn_i, f"convstack.bn{i}", None, rows, co, F, stats_only=True, partial=g_partial)
             dy = g                                                 # in place: every element is read and written once, by the same thread
-            hip.check(L.a2s_conv3x3_wgrad_bn_ranged(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]),
-                                                    hip._p(c12), hip._p(g_amax), g_amax.numel(), hip._p(cs["yabs"][i - 1]), hip._p(dy), hip._p(dy_amax), hip._p(x_in),
-                                                    hip._p(in_bn[2]), hip._p(in_bn[3]), hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), C.c_size_t(nb),
-                                                    B, T, F, ci, co, hip._p(cs["abound"][i - 2])), "a2s_conv3x3_wgrad_bn_ranged")
+            hip.check(L.a2s_conv3x3_wgrad_bn_ranged(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]), hip._p(c12),
+                                                    hip._p(g_amax), g_amax.numel(), hip._p(cs["yabs"][i - 1]), hip._p(dy), hip._p(dy_amax), hip._p(x_in),
+                                                    hip._p(in_bn[2]), hip._p(in_bn[3]), hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), nb, B, T, F, ci, co,
+                                                    hip._p(cs["abound"][i - 2])), "a2s_conv3x3_wgrad_bn_ranged")
         elif eng.sync_bn or not fuse_here:
             dy = bn_bwd(g, y, cs["bn"][i - 1], f"convstack.bn{i}", None, rows, co, F, partial=g_partial, amax=dy_amax)
             if eng.sync_bn and dy_amax is not None:            # (the synchronised apply pass does not reduce the range of what it writes)
@@ -916,9 +909,9 @@ def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
             bn_i = cs["bn"][i - 1]
             c12 = bn_bwd(g, y, bn_i, f"convstack.bn{i}", None, rows, co, F, stats_only=True, partial=g_partial)
             dy = torch.empty_like(g) if i > 1 else None
-            hip.check(L.a2s_conv3x3_wgrad_bn(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]),
-                                             hip._p(c12), hip._p(dy), hip._p(x_in), hip._p(in_bn[2]) if in_bn else NULL, hip._p(in_bn[3]) if in_bn else NULL,
-                                             hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), C.c_size_t(nb), B, T, F, ci, co), "a2s_conv3x3_wgrad_bn")
+            hip.check(L.a2s_conv3x3_wgrad_bn(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]), hip._p(c12),
+                                             hip._p(dy), hip._p(x_in), hip._p(in_bn[2]) if in_bn else None, hip._p(in_bn[3]) if in_bn else None,
+                                             hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), nb, B, T, F, ci, co), "a2s_conv3x3_wgrad_bn")
         if i > 1:
             gprev = torch.empty((B, T, ci, F), dtype=torch.float32, device=dev)
             cws = hip.conv_workspace(co, dev)
@@ -928,13 +921,12 @@ def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
                 nblk = L.a2s_conv3x3_stat_blocks(B, T, F, co)
                 part = torch.empty((nblk, ci, 2), dtype=torch.float32, device=dev)
                 g_amax_next = torch.empty(ci, dtype=torch.float32, device=dev) if (_FUSE_BN_ROWS and i > 2) else None      # max |g| per channel (zeroed by the launch)
-                hip.check(L.a2s_conv3x3_dgrad_bnstats_ranged(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev),
-                                                             hip._p(cs["y"][i - 2]), hip._p(bn_l[0]), hip._p(bn_l[1]), hip._p(bn_l[2]), hip._p(bn_l[3]),
-                                                             hip._p(part), B, T, F, co, ci, hip._p(cws),
-                                                             hip._p(dy_amax) if not fuse_here else NULL, hip._p(g_amax_next)), "a2s_conv3x3_dgrad_bnstats")
+                hip.check(L.a2s_conv3x3_dgrad_bnstats_ranged(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev), hip._p(cs["y"][i - 2]),
+                                                             hip._p(bn_l[0]), hip._p(bn_l[1]), hip._p(bn_l[2]), hip._p(bn_l[3]), hip._p(part), B, T, F, co, ci,
+                                                             hip._p(cws), hip._p(dy_amax) if not fuse_here else None, hip._p(g_amax_next)), "a2s_conv3x3_dgrad_bnstats")
                 g_partial = (part, nblk)
             else:
-                hip.check(L.a2s_conv3x3(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev), NULL, NULL, NULL, B, T, F, co, ci, 1,
+                hip.check(L.a2s_conv3x3(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev), None, None, None, B, T, F, co, ci, 1,
                                         hip._p(cws)), "a2s_conv3x3 dgrad")
                 g_partial = None
             g = gprev

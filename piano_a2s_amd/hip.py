@@ -6,59 +6,14 @@ import threading
 
 import torch
 
+from .abi import PROTOTYPES, STRUCTS, A2SError          # the ABI as include/a2s.h declares it; the package's one error type
 from .build import LIB
 
 LIB = os.environ.get("A2S_LIB", LIB)          # A/B measurements against an older build of the library
 
+# the argument blocks as include/a2s.h declares them (abi.py; lib() types the prototypes from it too): nothing of the ABI is restated here
+NoteDecArgs, NoteDecBwdArgs, BeamArgs, AlignArgs = (STRUCTS[n] for n in ("a2s_note_dec_args", "a2s_note_dec_bwd_args", "a2s_beam_args", "a2s_align_args"))
 _lib = None
-
-
-class A2SError(RuntimeError):
-    pass
-
-
-class NoteDecArgs(C.Structure):
-    """Mirror of `a2s_note_dec_args` (include/a2s.h) -- same members, same order."""
-    _fields_ = [(n, C.c_void_p) for n in (
-        "attn_w", "attn_b", "attn_v", "w_ih", "w_hh", "b_ih", "b_hh", "out_w", "out_b", "emb", "keys", "enc",
-        "h", "x", "q", "gates", "attw", "o", "gh", "gi", "logits")] + [
-        ("probs", C.c_void_p), ("probs_bstride", C.c_long),
-        ("gt", C.c_void_p), ("gt_bstride", C.c_long),
-        ("tf_flags", C.c_void_p),
-        ("drop", C.c_void_p), ("inv_keep", C.c_float),
-        ("argmax_out", C.c_void_p), ("am_bstride", C.c_long),
-        ("eos_seen", C.c_void_p), ("lengths", C.c_void_p), ("n_done", C.c_void_p), ("steps_exec", C.c_void_p), ("attn_ws", C.c_void_p),
-        ("gemm_ws", C.c_void_p), ("gemm_ws_bytes", C.c_size_t), ("t_base", C.c_void_p), ("clip_order", C.c_void_p), ("clip_rank", C.c_void_p),
-        ("row_until", C.c_void_p), ("n_active", C.c_void_p), ("n_clips", C.c_int), ("m_active", C.c_void_p),
-        ("row_list", C.c_void_p), ("n_rows_active", C.c_void_p),
-        ("R", C.c_int), ("T", C.c_int), ("H", C.c_int), ("E", C.c_int), ("V", C.c_int),
-        ("steps", C.c_int), ("poll", C.c_int), ("eos_id", C.c_int), ("use_graph", C.c_int),
-        ("step_ws", C.c_void_p), ("step_ws_floats", C.c_size_t),
-        ("tf_flags_dev", C.c_void_p), ("persist_ws", C.c_void_p), ("persist_ws_bytes", C.c_size_t)]
-
-
-class BeamArgs(C.Structure):
-    """Mirror of `a2s_beam_args` (include/a2s.h) -- same members, same order."""
-    _fields_ = [("K", C.c_int), ("alpha", C.c_float), ("next_state", C.c_void_p), ("n_states", C.c_int), ("pad_id", C.c_int)] + [
-        (n, C.c_void_p) for n in ("row_state", "score", "finished", "done_count", "token_hist", "parent_hist", "score_hist", "probs_scratch",
-                                  "ids_out", "lengths_out", "score_out")]
-
-
-class AlignArgs(C.Structure):
-    """Mirror of `a2s_align_args` (include/a2s.h) -- same members, same order."""
-    _fields_ = [("attw_step", C.c_void_p), ("peak", C.c_void_p), ("weight", C.c_void_p), ("centroid", C.c_void_p), ("out_stride", C.c_long),
-                ("next_state", C.c_void_p), ("n_states", C.c_int), ("row_state", C.c_void_p)]
-
-
-class NoteDecBwdArgs(C.Structure):
-    """Mirror of `a2s_note_dec_bwd_args` (include/a2s.h) -- same members, same order."""
-    _fields_ = [(n, C.c_void_p) for n in (
-        "attn_w", "attn_v", "w_ih", "w_hh", "keys", "enc", "h", "x", "q", "gates", "attw", "do_all",
-        "dgi_all", "dgh_all", "dq_all", "ds_all", "dctx_all", "dx", "dh", "attn_ws", "gemm_ws")] + [
-        ("gemm_ws_bytes", C.c_size_t), ("clip_order", C.c_void_p), ("clip_rank", C.c_void_p), ("row_until", C.c_void_p),
-        ("n_active", C.c_void_p), ("n_clips", C.c_int), ("m_active", C.c_void_p), ("row_list", C.c_void_p), ("n_rows_active", C.c_void_p),
-        ("R", C.c_int), ("T", C.c_int), ("H", C.c_int), ("E", C.c_int), ("steps", C.c_int),
-        ("step_ws", C.c_void_p), ("step_ws_floats", C.c_size_t), ("persist_ws", C.c_void_p), ("persist_ws_bytes", C.c_size_t), ("w_ih_full", C.c_void_p)]
 
 
 def lib():
@@ -74,21 +29,14 @@ def lib():
         if arith not in ("f16x2", "bf16x3", "f32"):
             raise A2SError(f"A2S_ARITH={arith!r}: expected f16x2, bf16x3 or f32")
         L = C.CDLL(LIB)
-        L.a2s_last_error.restype = C.c_char_p
-        L.a2s_launch_count.restype = C.c_longlong
-        for fn in ("a2s_note_step_workspace_floats", "a2s_note_decoder_persist_ws_bytes", "a2s_note_decoder_bwd_persist_ws_bytes", "a2s_linear_dgrad_ws_bytes", "a2s_linear_wgrad_ws_bytes", "a2s_tallk_wgrad_ws_bytes", "a2s_gemm_workspace_bytes", "a2s_bn_bwd_partial_floats", "a2s_conv3x3_wgrad_workspace_bytes", "a2s_attn_workspace_floats", "a2s_attn_workspace_floats_fused",
-                   "a2s_conv3x3_workspace_floats"):
-            getattr(L, fn).restype = C.c_size_t
+        for name, restype, argtypes in PROTOTYPES:          # every prototype the library exports is typed once, here: calls take plain Python numbers
+            fn = getattr(L, name, None)                  # (a build from before an entry point lacks it and leaves it unbound: its callers test hasattr)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         # the library has read the variables that override a switch's default itself (csrc/a2s_switches.h: the documented fallbacks of INTEGRATION.md)
         # (a build from before that call -- A2S_LIB, tools/lib_ab.sh -- reads them lazily and has nothing to report)
         if hasattr(L, "a2s_env_check") and L.a2s_env_check() != 0:
             raise A2SError(L.a2s_last_error().decode())
-        if hasattr(L, "a2s_edit_distance"):          # (absent from builds older than the device-side scoring: metrics.edit_distances then raises)
-            L.a2s_edit_distance.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]
-        if hasattr(L, "a2s_attn_denc_accum"):        # (absent from builds older than the live-pair dEnc kernel: engine_bwd then keeps the batched GEMM)
-            L.a2s_attn_denc_accum.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_int]
-        if hasattr(L, "a2s_tallk_wgrad_eligible"):   # (absent from builds older than the tall-K entry point: A2S_LIB, tools/lib_ab.sh)
-            L.a2s_tallk_wgrad_eligible.argtypes = [C.c_int] * 3 + [C.c_long] * 3 + [C.c_int]
         if arith != "f16x2":
             for key in (b"conv_f16x2", b"wgrad_f16x2", b"gemm_f16x2"):
                 L.a2s_debug_set(key, 0)
@@ -115,7 +63,7 @@ def abort_latch(device):
         t = _ABORT_LATCH[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
         _ABORT_LATCH["registered"] = None
     if _ABORT_LATCH.get("registered") != idx:
-        check(lib().a2s_persist_abort_latch(C.c_void_p(t.data_ptr())), "a2s_persist_abort_latch")
+        check(lib().a2s_persist_abort_latch(_p(t)), "a2s_persist_abort_latch")
         _ABORT_LATCH["registered"] = idx
     return t
 
@@ -240,8 +188,8 @@ def grammar_argmax_rows(x, table, row_state, y=None, V=None):
     if table.dtype != torch.int8 or row_state.dtype != torch.int32 or x.dtype != torch.float32 or not table.is_contiguous():
         raise A2SError("grammar_argmax_rows: expects float32 logits, a contiguous int8 table and int32 row states")
     choice = torch.empty(R, dtype=torch.int32, device=x.device)
-    check(lib().a2s_grammar_argmax_rows(stream(), _p(x), C.c_long(x.stride(0)), _p(y), C.c_long(y.stride(0) if y is not None else 0), _p(table),
-                                        table.shape[0], _p(row_state), _p(choice), R, V), "a2s_grammar_argmax_rows")
+    check(lib().a2s_grammar_argmax_rows(stream(), _p(x), x.stride(0), _p(y), y.stride(0) if y is not None else 0, _p(table), table.shape[0], _p(row_state), _p(choice),
+                                        R, V), "a2s_grammar_argmax_rows")
     return choice
 
 
@@ -285,13 +233,13 @@ def beam_buffers(B, K, max_steps, V, device, pad_id, table=None, start=0, alpha=
 def beam_step(g, logits, emb, xnext, h, q, n_done, steps_exec, B, t, max_steps, eos_id, V=None):
     """a2s_beam_step: one beam step epilogue over logits (K * B, >= V); h (K * B, cols) and q (or None) are re-parented in place."""
     V = logits.shape[1] if V is None else V
-    check(lib().a2s_beam_step(stream(), C.byref(g), _p(logits), C.c_long(logits.stride(0)), _p(emb), _p(xnext), C.c_long(xnext.stride(0)), _p(h), h.shape[1],
-                              _p(q), q.shape[1] if q is not None else 0, _p(n_done), _p(steps_exec), B, V, emb.shape[1], t, max_steps, eos_id), "a2s_beam_step")
+    check(lib().a2s_beam_step(stream(), C.byref(g), _p(logits), logits.stride(0), _p(emb), _p(xnext), xnext.stride(0), _p(h), h.shape[1], _p(q),
+                              q.shape[1] if q is not None else 0, _p(n_done), _p(steps_exec), B, V, emb.shape[1], t, max_steps, eos_id), "a2s_beam_step")
 
 
 def beam_backtrack(g, probs, steps_exec, B, V, max_steps, eos_id):
     """a2s_beam_backtrack: the pick and the walk back; probs (B, max_steps, V) receives the winning lineage's log-probabilities."""
-    check(lib().a2s_beam_backtrack(stream(), C.byref(g), _p(probs), C.c_long(probs.stride(0)), _p(steps_exec), B, V, max_steps, eos_id), "a2s_beam_backtrack")
+    check(lib().a2s_beam_backtrack(stream(), C.byref(g), _p(probs), probs.stride(0), _p(steps_exec), B, V, max_steps, eos_id), "a2s_beam_backtrack")
 
 
 def beam_launches():
@@ -310,7 +258,7 @@ def attn_align_rows(attw, peak, weight, centroid, T=None, R=None):
     stride = peak.stride(0) if peak.dim() else 1
     if any((o.stride(0) if o.dim() else 1) != stride or (o.shape[0] if o.dim() else 1) < R for o in (peak, weight, centroid)):
         raise A2SError("attn_align_rows: the three outputs need R rows and one common row stride")
-    check(lib().a2s_attn_align_rows(stream(), _p(attw), C.c_long(attw.stride(0) if attw.dim() > 1 else T), R, T, _p(peak), _p(weight), _p(centroid), C.c_long(stride)),
+    check(lib().a2s_attn_align_rows(stream(), _p(attw), attw.stride(0) if attw.dim() > 1 else T, R, T, _p(peak), _p(weight), _p(centroid), stride),
           "a2s_attn_align_rows")
 
 
@@ -331,7 +279,7 @@ def render_notes(programs, n_samples, wave=None):
         raise A2SError("render_notes: the output needs B rows of at least n_samples float32 with unit stride on the programs' device")
     if B == 0:
         return wave                           # (an empty tensor has no data pointer to pass: nothing to launch, as a2s_render_notes with B = 0)
-    check(lib().a2s_render_notes(stream(), _p(programs), programs.shape[1], int(n_samples), _p(wave), C.c_long(wave.stride(0)), B), "a2s_render_notes")
+    check(lib().a2s_render_notes(stream(), _p(programs), programs.shape[1], int(n_samples), _p(wave), wave.stride(0), B), "a2s_render_notes")
     return wave
 
 
@@ -379,21 +327,17 @@ def gemm(A, sAm, sAk, B, sBk, sBn, Cout, ldc, M, N, K, alpha=1.0, beta=0.0, bias
     pb = C.c_void_p(B.data_ptr() + 4 * b_off)
     pc = C.c_void_p(Cout.data_ptr() + 4 * c_off)
     if a_affine is None and b_affine is None and two_term is None:
-        check(L.a2s_gemm_f32(stream(), M, N, K, f32(alpha), pa, C.c_long(sAm), C.c_long(sAk), pb, C.c_long(sBk), C.c_long(sBn),
-                             f32(beta), pc, C.c_long(ldc), _p(bias), act, batch, C.c_long(bsA), C.c_long(bsB), C.c_long(bsC),
-                             splitk, _p(ws), C.c_size_t(ws_bytes)), "a2s_gemm_f32")
+        check(L.a2s_gemm_f32(stream(), M, N, K, alpha, pa, sAm, sAk, pb, sBk, sBn, beta, pc, ldc, _p(bias), act, batch, bsA, bsB, bsC, splitk, _p(ws), ws_bytes),
+              "a2s_gemm_f32")
         return
     asc, ash, ap = a_affine if a_affine is not None else (None, None, 0)
     bsc, bsh, bp = b_affine if b_affine is not None else (None, None, 0)
     if two_term is not None:
-        check(L.a2s_gemm_f32_affine_scaled(stream(), M, N, K, f32(alpha), pa, C.c_long(sAm), C.c_long(sAk), pb, C.c_long(sBk), C.c_long(sBn),
-                                           f32(beta), pc, C.c_long(ldc), _p(bias), act, batch, C.c_long(bsA), C.c_long(bsB), C.c_long(bsC),
-                                           splitk, _p(ws), C.c_size_t(ws_bytes), _p(asc), _p(ash), ap, _p(bsc), _p(bsh), bp,
-                                           _p(two_term[0]), _p(two_term[1])), "a2s_gemm_f32_affine_scaled")
+        check(L.a2s_gemm_f32_affine_scaled(stream(), M, N, K, alpha, pa, sAm, sAk, pb, sBk, sBn, beta, pc, ldc, _p(bias), act, batch, bsA, bsB, bsC, splitk, _p(ws),
+                                           ws_bytes, _p(asc), _p(ash), ap, _p(bsc), _p(bsh), bp, _p(two_term[0]), _p(two_term[1])), "a2s_gemm_f32_affine_scaled")
         return
-    check(L.a2s_gemm_f32_affine(stream(), M, N, K, f32(alpha), pa, C.c_long(sAm), C.c_long(sAk), pb, C.c_long(sBk), C.c_long(sBn),
-                                f32(beta), pc, C.c_long(ldc), _p(bias), act, batch, C.c_long(bsA), C.c_long(bsB), C.c_long(bsC),
-                                splitk, _p(ws), C.c_size_t(ws_bytes), _p(asc), _p(ash), ap, _p(bsc), _p(bsh), bp), "a2s_gemm_f32_affine")
+    check(L.a2s_gemm_f32_affine(stream(), M, N, K, alpha, pa, sAm, sAk, pb, sBk, sBn, beta, pc, ldc, _p(bias), act, batch, bsA, bsB, bsC, splitk, _p(ws), ws_bytes,
+                                _p(asc), _p(ash), ap, _p(bsc), _p(bsh), bp), "a2s_gemm_f32_affine")
 
 
 _ONES = {}
@@ -411,7 +355,7 @@ def absmax(x, out=None):
     """max |x| of a contiguous float32 tensor as a device scalar (operand scale of the two-term fp16 kernels)."""
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=x.device)
-    check(lib().a2s_absmax(stream(), _p(x), C.c_long(x.numel()), _p(out)), "a2s_absmax")
+    check(lib().a2s_absmax(stream(), _p(x), x.numel(), _p(out)), "a2s_absmax")
     return out
 
 
@@ -466,8 +410,8 @@ def conv3x3_wgrad(dy, x, scale, shift, dW, ws, dy_absmax, act_absmax):
     dy_absmax / act_absmax: device scalars max |dy| / bound of the activated input (None: unknown -> that operand unscaled)."""
     B, T, Cout, F = dy.shape
     Cin = x.shape[2]
-    check(lib().a2s_conv3x3_wgrad_ranged(stream(), _p(dy), _p(x), _p(scale), _p(shift), _p(dW), _p(ws), C.c_size_t(ws.numel() * 4), B, T, F, Cin, Cout,
-                                          _p(dy_absmax), _p(act_absmax)), "a2s_conv3x3_wgrad_ranged")
+    check(lib().a2s_conv3x3_wgrad_ranged(stream(), _p(dy), _p(x), _p(scale), _p(shift), _p(dW), _p(ws), ws.numel() * 4, B, T, F, Cin, Cout, _p(dy_absmax),
+                                         _p(act_absmax)), "a2s_conv3x3_wgrad_ranged")
 
 
 def conv3x3_wgrad_for_test(dy, x, scale, shift):
@@ -498,8 +442,8 @@ def linear_forward(x2d, weight, x_affine, x_bound, w_absmax, out=None):
             out = torch.empty((M, N), dtype=torch.float32, device=x2d.device)
         nb = L.a2s_linear_dgrad_ws_bytes(N, K)
         ws = torch.empty(nb // 4, dtype=torch.float32, device=x2d.device)
-        check(L.a2s_linear_fwd(stream(), M, N, K, _p(x2d), C.c_long(K), _p(weight), _p(out), C.c_long(N), _p(x_affine[0]), _p(x_affine[1]), period,
-                               _p(x_bound), _p(w_absmax), _p(ws), C.c_size_t(nb)), "a2s_linear_fwd")
+        check(L.a2s_linear_fwd(stream(), M, N, K, _p(x2d), K, _p(weight), _p(out), N, _p(x_affine[0]), _p(x_affine[1]), period, _p(x_bound), _p(w_absmax), _p(ws), nb),
+              "a2s_linear_fwd")
         return out
     return linear(x2d, weight, out=out, x_affine=x_affine, two_term=(x_bound, w_absmax))
 
@@ -515,8 +459,8 @@ def linear_wgrad(dz, x2d, x_affine, dz_absmax, x_bound, G):
         return False
     nb = L.a2s_linear_wgrad_ws_bytes(M, K)
     ws = torch.empty(nb // 4, dtype=torch.float32, device=x2d.device)
-    check(L.a2s_linear_wgrad(stream(), M, N, K, _p(dz), C.c_long(N), _p(x2d), C.c_long(K), _p(G), C.c_long(K), _p(x_affine[0]), _p(x_affine[1]), x_affine[2],
-                             _p(dz_absmax), _p(x_bound), _p(ws), C.c_size_t(nb)), "a2s_linear_wgrad")
+    check(L.a2s_linear_wgrad(stream(), M, N, K, _p(dz), N, _p(x2d), K, _p(G), K, _p(x_affine[0]), _p(x_affine[1]), x_affine[2], _p(dz_absmax), _p(x_bound), _p(ws), nb),
+          "a2s_linear_wgrad")
     return True
 
 
@@ -540,8 +484,8 @@ def tallk_wgrad(P, p_off, ldp, A, a_off, lda, G, g_off, ldg, M, Np, K, p_absmax,
     ws = _TALLK_WS.get(key)
     if ws is None or ws.numel() * 4 < nb:
         ws = _TALLK_WS[key] = torch.empty((nb + 3) // 4, dtype=torch.float32, device=A.device)
-    check(L.a2s_tallk_wgrad(stream(), M, Np, K, C.c_void_p(pp), C.c_long(ldp), C.c_void_p(pa), C.c_long(lda), C.c_void_p(pg), C.c_long(ldg), int(transposed),
-                            _p(bias), _p(p_absmax), _p(a_absmax), _p(ws), C.c_size_t(ws.numel() * 4)), "a2s_tallk_wgrad")
+    check(L.a2s_tallk_wgrad(stream(), M, Np, K, C.c_void_p(pp), ldp, C.c_void_p(pa), lda, C.c_void_p(pg), ldg, int(transposed), _p(bias), _p(p_absmax), _p(a_absmax),
+                            _p(ws), ws.numel() * 4), "a2s_tallk_wgrad")
     return True
 
 

@@ -105,7 +105,6 @@ def edit_distance_capacity():
 def edit_distances(ref_words, ref_off, hyp_words, hyp_off, device=None):
     """Unit-cost Levenshtein distance of every pair (ref_words[ref_off[p]:ref_off[p + 1]], hyp_words[hyp_off[p]:hyp_off[p + 1]]) as a numpy
     int array: one host-to-device copy, one launch on the current stream of `device` (default: the current one), one copy back."""
-    import ctypes as C
     import torch
     from . import hip
     L = hip.lib()

@@ -9,7 +9,6 @@ there is no host synchronisation in the step except the one the forward needs to
 Data parallelism: one process per GPU, gradients summed with ONE all-reduce over the flat gradient buffer (RCCL when the
 process group's backend is nccl; gloo on CPU in tests) and divided by the world size, as DDP does.
 """
-import ctypes as C
 import random as _py_random
 
 import torch
@@ -84,8 +83,8 @@ class Objective:
             V = o.shape[-1]
             rows = o.numel() // V
             t = t.contiguous()
-            hip.check(L.a2s_nll_loss(hip.stream(), hip._p(o), hip._p(t), C.c_long(rows), V, C.c_longlong(ign), C.c_void_p(self.losses.data_ptr() + 8 * i),
-                                     hip._p(grads[i]), hip.f32(1.0), hip._p(self.partial), self.nblocks), "a2s_nll_loss")
+            hip.check(L.a2s_nll_loss(hip.stream(), hip._p(o), hip._p(t), rows, V, ign, hip._p(self.losses.data_ptr() + 8 * i), hip._p(grads[i]), 1.0,
+                                     hip._p(self.partial), self.nblocks), "a2s_nll_loss")
         return self.losses, (grads if want_grad else None)
 
 
@@ -111,9 +110,9 @@ class FusedAdadelta:
 
     def step(self, flat_grads, loss_scalar=None, zero_grad=True):
         """The update is skipped ON THE DEVICE (ctl[2] = 0) when *loss_scalar or the gradient norm is not finite."""
-        hip.check(hip.lib().a2s_clip_adadelta(hip.stream(), hip._p(self.p), hip._p(flat_grads), hip._p(self.square_avg), hip._p(self.acc_delta),
-                                              C.c_long(self.p.numel()), hip._p(loss_scalar), hip.f32(self.max_grad_norm), hip.f32(self.lr), hip.f32(self.rho),
-                                              hip.f32(self.eps), hip._p(self.ctl), hip._p(self.partial), self.nblocks, 1 if zero_grad else 0), "a2s_clip_adadelta")
+        hip.check(hip.lib().a2s_clip_adadelta(hip.stream(), hip._p(self.p), hip._p(flat_grads), hip._p(self.square_avg), hip._p(self.acc_delta), self.p.numel(),
+                                              hip._p(loss_scalar), self.max_grad_norm, self.lr, self.rho, self.eps, hip._p(self.ctl), hip._p(self.partial), self.nblocks,
+                                              1 if zero_grad else 0), "a2s_clip_adadelta")
         self.steps += 1
 
     @property
@@ -485,8 +484,8 @@ class TrainStep:
                 d = [gouts[0][b0:b1], gouts[1][b0:b1], engine.group_views(gouts[2], groups, gidx), engine.group_views(gouts[3], groups, gidx)]
                 tg = [ts_t[b0:b1], key_t[b0:b1], up_lay[bars * U * b0: bars * U * b1], lo_lay[bars * Lo * b0: bars * Lo * b1]]
                 for i, (V_, ign) in enumerate(((cfg["num_time_sig"], -1), (cfg["num_keys"], -1), (VOCAB_SIZE, PAD), (VOCAB_SIZE, PAD))):
-                    hip.check(L.a2s_nll_grad(hip.stream(), hip._p(d[i]), hip._p(tg[i]), C.c_void_p(inv.data_ptr() + 8 * i), hip.f32(1.0),
-                                             C.c_long(d[i].numel() // V_), V_, C.c_longlong(ign)), "a2s_nll_grad")
+                    hip.check(L.a2s_nll_grad(hip.stream(), hip._p(d[i]), hip._p(tg[i]), hip._p(inv.data_ptr() + 8 * i), 1.0, d[i].numel() // V_, V_, ign),
+                              "a2s_nll_grad")
                 ctx.decoder_group(gidx, gs, *d)
 
             eng.group_hook = grads_and_backward

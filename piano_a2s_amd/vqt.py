@@ -23,7 +23,6 @@ oracle/vqt_ref.py restates the same algorithm on the CPU in float64 with FFTs (l
 report how far the round-1 direct-form definition was from it (it used the wrong channel scaling: 1/sqrt(length) without librosa's
 length/n_fft factor, a 14 dB tilt across the 8 octaves).
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -127,8 +126,7 @@ class VQT:
         yp = torch.zeros((B, plen), dtype=torch.float32, device=y.device)
         yp[:, self.half:self.half + N] = y
         out = torch.empty((B, n_out), dtype=torch.float32, device=y.device)
-        hip.check(hip.lib().a2s_vqt_decimate(hip.stream(), hip._p(yp), C.c_long(plen), hip._p(self.dec_bank), self.dec_taps, hip._p(out), C.c_long(n_out), B),
-                  "a2s_vqt_decimate")
+        hip.check(hip.lib().a2s_vqt_decimate(hip.stream(), hip._p(yp), plen, hip._p(self.dec_bank), self.dec_taps, hip._p(out), n_out, B), "a2s_vqt_decimate")
         return out
 
     def __call__(self, wave):
@@ -160,6 +158,6 @@ class VQT:
             col += 2 * nb
         out = torch.empty((B, 1, frames, self.n_bins), dtype=torch.float32, device=wave.device)
         partial = torch.empty(B * 64, dtype=torch.float32, device=wave.device)
-        hip.check(hip.lib().a2s_vqt_logmag_octaves(hip.stream(), hip._p(Cc), hip._p(out), hip._p(partial), B, C.c_long(frames), self.n_bins, self.bpo,
-                                                   hip.f32(80.0)), "a2s_vqt_logmag_octaves")
+        hip.check(hip.lib().a2s_vqt_logmag_octaves(hip.stream(), hip._p(Cc), hip._p(out), hip._p(partial), B, frames, self.n_bins, self.bpo, 80.0),
+                  "a2s_vqt_logmag_octaves")
         return out

@@ -1,5 +1,5 @@
 """CPU-side checks of the C-ABI boundary: the library builds, loads, exports every symbol include/a2s.h declares
-(no compute is launched without a GPU), the ctypes mirror of the argument block matches the C layout, and the
+(no compute is launched without a GPU), the ctypes classes of the four argument blocks match the C layout, and the
 product path refuses to run without device memory instead of falling back to anything."""
 import ctypes as C
 import os
@@ -29,9 +29,10 @@ def test_exports_every_declared_symbol(libpath):
     assert lib.a2s_version() >= 1 and isinstance(lib.a2s_last_error(), bytes)
 
 
-@pytest.mark.parametrize("cname,pyname", [("a2s_note_dec_args", "NoteDecArgs"), ("a2s_note_dec_bwd_args", "NoteDecBwdArgs")])
+@pytest.mark.parametrize("cname,pyname", [("a2s_note_dec_args", "NoteDecArgs"), ("a2s_note_dec_bwd_args", "NoteDecBwdArgs"),
+                                          ("a2s_beam_args", "BeamArgs"), ("a2s_align_args", "AlignArgs")])
 def test_arg_block_layout_matches_c(libpath, tmp_path, cname, pyname):
-    """sizeof / offsetof of the argument blocks as the C compiler sees them == the ctypes mirrors."""
+    """sizeof / offsetof of the argument blocks as the C compiler sees them == the ctypes classes piano_a2s_amd/abi.py derives from the header."""
     from piano_a2s_amd import hip
     cls = getattr(hip, pyname)
     fields = [f[0] for f in cls._fields_]

@@ -78,6 +78,25 @@ def test_gemm_strided_forms(dev):
     assert err < 5e-6, err
 
 
+def test_gemm_entry_point_takes_plain_python_scalars(dev):
+    """a2s_gemm_f32 called directly, every scalar a bare Python int or float (hip.lib() types the arguments from include/a2s.h), the pointers
+    through hip._p: alpha = 0.5 and beta = 2 on a pre-filled C catch a float passed as garbage, strides other than 1 (every second column of
+    A and B, a padded C) a `long` cut or misplaced."""
+    from piano_a2s_amd import hip
+    g = torch.Generator().manual_seed(64)
+    M = N = K = 64
+    A2, B2, C0 = torch.randn(M, 2 * K, generator=g), torch.randn(K, 2 * N, generator=g), torch.randn(M, N + 16, generator=g)
+    ref = 0.5 * (A2[:, ::2].double() @ B2[:, ::2].double()) + 2.0 * C0[:, :N].double()
+    Ad, Bd, Cd = A2.to(dev), B2.to(dev), C0.to(dev)
+    hip.check(hip.lib().a2s_gemm_f32(hip.stream(), M, N, K, 0.5, hip._p(Ad), 2 * K, 2, hip._p(Bd), 2 * N, 2, 2.0, hip._p(Cd), N + 16, hip._p(None), 0,
+                                     1, 0, 0, 0, 1, hip._p(None), 0), "a2s_gemm_f32")
+    torch.cuda.synchronize()
+    err = _rel(Cd[:, :N], ref)
+    _report(f"gemm plain scalars {M}x{N}x{K}", err)
+    assert err < 2e-6 * max(1.0, K ** 0.5 / 8), err        # as test_gemm_nt: fp32 accumulation of K products
+    assert torch.equal(Cd[:, N:].cpu(), C0[:, N:]), "the padding columns of C are not the launch's to write"
+
+
 @pytest.mark.parametrize("Cin,Cout", [(1, 20), (20, 20), (20, 40), (40, 40)])
 @pytest.mark.parametrize("B,T,F", [(2, 9, 24), (1, 41, 480), (1, 6, 100)])
 def test_conv3x3_with_input_affine_and_stats(dev, Cin, Cout, B, T, F):
