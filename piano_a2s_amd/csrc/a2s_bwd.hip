@@ -467,36 +467,36 @@ int a2s_ew_act_bwd_impl(hipStream_t st, const float* g, const float* y, float* d
 // Reverse of a2s_note_decoder_fwd for one (bar, staff); `steps` = steps the forward executed.
 // argument block: a2s_note_dec_bwd_args (single definition in include/a2s.h)
 
-// the pair's clip bookkeeping at one step and the geometry its dq partials use (both staves' sweeps of the step in one launch: attn_bwd_split256_pair)
-struct AttnPairBwdStep { const int* clip_order; const int* clip_rank; int n_clips; int n_active; int step; int G; int chunk; };
-static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, int s, AttnPairBwdStep& p);
-static int attn_pair_bwd_combine(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const AttnPairBwdStep& p);
+// both staves' sweeps of a step in one launch (attn_bwd_split256_pair, further down; AttnPairStep: a2s_internal.h)
+static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, int s, AttnPairStep& p);
+static int attn_pair_bwd_combine(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const AttnPairStep& p);
 
+// what a reverse loop keeps per staff: do the steps that stay on the loop run on the mid-size kernels (note_bwd_prepare), which half of a.dh holds the
+// incoming carry, and above how many rows the few-row kernels may not take a step over (-1: their own limit; as NoteStepMode::fused_rows_limit, a2s_seq.hip)
+struct NoteBwdStaff { bool mid = false; int cur = 0; int fused_rows_limit = -1; };
 static int note_bwd_step_rows(const a2s_note_dec_bwd_args& a, int s) { return (a.row_list && a.n_rows_active) ? a.n_rows_active[s] : a.R; }
-static thread_local int t_pair_rows_limit = -1;
-struct PairRowsLimit { PairRowsLimit(int v) { t_pair_rows_limit = v; } ~PairRowsLimit() { t_pair_rows_limit = -1; } };
-static bool note_bwd_step_fused(const a2s_note_dec_bwd_args& a, int s) {
+static bool note_bwd_step_fused(const a2s_note_dec_bwd_args& a, int s, int rows_limit) {
     const void* ptrs[] = {a.dgi_all, a.dgh_all, a.dq_all, a.dx, a.dh, a.w_ih, a.w_hh, a.attn_w};
     const int n = note_bwd_step_rows(a, s);
-    if (t_pair_rows_limit >= 0 && n > t_pair_rows_limit) return false;
+    if (rows_limit >= 0 && n > rows_limit) return false;
     return n > 0 && a2s_dec_step_fusable(n, a.H, a.E, 173, ptrs, 8, a.step_ws, a.step_ws_floats);      // (the vocabulary size plays no role here)
 }
 
-// One reverse step of a note decoder; `cur` = which half of a.dh holds the incoming carry (flipped on return).  part: 0 = the whole step; 1 = what
+// One reverse step of a note decoder; c.cur = which half of a.dh holds the incoming carry (flipped on return).  part: 0 = the whole step; 1 = what
 // comes before the attention sweep of a launch-per-step step (GRU cell, dx products), 2 = what comes behind it (dq reduction, dh products) -- the
 // pair loop runs 1, the two staves' sweep as one launch, then 2 with `pair` set.
-static int note_bwd_step(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, int& cur, bool mid, int part, const AttnPairBwdStep* pair) {
+static int note_bwd_step(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, NoteBwdStaff& c, int part, const AttnPairStep* pair) {
     const int H2 = 2 * a.H, ldx = a.E + H2, R = a.R;
-    const bool fused = note_bwd_step_fused(a, s);
+    const bool fused = note_bwd_step_fused(a, s, c.fused_rows_limit);
     a2s_attn_rows rows_v = {a.clip_order, a.clip_rank, a.row_until, a.n_clips > 0 ? a.n_clips : R, a.n_active ? a.n_active[s] : 0, s};
     const a2s_attn_rows* rows = a.n_active ? &rows_v : nullptr;
-    float* dh_in = a.dh + (long)cur * R * H2;
-    float* dh_out = a.dh + (long)(cur ^ 1) * R * H2;
+    float* dh_in = a.dh + (long)c.cur * R * H2;
+    float* dh_out = a.dh + (long)(c.cur ^ 1) * R * H2;
     if (fused) {
         const int nrows = note_bwd_step_rows(a, s);
         int rc = a2s_note_step_fused_bwd(st, a, s, dh_in, dh_out, rows, nrows, nrows < R ? a.row_list : nullptr);
         if (rc) return rc;
-        cur ^= 1;
+        c.cur ^= 1;
         return A2S_OK;
     }
     int gM = R, gB = 1;                  // rows of the per-step products: see enqueue_note_step (a2s_seq.hip); rows left out carry zero gradients
@@ -512,7 +512,7 @@ static int note_bwd_step(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, 
         rc = a2s_gru_gates_bwd_impl(st, dh_in, H2, dos, 2 * H2, a.gates + (long)s * R * 4 * H2, a.h + (long)s * R * H2, H2,
                                     dgi, 3 * H2, dgh, 3 * H2, nullptr, 0, dh_out, H2, R, H2);
         if (rc) return rc;
-        if (mid) {
+        if (c.mid) {
             const int nrows = note_bwd_step_rows(a, s);
             rc = a2s_note_step_mid_bwd(st, a, s, dh_out, nrows, nrows < R ? a.row_list : nullptr);
         } else {
@@ -530,22 +530,22 @@ static int note_bwd_step(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, 
                                        a.ds_all + (long)s * R * a.T, R, a.T, a.H, a.attn_ws, rows);
     if (rc) return rc;
     // dh_prev += dgh W_hh + dq W_h   (W_h = first 2H columns of attn_w (H, 4H))
-    if (!mid) {
+    if (!c.mid) {
         rc = a2s_gemm_impl(st, gM, H2, 3 * H2, 1.f, dgh, 3 * H2, 1, a.w_hh, H2, 1, 1.f, dh_out, H2, nullptr, 0, gB, gS * 3 * H2, 0, gS * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
         if (rc) return rc;
     }
-    if (mid) {
+    if (c.mid) {
         const int nrows = note_bwd_step_rows(a, s);
         rc = a2s_note_step_mid_bwd_query(st, a, s, dh_out, nrows, nrows < R ? a.row_list : nullptr);
     } else
     rc = a2s_gemm_impl(st, gM, H2, a.H, 1.f, a.dq_all + (long)s * R * a.H, a.H, 1, a.attn_w, 2 * H2, 1, 1.f, dh_out, H2, nullptr, 0, gB, gS * a.H, 0, gS * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
     if (rc) return rc;
-    cur ^= 1;
+    c.cur ^= 1;
     return A2S_OK;
 }
 
 // what a reverse loop needs before its first step: zeroed carries / dx, the transposed weight copies of the few-row and mid-size kernels
-static int note_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a, bool* mid_out) {
+static int note_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a, NoteBwdStaff& c) {
     const int H2 = 2 * a.H, ldx = a.E + H2, R = a.R;
     hipError_t e = hipMemsetAsync(a.dh, 0, sizeof(float) * 2 * R * H2, st);
     // (steps that skip finished rows leave their dx rows unwritten: they must read as zero gradients)
@@ -554,14 +554,14 @@ static int note_bwd_prepare(hipStream_t st, const a2s_note_dec_bwd_args& a, bool
     // transposed weight copies for the few-row kernels: needed as soon as ANY step of the call runs on them (the last step has the fewest rows,
     // but it may have none at all -- a row without <eos> whose last targets are <pad> -- while earlier steps still have 1 .. max_rows)
     bool any_fused = false;
-    for (int s = a.steps - 1; s >= 0 && !any_fused; --s) any_fused = note_bwd_step_fused(a, s);
+    for (int s = a.steps - 1; s >= 0 && !any_fused; --s) any_fused = note_bwd_step_fused(a, s, c.fused_rows_limit);
     // round 6: the dx / dh products of the steps that stay on this loop as ONE launch in front of the attention (dec_bwd_mid, a2s_step.hip), over the
     // rows still running; it reads the same transposed weight copies
     const bool mid = a2s_note_step_mid_bwd_ok(a);
     bool any_mid = false;
-    if (mid) for (int s = a.steps - 1; s >= 0 && !any_mid; --s) any_mid = !note_bwd_step_fused(a, s);
+    if (mid) for (int s = a.steps - 1; s >= 0 && !any_mid; --s) any_mid = !note_bwd_step_fused(a, s, c.fused_rows_limit);
     if (any_fused || any_mid) { int rc = a2s_note_step_fused_bwd_prepare(st, a); if (rc) return rc; }
-    *mid_out = mid;
+    c.mid = mid;
     return A2S_OK;
 }
 static int note_bwd_finish(hipStream_t st, const a2s_note_dec_bwd_args& a, int cur) {
@@ -575,17 +575,16 @@ static int note_bwd_finish(hipStream_t st, const a2s_note_dec_bwd_args& a, int c
 int a2s_note_decoder_bwd_impl(hipStream_t st, const a2s_note_dec_bwd_args& a) {
     // few clips: one persistent launch for the whole reverse loop (a2s_dec_persist.hip)
     if (a2s_note_decoder_bwd_persist_ok(a)) return a2s_note_decoder_bwd_persist(st, a);
-    bool mid = false;
-    int rc = note_bwd_prepare(st, a, &mid);
+    NoteBwdStaff c;
+    int rc = note_bwd_prepare(st, a, c);
     if (rc) return rc;
-    int cur = 0;
     // rows step s covers on the few-row kernels: all R, or the rows still running (a prefix of row_list); the kernels take over for the steps
     // whose rows fit them (see a2s_note_decoder_fwd_impl)
     for (int s = a.steps - 1; s >= 0; --s) {
-        rc = note_bwd_step(st, a, s, cur, mid, 0, nullptr);
+        rc = note_bwd_step(st, a, s, c, 0, nullptr);
         if (rc) return rc;
     }
-    return note_bwd_finish(st, a, cur);
+    return note_bwd_finish(st, a, c.cur);
 }
 
 // The reverse loops of a segment's two NoteDecoders issued by ONE host loop on their two streams (forward: a2s_note_decoder_fwd_pair_impl,
@@ -601,36 +600,30 @@ int a2s_note_decoder_bwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
         const int rc = a2s_note_decoder_bwd_impl(su, au);
         return rc ? rc : a2s_note_decoder_bwd_impl(sl, al);
     }
-    static thread_local hipEvent_t ev[2] = {nullptr, nullptr};
-    for (int k = 0; k < 2; ++k)
-        if (!ev[k]) { const hipError_t e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming); if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_bwd_pair: hipEventCreate: %s", hipGetErrorString(e)); }
-    bool mid[2] = {false, false};
-    int cur[2] = {0, 0};
-    const PairRowsLimit limit(a2s_attn_pair_fused_rows());
-    for (int k = 0; k < 2; ++k) { const int rc = note_bwd_prepare(sts[k], *as[k], &mid[k]); if (rc) return rc; }
+    const char* who = "note_decoder_bwd_pair";
+    hipEvent_t* ev = nullptr;
+    { const int rc = a2s_pair_events(who, &ev); if (rc) return rc; }
+    NoteBwdStaff cs[2] = {{.fused_rows_limit = a2s_attn_pair_fused_rows()}, {.fused_rows_limit = a2s_attn_pair_fused_rows()}};
+    for (int k = 0; k < 2; ++k) { const int rc = note_bwd_prepare(sts[k], *as[k], cs[k]); if (rc) return rc; }
     const int nmax = au.steps > al.steps ? au.steps : al.steps;
     for (int s = nmax - 1; s >= 0; --s) {
         bool in[2], fused[2] = {false, false};
-        for (int k = 0; k < 2; ++k) { in[k] = s < as[k]->steps; if (in[k]) fused[k] = note_bwd_step_fused(*as[k], s); }
-        AttnPairBwdStep p = {pair_order, pair_rank, au.n_clips, pair_n_active[s], s, 1, au.T};
-        const bool joint = in[0] && in[1] && mid[0] && mid[1] && !fused[0] && !fused[1] && p.n_active > 0 && au.n_active[s] > 0 && al.n_active[s] > 0;
+        for (int k = 0; k < 2; ++k) { in[k] = s < as[k]->steps; if (in[k]) fused[k] = note_bwd_step_fused(*as[k], s, cs[k].fused_rows_limit); }
+        AttnPairStep p = {pair_order, pair_rank, au.n_clips, pair_n_active[s], s, 1, au.T};
+        const bool joint = in[0] && in[1] && cs[0].mid && cs[1].mid && !fused[0] && !fused[1] && p.n_active > 0 && au.n_active[s] > 0 && al.n_active[s] > 0;
         if (!joint) {
             for (int k = 0; k < 2; ++k)
-                if (in[k]) { const int rc = note_bwd_step(sts[k], *as[k], s, cur[k], mid[k], 0, nullptr); if (rc) return rc; }
+                if (in[k]) { const int rc = note_bwd_step(sts[k], *as[k], s, cs[k], 0, nullptr); if (rc) return rc; }
             continue;
         }
-        for (int k = 0; k < 2; ++k) { const int rc = note_bwd_step(sts[k], *as[k], s, cur[k], mid[k], 1, nullptr); if (rc) return rc; }
-        hipError_t e = hipEventRecord(ev[1], sl);                           // the lower staff's dx of this step
-        if (e == hipSuccess) e = hipStreamWaitEvent(su, ev[1], 0);
-        if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_bwd_pair: event: %s", hipGetErrorString(e));
-        const int rc = attn_pair_bwd_sweep(su, au, al, s, p);
+        for (int k = 0; k < 2; ++k) { const int rc = note_bwd_step(sts[k], *as[k], s, cs[k], 1, nullptr); if (rc) return rc; }
+        int rc = a2s_record_wait(ev[1], sl, su, who);                       // the lower staff's dx of this step
+        if (rc == A2S_OK) rc = attn_pair_bwd_sweep(su, au, al, s, p);
+        if (rc == A2S_OK) rc = a2s_record_wait(ev[0], su, sl, who);
         if (rc) return rc;
-        e = hipEventRecord(ev[0], su);
-        if (e == hipSuccess) e = hipStreamWaitEvent(sl, ev[0], 0);
-        if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_bwd_pair: event: %s", hipGetErrorString(e));
-        for (int k = 0; k < 2; ++k) { const int rc2 = note_bwd_step(sts[k], *as[k], s, cur[k], mid[k], 2, &p); if (rc2) return rc2; }
+        for (int k = 0; k < 2; ++k) { const int rc2 = note_bwd_step(sts[k], *as[k], s, cs[k], 2, &p); if (rc2) return rc2; }
     }
-    for (int k = 0; k < 2; ++k) { const int rc = note_bwd_finish(sts[k], *as[k], cur[k]); if (rc) return rc; }
+    for (int k = 0; k < 2; ++k) { const int rc = note_bwd_finish(sts[k], *as[k], cs[k].cur); if (rc) return rc; }
     return A2S_OK;
 }
 
@@ -1586,7 +1579,7 @@ static int attn_step_bwd_split_impl(hipStream_t st, const float* Kmat, const flo
 
 template <int NQ>
 static void launch_bwd_pair(hipStream_t st, int nwg, size_t shm, const AttnPairBwdSide& s0, const AttnPairBwdSide& s1, const float* enc, long ldq, long ldctx,
-                            long ldda, long lddb, long lddo, int T, const AttnPairBwdStep& p) {
+                            long ldda, long lddb, long lddo, int T, const AttnPairStep& p) {
     hipLaunchKernelGGL((attn_bwd_split256_pair<NQ, false>), dim3(nwg), dim3(256), shm, st, s0, s1, enc, ldq, ldctx, ldda, lddb, lddo, T, p.G, p.chunk,
                        p.clip_order, p.step, p.n_clips);
 }
@@ -1600,7 +1593,7 @@ static AttnPairBwdSide attn_pair_bwd_side(const a2s_note_dec_bwd_args& a, int s)
                            a.do_all + (long)s * R * 2 * H2 + H2, a.dctx_all + (long)s * R * H2, a.attn_ws + A2S_ATTN_TICKETS, a.ds_all + (long)s * R * a.T, a.row_until};
 }
 
-static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, int s, AttnPairBwdStep& p) {
+static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, const a2s_note_dec_bwd_args& al, int s, AttnPairStep& p) {
     const int T = au.T, H2 = 2 * au.H, ldx = au.E + H2, groups = au.R / p.n_clips;
     A2S_REQUIRE(au.H == 256 && au.E == al.E && au.enc == al.enc && au.R == al.R && groups >= 1 && groups <= A2S_ATTN_MAX_GROUPS && ldx % 4 == 0,
                 "attn_pair_bwd_sweep: the staves must decode the same rows over the same encoder outputs");
@@ -1624,7 +1617,7 @@ static int attn_pair_bwd_sweep(hipStream_t st, const a2s_note_dec_bwd_args& au, 
 }
 
 // one staff's dq reduction behind a pair sweep (rows the forward skipped: zeros in dq, ds, dctx)
-static int attn_pair_bwd_combine(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const AttnPairBwdStep& p) {
+static int attn_pair_bwd_combine(hipStream_t st, const a2s_note_dec_bwd_args& a, int s, const AttnPairStep& p) {
     const int H2 = 2 * a.H;
     const long R = a.R;
     hipLaunchKernelGGL(attn_bwd_combine256, dim3(a.R), dim3(256), 0, st, a.attn_ws + A2S_ATTN_TICKETS, a.dq_all + (long)s * R * a.H, (long)a.H, p.G, p.clip_rank,

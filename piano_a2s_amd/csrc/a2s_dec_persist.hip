@@ -977,14 +977,9 @@ int a2s_note_decoder_fwd_persist(hipStream_t st, const a2s_note_dec_args& a, int
     char* base = reinterpret_cast<char*>(a.persist_ws);
     const size_t head = 512 + sizeof(unsigned) * 8 * NWG + sizeof(u64) * (size_t)C * DP_REGION;
     hipError_t e = hipMemsetAsync(base, 0, head, st);
-    // what the backward pass reads of rows / steps this call never writes must be finite (as a2s_note_decoder_fwd_impl does for its tail path)
-    const long n = a.steps, R = a.R;
-    if (e == hipSuccess) e = hipMemsetAsync(a.h + R * H2, 0, sizeof(float) * n * R * H2, st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.x + R * KX, 0, sizeof(float) * n * R * KX, st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.q, 0, sizeof(float) * n * R * HH, st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.o, 0, sizeof(float) * n * R * 2 * H2, st);
-    if (e == hipSuccess && a.gates) e = hipMemsetAsync(a.gates, 0, sizeof(float) * n * R * 4 * H2, st);
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_persist memset: %s", hipGetErrorString(e));
+    { const int rc = a2s_note_decoder_zero_unwritten(st, a, "note_decoder_fwd_persist"); if (rc) return rc; }
+    const long n = a.steps, R = a.R;
     DecPersistFwd p;
     p.attn_w = a.attn_w; p.attn_b = a.attn_b; p.attn_v = a.attn_v; p.w_ih = a.w_ih; p.w_hh = a.w_hh; p.b_ih = a.b_ih; p.b_hh = a.b_hh;
     p.out_w = a.out_w; p.out_b = a.out_b; p.emb = a.emb; p.keys = a.keys; p.enc = a.enc;

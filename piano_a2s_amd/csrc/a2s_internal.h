@@ -150,9 +150,21 @@ int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_not
 int a2s_staff_emb_fwd_impl(hipStream_t st, const float* note_emb, const float* const* w /* 8 GRU tensors f then r */,
     const long long* ids64, const int* ids32, long id_bstride, const long long* lengths,
     long len_stride, float* out, long ldo, int col0, float* hsave, int R, int maxlen, int E, int S);
+int a2s_note_decoder_zero_unwritten(hipStream_t st, const a2s_note_dec_args& a, const char* who /* in the error message */);
 size_t a2s_attn_workspace_floats_impl(int B, int T, int H, int groups);
 size_t a2s_attn_bulk_lds(size_t shm, int n_active, int backward);
 long a2s_attn_pair_launches(void);
+// the pair loops (forward here, reverse in a2s_bwd.hip) launch both staves' sweeps of a step at once.  AttnPairStep: the pair's clip bookkeeping at
+// one step and the geometry its partials use (the sweep sets G and chunk, the staves' combines read them)
+struct AttnPairStep { const int* clip_order; const int* clip_rank; int n_clips; int n_active; int step; int G; int chunk; };
+int a2s_pair_events(const char* who, hipEvent_t** ev_out);       // -> the issuing thread's two events on the current device
+// what stream `from` has been given so far, stream `to` waits for
+static inline int a2s_record_wait(hipEvent_t ev, hipStream_t from, hipStream_t to, const char* who) {
+    hipError_t e = hipEventRecord(ev, from);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+    if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "%s: event: %s", who, hipGetErrorString(e));
+    return A2S_OK;
+}
 
 // ---- a2s_bwd.hip
 int a2s_log_softmax_bwd_rows_impl(hipStream_t st, const float* g, const float* y, long outer_stride, int inner, float* dx,

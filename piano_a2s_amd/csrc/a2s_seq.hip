@@ -7,6 +7,7 @@
 //   energy = tanh(W [h ; enc_t] + b) = tanh(W_h h + b  +  W_e enc_t) = tanh(q + K_t)
 // K = enc W_e^T is step-invariant and computed once per layer by the GEMM; per step only
 // q (a skinny GEMM), the score/softmax and the context remain -- one pass over K and one over enc.
+#include <vector>
 #include "a2s_internal.h"
 
 // ------------------------------------------------------------------------------------------- GRU cell
@@ -484,21 +485,16 @@ int a2s_embed_rows_impl(hipStream_t st, const float* table, const long long* ids
 // no-op once n_done == R, and the host polls n_done every `poll` steps to stop launching.
 typedef a2s_note_dec_args NoteDecArgs;   // one definition only: the public C struct (include/a2s.h)
 
-// rows the fused step of step t would cover: all R, or (training, finished rows skipped) the rows still running, a prefix of row_list
-// both staves' sweeps of a step in one launch (round 6, further down): the pair's clip bookkeeping at this step and the geometry its partials use
-struct AttnPairStep { const int* clip_order; const int* clip_rank; int n_clips; int n_active; int step; int G; int chunk; };
+// both staves' sweeps of a step in one launch (round 6, further down; AttnPairStep: a2s_internal.h)
 static int attn_pair_sweep(hipStream_t st, const NoteDecArgs& au, const NoteDecArgs& al, int sv, AttnPairStep& p);
 static int attn_pair_combine(hipStream_t st, const NoteDecArgs& a, int si, int sv, const AttnPairStep& p);
+// rows the fused step of step t would cover: all R, or (training, finished rows skipped) the rows still running, a prefix of row_list
 static int note_step_rows(const NoteDecArgs& a, int t) { return (a.row_list && a.n_rows_active && t >= 0) ? a.n_rows_active[t] : a.R; }
-// inside the pair loop (a2s_note_decoder_fwd_pair_impl) the few-row kernels take over later: at a2s_debug_set("attn_pair_fused_rows") rows (32) instead of
-// "dec_fused_max_rows" (192) -- above that, a lockstep step with its shared sweep beats two few-row steps (192 -> 64: +1.2 ms per step, 64 -> 32: +2.2, 32 -> 16: +0.1,
-// never: -16.8; profiles/r06_pair_fused_rows_ab.txt)
-static thread_local int t_pair_rows_limit = -1;
-struct PairRowsLimit { PairRowsLimit(int v) { t_pair_rows_limit = v; } ~PairRowsLimit() { t_pair_rows_limit = -1; } };
-static bool note_step_fusable(const NoteDecArgs& a, int t = -1) {
+// rows_limit >= 0: the few-row kernels take over only at that many rows or fewer (NoteStepMode::fused_rows_limit)
+static bool note_step_fusable(const NoteDecArgs& a, int t = -1, int rows_limit = -1) {
     const void* ptrs[] = {a.x, a.h, a.o, a.q, a.w_ih, a.w_hh, a.out_w, a.attn_w};
     const int n = note_step_rows(a, t);
-    if (t_pair_rows_limit >= 0 && n > t_pair_rows_limit) return false;
+    if (rows_limit >= 0 && n > rows_limit) return false;
     return n > 0 && a2s_dec_step_fusable(n, a.H, a.E, a.V, ptrs, 8, a.step_ws, a.step_ws_floats, a.gt == nullptr && !a.gates);
 }
 // the launch-per-step loop's steps on the mid-size kernels (round 6)?  Not in graph-replay mode: its captured chunk computes the query at the start of a step
@@ -513,25 +509,45 @@ static int enqueue_query(hipStream_t st, const NoteDecArgs& a, int si, int sv) {
                          0, 0, 0, a.gemm_ws, a.gemm_ws_bytes);
 }
 
-// one decode step: state read from slot `si`, written to slot `so` (slot = step index, or step parity in graph mode);
-// per-step saved tensors (q, o, gates, attention weights) go to index `sv`.  fused: the few-row path of a2s_step.hip -- the query
-// of slot sv must already be there (enqueue_query / the previous step), this step leaves the next one's in slot sv_next (!last).
-static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int so, int sv, int t, const int* t_base, int tf,
-                             bool fused = false, int sv_next = 0, bool last = false, const AttnPairStep* pair = nullptr,
-                             const a2s_grammar_ref* grammar = nullptr, const a2s_beam_args* beam = nullptr, const a2s_align_args* align = nullptr) {
-    const int H2 = 2 * a.H, ldx = a.E + H2;
-    if (fused) {
-        float* xs = a.x + (long)si * a.R * ldx;
-        float* os = a.o + (long)sv * a.R * 2 * H2;
-        a2s_attn_rows rows_v = {a.clip_order, a.clip_rank, a.row_until, a.n_clips > 0 ? a.n_clips : a.R, a.n_active ? a.n_active[t] : 0, t};
+// The step descriptor.  NoteStepMode: what holds for a whole call -- the entry point builds it once, with designated initialisers; a new decoding
+// feature gets a field here, not another positional argument or another loop.
+struct NoteStepMode {
+    const a2s_grammar_ref* grammar = nullptr;    // the epilogue: the constrained choice (a2s_grammar.hip) ...
+    const a2s_beam_args* beam = nullptr;         // ... the beam step (a2s_beam.hip), else the argmax epilogue
+    const a2s_align_args* align = nullptr;       // the step's attention weights reduced into column t of the alignment arrays (a2s_align.hip)
+    const int* t_base = nullptr;                 // graph replay: step index = t + *t_base
+    bool parity_slots = false;                   // state, input, query and output rows ping-pong between two slots (beam); else slot = step index
+    bool few_row = false;                        // may the few-row kernels of a2s_step.hip take a step over?
+    int fused_rows_limit = -1;                   // ... and above how many rows they may not (-1: their own limit).  The pair loop sets "attn_pair_fused_rows" (32,
+                                                 // not 192: above it a lockstep step with its shared sweep beats two few-row steps; profiles/r06_pair_fused_rows_ab.txt)
+    const char* label = "note_decoder";          // the entry point's name in error messages
+};
+// NoteStep: one decode step.  State read from slot `si`, written to slot `so`; per-step saved tensors (q, o, gates, attention weights) go to index
+// `sv`.  fused: the few-row path -- the query of slot sv must already be there (enqueue_query / the previous step), this step leaves the next
+// one's in slot sv_next (!last).  pair: this step's sweep has been launched for both staves at once.
+struct NoteStep { int si, so, sv, sv_next, t, tf; bool fused, last; const AttnPairStep* pair; };
+// step s of a call in mode m (the launch-per-step loops; graph replay names its steps itself)
+static NoteStep note_step_at(const NoteDecArgs& a, const NoteStepMode& m, int s, bool fused, const AttnPairStep* pair = nullptr) {
+    const int i = m.parity_slots ? s & 1 : s, o = m.parity_slots ? (s + 1) & 1 : s + 1;
+    return {.si = i, .so = o, .sv = i, .sv_next = o, .t = s, .tf = a.tf_flags ? a.tf_flags[s] : 0, .fused = fused, .last = s + 1 == a.steps, .pair = pair};
+}
+
+static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, const NoteStepMode& m, const NoteStep& k) {
+    const int si = k.si, so = k.so, sv = k.sv, sv_next = k.sv_next, t = k.t, H2 = 2 * a.H, ldx = a.E + H2;
+    float* xs = a.x + (long)si * a.R * ldx;
+    float* qs = a.q + (long)sv * a.R * a.H;
+    float* os = a.o + (long)sv * a.R * 2 * H2;
+    a2s_attn_rows rows_v = {a.clip_order, a.clip_rank, a.row_until, a.n_clips > 0 ? a.n_clips : a.R, a.n_active ? a.n_active[t] : 0, t};
+    const a2s_attn_rows* rows = a.n_active ? &rows_v : nullptr;
+    int rc;
+    if (k.fused) {
         a2s_attn_deferred defer;
         defer.G = 0;
-        int rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, a.q + (long)sv * a.R * a.H, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2,
-                                        a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H, a.gt ? nullptr : a.n_done, a.R, a.attn_ws,
-                                        a.n_active ? &rows_v : nullptr, (a.gt && a.n_active && !t_base) ? &defer : nullptr);
+        rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, a.attw ? a.attw + (long)sv * a.R * a.T : nullptr, a.R, a.T, a.H,
+                                    a.gt ? nullptr : a.n_done, a.R, a.attn_ws, rows, (a.gt && a.n_active && !m.t_base) ? &defer : nullptr);
         if (rc) return rc;
-        const int nrows = note_step_rows(a, t_base ? -1 : t);
-        return a2s_note_step_fused_fwd(st, a, si, so, sv, sv_next, t, t_base, tf, last, nrows, nrows < a.R ? a.row_list : nullptr, defer.G > 0 ? &defer : nullptr);
+        const int nrows = note_step_rows(a, m.t_base ? -1 : t);
+        return a2s_note_step_fused_fwd(st, a, si, so, sv, sv_next, t, m.t_base, k.tf, k.last, nrows, nrows < a.R ? a.row_list : nullptr, defer.G > 0 ? &defer : nullptr);
     }
     // Rows the per-step products run on: all R, or -- late in a large call, when only a few leading clips still have an unfinished row --
     // the first m clips of every fused bar (batch = bars, row stride n_clips).  The elementwise kernels below keep running over all rows:
@@ -541,59 +557,50 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     if (a.m_active && a.n_clips > 0 && a2s_prefix_rows_ok(a.m_active[t], a.n_clips)) { gM = a.m_active[t]; gB = a.R / a.n_clips; gS = a.n_clips; }
     const float* hp = a.h + (long)si * a.R * H2;
     float* hq = a.h + (long)so * a.R * H2;
-    float* xs = a.x + (long)si * a.R * ldx;
-    float* qs = a.q + (long)sv * a.R * a.H;
-    float* os = a.o + (long)sv * a.R * 2 * H2;
-    int rc;
-    a2s_attn_rows rows_v = {a.clip_order, a.clip_rank, a.row_until, a.n_clips > 0 ? a.n_clips : a.R, a.n_active ? a.n_active[t] : 0, t};
-    const a2s_attn_rows* rows = a.n_active ? &rows_v : nullptr;
     // beam search (a2s_beam.hip): the rows are K slots of n_clips clips, every clip running, in the order of the call -- the K rows of a clip share
     // one pass over its key image and encoder rows (without this, row r would be read as clip r).  The kernels that fuse rows know no done
     // counter: with more than one slot the sweep runs until the host's poll ends the loop.
     const a2s_attn_rows rows_b = {nullptr, nullptr, nullptr, a.n_clips, a.n_clips, t};
-    if (beam) rows = &rows_b;
-    const int* attn_done = (a.gt || (beam && beam->K > 1)) ? nullptr : a.n_done;
+    if (m.beam) rows = &rows_b;
+    const int* attn_done = (a.gt || (m.beam && m.beam->K > 1)) ? nullptr : a.n_done;
     // alignment (a2s_align.hip): the step's weights go to the one-step slot, attn_align_rows reduces them into column t behind the attention launch
-    float* attw_s = align ? align->attw_step : (a.attw ? a.attw + (long)sv * a.R * a.T : nullptr);
+    float* attw_s = m.align ? m.align->attw_step : (a.attw ? a.attw + (long)sv * a.R * a.T : nullptr);
     float* q_left = nullptr;                  // the next step's query, where this step leaves it behind (a beam re-parents it with the state)
-    if (note_step_mid(a, t_base)) {
-        // round 6 (a2s_step.hip): the query of slot sv is already there (enqueue_query / the previous step, as on the few-row path); behind the
-        // attention ONE launch for the GRU cell (dec_gru_mid: gh, gi, gates) and ONE for the logits and the next step's query (dec_outq_mid), over
-        // the rows still running
-        // (pair: the sweep of this step has been launched for both staves at once -- only this staff's combine is left)
-        rc = pair ? attn_pair_combine(st, a, si, sv, *pair)
-                  : a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, attw_s, a.R, a.T, a.H, attn_done, a.R, a.attn_ws, rows);
+    // round 6 (a2s_step.hip), the mid-size kernels: the query of slot sv is already there (enqueue_query / the previous step, as on the few-row path)
+    const bool mid = note_step_mid(a, m.t_base);
+    if (!mid) {
+        // q = h W_h^T + b   (W = [W_h | W_e], W_h = first 2H columns of the (H, 4H) matrix)
+        rc = a2s_gemm_impl(st, gM, a.H, H2, 1.f, hp, H2, 1, a.attn_w, 1, 2 * H2, 0.f, qs, a.H, a.attn_b, 0, gB, gS * H2, 0, gS * a.H, 0, a.gemm_ws, a.gemm_ws_bytes);
         if (rc) return rc;
-        if (align) { rc = a2s_attn_align_rows_impl(st, attw_s, a.T, a.R, a.T, align->peak + t, align->weight + t, align->centroid + t, align->out_stride, attn_done, a.R); if (rc) return rc; }
-        const int nrows = note_step_rows(a, t);
-        rc = a2s_note_step_mid_gru(st, a, si, so, sv, last ? -1 : sv_next, nrows, nrows < a.R ? a.row_list : nullptr);
+        // gh = h W_hh^T + b_hh
+        rc = a2s_gemm_impl(st, gM, 3 * H2, H2, 1.f, hp, H2, 1, a.w_hh, 1, H2, 0.f, a.gh, 3 * H2, a.b_hh, 0, gB, gS * H2, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
         if (rc) return rc;
-        if (!last) q_left = a.q + (long)sv_next * a.R * a.H;
-    } else {
-    // q = h W_h^T + b   (W = [W_h | W_e], W_h = first 2H columns of the (H, 4H) matrix)
-    rc = a2s_gemm_impl(st, gM, a.H, H2, 1.f, hp, H2, 1, a.attn_w, 1, 2 * H2, 0.f, qs, a.H, a.attn_b, 0, gB, gS * H2, 0, gS * a.H, 0, a.gemm_ws, a.gemm_ws_bytes);
-    if (rc) return rc;
-    // gh = h W_hh^T + b_hh
-    rc = a2s_gemm_impl(st, gM, 3 * H2, H2, 1.f, hp, H2, 1, a.w_hh, 1, H2, 0.f, a.gh, 3 * H2, a.b_hh, 0, gB, gS * H2, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
-    if (rc) return rc;
-    // attention -> ctx into x[si][:, E:] and o[sv][:, 2H:]
-    rc = a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, attw_s, a.R, a.T, a.H, attn_done, a.R, a.attn_ws,
-                                rows);
-    if (rc) return rc;
-    if (align) { rc = a2s_attn_align_rows_impl(st, attw_s, a.T, a.R, a.T, align->peak + t, align->weight + t, align->centroid + t, align->out_stride, attn_done, a.R); if (rc) return rc; }
-    // gi = x W_ih^T + b_ih
-    rc = a2s_gemm_impl(st, gM, 3 * H2, ldx, 1.f, xs, ldx, 1, a.w_ih, 1, ldx, 0.f, a.gi, 3 * H2, a.b_ih, 0, gB, gS * ldx, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
-    if (rc) return rc;
-    // h' -> h[so] and o[sv][:, :2H]
-    rc = a2s_gru_gates_fwd_impl(st, a.gi, 3 * H2, a.gh, 3 * H2, hp, H2, hq, H2, os, 2 * H2,
-                                a.gates ? a.gates + (long)sv * a.R * 4 * H2 : nullptr, a.R, H2);
-    if (rc) return rc;
-    // logits = o W_out^T + b_out
-    rc = a2s_gemm_impl(st, gM, a.V, 2 * H2, 1.f, os, 2 * H2, 1, a.out_w, 1, 2 * H2, 0.f, a.logits, a.V, a.out_b, 0, gB, gS * 2 * H2, 0, gS * a.V, 0, a.gemm_ws, a.gemm_ws_bytes);
-    if (rc) return rc;
     }
-    if (beam) {
-        const a2s_beam_args& g = *beam;
+    // attention -> ctx into x[si][:, E:] and o[sv][:, 2H:]
+    // (pair, mid-size steps only: the sweep of this step has been launched for both staves at once -- only this staff's combine is left)
+    rc = (mid && k.pair) ? attn_pair_combine(st, a, si, sv, *k.pair)
+                         : a2s_attn_step_fwd_impl(st, a.keys, a.enc, qs, a.H, a.attn_v, xs + a.E, ldx, os + H2, 2 * H2, attw_s, a.R, a.T, a.H, attn_done, a.R, a.attn_ws, rows);
+    if (rc) return rc;
+    if (m.align) { rc = a2s_attn_align_rows_impl(st, attw_s, a.T, a.R, a.T, m.align->peak + t, m.align->weight + t, m.align->centroid + t, m.align->out_stride, attn_done, a.R); if (rc) return rc; }
+    if (mid) {
+        // ONE launch for the GRU cell (dec_gru_mid: gh, gi, gates) and ONE for the logits and the next step's query (dec_outq_mid), over the rows still running
+        const int nrows = note_step_rows(a, t);
+        rc = a2s_note_step_mid_gru(st, a, si, so, sv, k.last ? -1 : sv_next, nrows, nrows < a.R ? a.row_list : nullptr);
+        if (rc) return rc;
+        if (!k.last) q_left = a.q + (long)sv_next * a.R * a.H;
+    } else {
+        // gi = x W_ih^T + b_ih
+        rc = a2s_gemm_impl(st, gM, 3 * H2, ldx, 1.f, xs, ldx, 1, a.w_ih, 1, ldx, 0.f, a.gi, 3 * H2, a.b_ih, 0, gB, gS * ldx, 0, gS * 3 * H2, 0, a.gemm_ws, a.gemm_ws_bytes);
+        if (rc) return rc;
+        // h' -> h[so] and o[sv][:, :2H]
+        rc = a2s_gru_gates_fwd_impl(st, a.gi, 3 * H2, a.gh, 3 * H2, hp, H2, hq, H2, os, 2 * H2, a.gates ? a.gates + (long)sv * a.R * 4 * H2 : nullptr, a.R, H2);
+        if (rc) return rc;
+        // logits = o W_out^T + b_out
+        rc = a2s_gemm_impl(st, gM, a.V, 2 * H2, 1.f, os, 2 * H2, 1, a.out_w, 1, 2 * H2, 0.f, a.logits, a.V, a.out_b, 0, gB, gS * 2 * H2, 0, gS * a.V, 0, a.gemm_ws, a.gemm_ws_bytes);
+        if (rc) return rc;
+    }
+    if (m.beam) {
+        const a2s_beam_args& g = *m.beam;
         const BeamStepArgs bs = {a.logits, a.V, a.emb, a.x + (long)so * a.R * ldx, ldx, hq, H2, q_left, a.H, g.next_state, g.n_states, g.row_state, g.score, g.finished,
                                  g.done_count, g.token_hist, g.parent_hist, g.score_hist, g.probs_scratch, a.n_done, a.steps_exec, a.n_clips, g.K, a.V, a.E, t, a.steps,
                                  a.eos_id, g.pad_id};
@@ -606,10 +613,10 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, int si, int s
     f.drop = a.drop ? a.drop + (long)so * a.R * a.E : nullptr; f.inv_keep = a.inv_keep;
     f.argmax_out = a.argmax_out; f.am_bstride = a.am_bstride;
     f.eos_seen = a.eos_seen; f.lengths = a.lengths; f.n_done = a.n_done; f.steps_exec = a.steps_exec;
-    f.t_base = t_base;
+    f.t_base = m.t_base;
     f.row_until = a.n_active ? a.row_until : nullptr; f.n_clips = a.n_clips > 0 ? a.n_clips : a.R;
-    f.R = a.R; f.V = a.V; f.E = a.E; f.t = t; f.teacher_force = tf; f.eos_id = a.eos_id; f.max_t = a.steps;
-    if (grammar) return a2s_grammar_step_finalize_impl(st, f, *grammar);       // the constrained choice in the place of the argmax (a2s_grammar.hip)
+    f.R = a.R; f.V = a.V; f.E = a.E; f.t = t; f.teacher_force = k.tf; f.eos_id = a.eos_id; f.max_t = a.steps;
+    if (m.grammar) return a2s_grammar_step_finalize_impl(st, f, *m.grammar);       // the constrained choice in the place of the argmax (a2s_grammar.hip)
     return a2s_note_step_finalize_impl(st, f);
 }
 
@@ -618,19 +625,20 @@ __global__ void advance_counter(int* p, int inc) { if (threadIdx.x == 0 && block
 // Greedy decode as a replayed hipGraph: the state ping-pongs between two slots (nothing is kept for a backward pass), the step
 // index comes from a device counter, so ONE captured chunk of `chunk` steps serves the whole sequence; the host replays it and
 // looks at the done counter after every replay.  Removes the per-launch host cost that dominates small-batch decoding.
-static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar = nullptr) {
+static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, const NoteStepMode& m, int* steps_done) {
     int chunk = a.poll > 0 ? a.poll : 16;
     if (chunk & 1) ++chunk;                                   // even: the state is back in slot 0 after every replay
     hipError_t e = hipMemsetAsync(a.t_base, 0, sizeof(int), st);
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "greedy graph memset: %s", hipGetErrorString(e));
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    const bool fused = !grammar && note_step_fusable(a);
+    const bool fused = m.few_row && note_step_fusable(a);
     int rc = fused ? enqueue_query(st, a, 0, 0) : A2S_OK;     // the very first query; every later one is left behind by the previous step
     if (rc) return rc;
     e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
-    for (int j = 0; j < chunk && rc == A2S_OK; ++j) rc = enqueue_note_step(st, a, j & 1, (j + 1) & 1, 0, j, a.t_base, 0, fused, 0, false, nullptr, grammar);
+    for (int j = 0; j < chunk && rc == A2S_OK; ++j)      // (every query and saved row in slot 0, no step the last: the chunk is replayed)
+        rc = enqueue_note_step(st, a, m, {.si = j & 1, .so = (j + 1) & 1, .sv = 0, .sv_next = 0, .t = j, .tf = 0, .fused = fused, .last = false, .pair = nullptr});
     if (rc == A2S_OK) hipLaunchKernelGGL(advance_counter, dim3(1), dim3(64), 0, st, a.t_base, chunk);
     e = hipStreamEndCapture(st, &graph);
     if (rc != A2S_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -654,45 +662,41 @@ static int note_decoder_greedy_graph(hipStream_t st, const NoteDecArgs& a, int* 
     return A2S_OK;
 }
 
-// Tail steps on the few-row kernels write only the rows still running.  What the backward pass reads of the others (operands of its
-// weight-gradient products over all rows and steps, the saved gates) must be finite: everything behind slot 0 starts as zeros
-// (~6 GB per training step at B = 256, ~1.3 ms; issued here and not by the Python host: see engine.Engine._decode_staff).
-static int note_decoder_zero_fill(hipStream_t st, const NoteDecArgs& a) {
-    if (!(a.row_list && a.n_rows_active && a.steps > 0)) return A2S_OK;
+// What the backward pass reads of rows and steps a call never writes (operands of its weight-gradient products, the saved gates) must be finite:
+// everything behind slot 0 starts as zeros.  The loops need it when tail steps on the few-row kernels write only the rows still running, the persistent
+// launch (a2s_dec_persist.hip) always (~6 GB per training step at B = 256, ~1.3 ms; issued here and not by the Python host: engine.Engine._decode_staff).
+int a2s_note_decoder_zero_unwritten(hipStream_t st, const NoteDecArgs& a, const char* who) {
     const long H2 = 2L * a.H, ldx = a.E + H2, n = a.steps, R = a.R;
     hipError_t e = hipMemsetAsync(a.h + R * H2, 0, sizeof(float) * n * R * H2, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.x + R * ldx, 0, sizeof(float) * n * R * ldx, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.q, 0, sizeof(float) * n * R * a.H, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.o, 0, sizeof(float) * n * R * 2 * H2, st);
     if (e == hipSuccess && a.gates) e = hipMemsetAsync(a.gates, 0, sizeof(float) * n * R * 4 * H2, st);
-    if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder memset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "%s memset: %s", who, hipGetErrorString(e));
     return A2S_OK;
 }
+static bool note_decoder_tail_rows(const NoteDecArgs& a) { return a.row_list && a.n_rows_active && a.steps > 0; }
 
-// grammar: the constrained greedy decoder (a2s_note_decoder_fwd_grammar_impl) -- the launch-per-step loop only, every step's epilogue the grammar kernel
-static int note_decoder_fwd_loop(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar) {
-    // few clips: one persistent launch for the whole call (a2s_dec_persist.hip)
-    if (!grammar && a2s_note_decoder_fwd_persist_ok(a)) return a2s_note_decoder_fwd_persist(st, a, steps_done);
-    // stream capture is not allowed on the legacy default stream: callers that want the graph path run on a created stream
-    if (!a.gt && a.use_graph && a.t_base && !a.gates && !a.attw && !a.drop && st != nullptr) return note_decoder_greedy_graph(st, a, steps_done, grammar);
-    { const int rc0 = note_decoder_zero_fill(st, a); if (rc0) return rc0; }
-    int s = 0;
-    // The few-row step kernels take over as soon as the rows still running fit them (the whole call when it is small; the tail of a large
-    // training call otherwise: the handful of full-length rows then decode in 4 launches per step instead of 12 over every row).  The
-    // first fused step finds no query left behind by a fused predecessor: it is computed for all rows first.
-    bool prev_q = false;                     // did the previous step leave this step's query behind?
+// THE launch-per-step loop: the plain, the grammar, the align and the beam call all run it and differ in the mode alone.  The few-row step kernels
+// take over as soon as the rows still running fit them (the whole call when it is small, else the tail of a large training call: its handful of full-length
+// rows then decode in 4 launches per step instead of 12 over every row).  A fused or mid-size step finds its query left behind by its predecessor; the
+// first such step finds none: it is computed for all rows first.
+static int note_decoder_run(hipStream_t st, const NoteDecArgs& a, const NoteStepMode& m, int* steps_done) {
+    if (note_decoder_tail_rows(a)) { const int rc = a2s_note_decoder_zero_unwritten(st, a, "note_decoder"); if (rc) return rc; }
     const bool mid = note_step_mid(a, nullptr);
+    bool prev_q = false;                     // did the previous step leave this step's query behind?
+    int s = 0;
     for (; s < a.steps; ++s) {
-        const bool fused = !grammar && note_step_fusable(a, s);
-        if ((fused || mid) && !prev_q) { int rc = enqueue_query(st, a, s, s); if (rc) return rc; }
-        prev_q = fused || mid;
-        int rc = enqueue_note_step(st, a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, fused, s + 1, s + 1 == a.steps, nullptr, grammar);
+        const NoteStep k = note_step_at(a, m, s, m.few_row && note_step_fusable(a, s, m.fused_rows_limit));
+        if ((k.fused || mid) && !prev_q) { const int rc = enqueue_query(st, a, k.si, k.sv); if (rc) return rc; }
+        prev_q = k.fused || mid;
+        const int rc = enqueue_note_step(st, a, m, k);
         if (rc) return rc;
         if (!a.gt && a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
             int done = 0;   // greedy only: one small D2H + sync per `poll` steps
             hipError_t e = hipMemcpyAsync(&done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder poll: %s", hipGetErrorString(e));
+            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "%s poll: %s", m.label, hipGetErrorString(e));
             if (done >= a.R) { ++s; break; }
         }
     }
@@ -700,7 +704,18 @@ static int note_decoder_fwd_loop(hipStream_t st, const NoteDecArgs& a, int* step
     return A2S_OK;
 }
 
-int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_done) { return note_decoder_fwd_loop(st, a, steps_done, nullptr); }
+// The plain and the grammar entry: the two shortcuts around the loop, else the loop.  grammar: the constrained greedy decoder
+// (a2s_note_decoder_fwd_grammar_impl) -- never the persistent launch or the few-row kernels, every step's epilogue the grammar kernel.
+static int note_decoder_fwd(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar) {
+    // few clips: one persistent launch for the whole call (a2s_dec_persist.hip)
+    if (!grammar && a2s_note_decoder_fwd_persist_ok(a)) return a2s_note_decoder_fwd_persist(st, a, steps_done);
+    // stream capture is not allowed on the legacy default stream: callers that want the graph path run on a created stream
+    if (!a.gt && a.use_graph && a.t_base && !a.gates && !a.attw && !a.drop && st != nullptr)
+        return note_decoder_greedy_graph(st, a, {.grammar = grammar, .t_base = a.t_base, .few_row = !grammar}, steps_done);
+    return note_decoder_run(st, a, {.grammar = grammar, .few_row = !grammar}, steps_done);
+}
+
+int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_done) { return note_decoder_fwd(st, a, steps_done, nullptr); }
 
 // Greedy decoding under a token grammar: row r starts in row_state[r] and walks the table with every token it emits.
 int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, const a2s_grammar_ref& g, int* steps_done) {
@@ -708,11 +723,11 @@ int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, cons
     A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list, "note_decoder_fwd_grammar: inference only (training buffers or row bookkeeping given)");
     A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_grammar: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
     A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_grammar: null bookkeeping or output buffers");
-    return note_decoder_fwd_loop(st, a, steps_done, &g);
+    return note_decoder_fwd(st, a, steps_done, &g);
 }
 
-// Decoding with the audio alignment of every step: the launch-per-step loop of note_decoder_fwd_loop -- greedy,
-// greedy under a grammar, or teacher-forced in evaluation mode -- with the step's attention weights kept for one step and reduced into column t of
+// Decoding with the audio alignment of every step: the launch-per-step loop -- greedy, greedy under a
+// grammar, or teacher-forced in evaluation mode -- with the step's attention weights kept for one step and reduced into column t of
 // the alignment arrays.  Never the persistent, few-row or graph paths: their attention does not write the weights of an inference step.
 int a2s_note_decoder_fwd_align_impl(hipStream_t st, const NoteDecArgs& a, const a2s_align_args& g, int* steps_done) {
     A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list && !a.m_active && !a.clip_order && !a.row_until,
@@ -726,23 +741,7 @@ int a2s_note_decoder_fwd_align_impl(hipStream_t st, const NoteDecArgs& a, const 
     const bool with_grammar = g.next_state || g.n_states || g.row_state;
     const a2s_grammar_ref gr = {g.next_state, g.n_states, g.row_state};
     A2S_REQUIRE(!with_grammar || a2s_grammar_ref_ok(gr, a.R, a.V), "note_decoder_fwd_align: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
-    const bool mid = note_step_mid(a, nullptr);
-    int s = 0;
-    for (; s < a.steps; ++s) {
-        if (mid && s == 0) { const int rc = enqueue_query(st, a, 0, 0); if (rc) return rc; }       // every later query is left behind by the previous step
-        const int rc = enqueue_note_step(st, a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, false, s + 1, s + 1 == a.steps, nullptr,
-                                         with_grammar ? &gr : nullptr, nullptr, &g);
-        if (rc) return rc;
-        if (!a.gt && a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
-            int done = 0;
-            hipError_t e = hipMemcpyAsync(&done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_align poll: %s", hipGetErrorString(e));
-            if (done >= a.R) { ++s; break; }
-        }
-    }
-    if (steps_done) *steps_done = s;
-    return A2S_OK;
+    return note_decoder_run(st, a, {.grammar = with_grammar ? &gr : nullptr, .align = &g, .label = "note_decoder_fwd_align"}, steps_done);
 }
 
 // Beam search over one greedy call: K slots per clip as extra rows, the launch-per-step loop with the beam
@@ -758,24 +757,28 @@ int a2s_note_decoder_fwd_beam_impl(hipStream_t st, const NoteDecArgs& a, const a
     A2S_REQUIRE(a.steps >= 0 && a.n_done && a.logits && a.probs && a.h && a.x && a.q && a.o, "note_decoder_fwd_beam: null bookkeeping or output buffers");
     int rc = a2s_beam_init_impl(st, g, a.n_done, a.n_clips, a.steps);
     if (rc) return rc;
-    const bool mid = note_step_mid(a, nullptr);
     int s = 0;
-    for (; s < a.steps; ++s) {
-        if (mid && s == 0) { rc = enqueue_query(st, a, 0, 0); if (rc) return rc; }     // every later query is left behind by the previous step
-        rc = enqueue_note_step(st, a, s & 1, (s + 1) & 1, s & 1, s, nullptr, 0, false, (s + 1) & 1, s + 1 == a.steps, nullptr, nullptr, &g);
-        if (rc) return rc;
-        if (a.poll > 0 && ((s + 1) % a.poll == 0) && s + 1 < a.steps) {
-            int done = 0;
-            hipError_t e = hipMemcpyAsync(&done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_beam poll: %s", hipGetErrorString(e));
-            if (done >= a.R) { ++s; break; }
-        }
-    }
+    rc = note_decoder_run(st, a, {.beam = &g, .parity_slots = true, .label = "note_decoder_fwd_beam"}, &s);
+    if (rc) return rc;
     const BeamBackArgs bk = {g.score, g.token_hist, g.parent_hist, g.probs_scratch, a.probs, a.probs_bstride, g.ids_out, (long)a.steps, g.lengths_out, g.score_out,
                              a.steps_exec, g.alpha, a.n_clips, g.K, a.V, a.steps, a.eos_id, g.pad_id};
     if (a.steps > 0) { rc = a2s_beam_backtrack_impl(st, bk); if (rc) return rc; }
     if (steps_done) *steps_done = s;
+    return A2S_OK;
+}
+
+// The two events of the pair loops (forward here, reverse in a2s_bwd.hip): the issuing thread's own -- two host threads run pair loops for different
+// clip groups at once -- and one pair per device.  Looked up once per pair call; never destroyed (thread-local events at library unload: its own hazard).
+int a2s_pair_events(const char* who, hipEvent_t** ev_out) {
+    struct Pair { hipEvent_t ev[2]; };
+    static thread_local std::vector<Pair> pairs;              // index = device ordinal
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "%s: hipGetDevice: %s", who, hipGetErrorString(e));
+    if ((size_t)dev >= pairs.size()) pairs.resize(dev + 1, Pair{{nullptr, nullptr}});
+    for (int k = 0; k < 2; ++k)
+        if (!pairs[dev].ev[k]) { e = hipEventCreateWithFlags(&pairs[dev].ev[k], hipEventDisableTiming); if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "%s: hipEventCreate: %s", who, hipGetErrorString(e)); }
+    *ev_out = pairs[dev].ev;
     return A2S_OK;
 }
 
@@ -796,11 +799,12 @@ int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const NoteDec
         int rc = a2s_note_decoder_fwd_impl(su, au, done_u);
         return rc ? rc : a2s_note_decoder_fwd_impl(sl, al, done_l);
     }
-    static thread_local hipEvent_t ev[2] = {nullptr, nullptr};
+    // (from here on: the few-row kernels take over later than in a single-staff call, see NoteStepMode)
+    const NoteStepMode m = {.few_row = true, .fused_rows_limit = a2s_attn_pair_fused_rows(), .label = "note_decoder_fwd_pair"};
+    hipEvent_t* ev = nullptr;
+    { const int rc = a2s_pair_events(m.label, &ev); if (rc) return rc; }
     for (int k = 0; k < 2; ++k)
-        if (!ev[k]) { const hipError_t e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming); if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_pair: hipEventCreate: %s", hipGetErrorString(e)); }
-    const PairRowsLimit limit(a2s_attn_pair_fused_rows());
-    for (int k = 0; k < 2; ++k) { const int rc = note_decoder_zero_fill(sts[k], *as[k]); if (rc) return rc; }
+        if (note_decoder_tail_rows(*as[k])) { const int rc = a2s_note_decoder_zero_unwritten(sts[k], *as[k], "note_decoder"); if (rc) return rc; }
     bool prev_q[2] = {false, false};
     const int nmax = au.steps > al.steps ? au.steps : al.steps;
     for (int s = 0; s < nmax; ++s) {
@@ -808,26 +812,21 @@ int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const NoteDec
         for (int k = 0; k < 2; ++k) {
             in[k] = s < as[k]->steps;
             if (!in[k]) continue;
-            fused[k] = note_step_fusable(*as[k], s);
+            fused[k] = note_step_fusable(*as[k], s, m.fused_rows_limit);
             if (!prev_q[k]) { const int rc = enqueue_query(sts[k], *as[k], s, s); if (rc) return rc; }       // (every step here is a fused or a mid-size one)
             prev_q[k] = true;
         }
         AttnPairStep p = {pair_order, pair_rank, au.n_clips, pair_n_active[s], s, 1, au.T};
         const bool joint = in[0] && in[1] && !fused[0] && !fused[1] && p.n_active > 0 && au.n_active[s] > 0 && al.n_active[s] > 0;
         if (joint) {
-            hipError_t e = hipEventRecord(ev[1], sl);                       // the lower staff's query of this step
-            if (e == hipSuccess) e = hipStreamWaitEvent(su, ev[1], 0);
-            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_pair: event: %s", hipGetErrorString(e));
-            const int rc = attn_pair_sweep(su, au, al, s, p);
+            int rc = a2s_record_wait(ev[1], sl, su, m.label);                // the lower staff's query of this step
+            if (rc == A2S_OK) rc = attn_pair_sweep(su, au, al, s, p);
+            if (rc == A2S_OK) rc = a2s_record_wait(ev[0], su, sl, m.label);
             if (rc) return rc;
-            e = hipEventRecord(ev[0], su);
-            if (e == hipSuccess) e = hipStreamWaitEvent(sl, ev[0], 0);
-            if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "note_decoder_fwd_pair: event: %s", hipGetErrorString(e));
         }
         for (int k = 0; k < 2; ++k) {
             if (!in[k]) continue;
-            const NoteDecArgs& a = *as[k];
-            const int rc = enqueue_note_step(sts[k], a, s, s + 1, s, s, nullptr, a.tf_flags ? a.tf_flags[s] : 0, fused[k], s + 1, s + 1 == a.steps, joint ? &p : nullptr);
+            const int rc = enqueue_note_step(sts[k], *as[k], m, note_step_at(*as[k], m, s, fused[k], joint ? &p : nullptr));
             if (rc) return rc;
         }
     }

@@ -313,6 +313,17 @@ def _dist_world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 0     # 0 = no process group
 
 
+# the ten weight fields of a2s_note_dec_args and the reference state_dict names (behind the decoder's prefix) that fill them
+_NOTE_DEC_WEIGHTS = (("attn_w", ".attn.attn.weight"), ("attn_b", ".attn.attn.bias"), ("attn_v", ".attn.v.weight"), ("w_ih", ".gru.weight_ih_l0"),
+                     ("w_hh", ".gru.weight_hh_l0"), ("b_ih", ".gru.bias_ih_l0"), ("b_hh", ".gru.bias_hh_l0"), ("out_w", ".out.weight"),
+                     ("out_b", ".out.bias"), ("emb", ".embedding.weight"))
+
+
+def _set_note_dec_weights(a, S, prefix):
+    for field, name in _NOTE_DEC_WEIGHTS:
+        setattr(a, field, S[prefix + name].data_ptr())
+
+
 class Engine:
     def __init__(self, cfg, sync_bn=False):
         self.cfg = cfg
@@ -573,11 +584,8 @@ class Engine:
                                    1.0 / (1.0 - drop_p) if drop is not None else 1.0), "a2s_embed_rows")
         flags = (C.c_uint8 * max(n, 1))(*([int(f) for f in tf_flags] if tf_flags is not None else [0] * n))
         a = hip.NoteDecArgs()
-        for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_b", S[prefix + ".attn.attn.bias"]),
-                        ("attn_v", S[prefix + ".attn.v.weight"]), ("w_ih", S[prefix + ".gru.weight_ih_l0"]),
-                        ("w_hh", S[prefix + ".gru.weight_hh_l0"]), ("b_ih", S[prefix + ".gru.bias_ih_l0"]),
-                        ("b_hh", S[prefix + ".gru.bias_hh_l0"]), ("out_w", S[prefix + ".out.weight"]), ("out_b", S[prefix + ".out.bias"]),
-                        ("emb", S[prefix + ".embedding.weight"]), ("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q),
+        _set_note_dec_weights(a, S, prefix)
+        for name, t in (("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q),
                         ("gates", gates), ("attw", attw), ("o", o), ("gh", gh), ("gi", gi), ("logits", logits),
                         ("argmax_out", ids), ("eos_seen", eos_seen), ("lengths", lengths), ("n_done", n_done), ("steps_exec", steps_exec), ("drop", drop), ("attn_ws", attn_ws), ("gemm_ws", gemm_ws), ("t_base", t_base),
                         ("clip_order", active and active["order"]), ("clip_rank", active and active["rank"]),
@@ -681,11 +689,8 @@ class Engine:
         g, bt = hip.beam_buffers(B, K, max_steps, V, dev, PAD, table=grammar.device_table(dev) if grammar is not None else None,
                                  start=grammar.start if grammar is not None else 0, alpha=self.beam_length_penalty)
         a = hip.NoteDecArgs()
-        for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_b", S[prefix + ".attn.attn.bias"]),
-                        ("attn_v", S[prefix + ".attn.v.weight"]), ("w_ih", S[prefix + ".gru.weight_ih_l0"]),
-                        ("w_hh", S[prefix + ".gru.weight_hh_l0"]), ("b_ih", S[prefix + ".gru.bias_ih_l0"]),
-                        ("b_hh", S[prefix + ".gru.bias_hh_l0"]), ("out_w", S[prefix + ".out.weight"]), ("out_b", S[prefix + ".out.bias"]),
-                        ("emb", S[prefix + ".embedding.weight"]), ("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q), ("o", o), ("gh", gh),
+        _set_note_dec_weights(a, S, prefix)
+        for name, t in (("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q), ("o", o), ("gh", gh),
                         ("gi", gi), ("logits", logits), ("n_done", n_done), ("steps_exec", steps_exec), ("attn_ws", attn_ws), ("gemm_ws", gemm_ws)):
             setattr(a, name, t.data_ptr() if t is not None else None)
         a.gemm_ws_bytes = gemm_ws.numel() * 4
