@@ -366,6 +366,31 @@ int a2s_align_launches(void);
  * nothing.  One launch per call; a2s_render_launches: launches so far (proof of the path). */
 int a2s_render_notes(void* stream, const int* programs, int rows_per_clip, int n_samples, float* wave, long wave_bstride, int B);
 int a2s_render_launches(void);
+
+/* ---- transposition augmentation of a training batch (csrc/a2s_augment.hip).  Both entry points take borrowed device pointers
+ * and a stream; they allocate nothing, do not synchronise and read nothing back.
+ * a2s_transpose_targets respells the targets of B clips in place, one workgroup per clip.  Tables (device, int32, piano_a2s_amd/kern_transpose.py):
+ * new_key (13, 14): [s + 6][key class] -> key class; interval (13, 14): [s + 6][key class] -> row of token_map; token_map (n_rows, V): token id ->
+ * token id, or -1 where the transposed pitch has no symbol.  Per clip b: semitones[b] = s in -6 .. 6 (int32) and detune[b] (float32, in bins); key
+ * (B, bars), upper (B, bars, U), lower (B, bars, L): int64, contiguous.  A bar's row is interval[s + 6][key[b][bar]]: the bars of a clip share s and may
+ * differ in their key.  A clip is NOT REPRESENTABLE when any of its tokens maps to -1, or s, a key, a row or a token id is out of range; such a clip
+ * keeps its tokens and keys.  Otherwise every token and key of the clip is rewritten through the tables.  In both cases
+ *     eff_bins[b] = float(bins_per_semitone * s) + detune[b]  (representable: one fp32 add)   |   detune[b]  (not representable),
+ * and counters[0 .. 2] (device int32; global atomic adds) grow by: clips seen, clips transposed (s != 0 and representable), clips kept because not
+ * representable.  Null pointers, B < 0, n_rows < 1, V < 1, bars < 1, U < 1, L < 1, bins_per_semitone < 1: A2S_ERR_ARG, nothing is launched; B = 0
+ * returns 0 and launches nothing.
+ * a2s_shift_bins shifts the feature rows, out of place: x, y = (B, rows, F) float32, contiguous, x != y; with n = eff_bins[b] (read on the device),
+ * m = floor(n), a = n - m:
+ *     y[b][t][j] = (1 - a) * x[b][t][j - m] + a * x[b][t][j - m - 1],   x taken as 0 outside [0, F).
+ * a == 0 writes x[b][t][j - m] itself (bit for bit; n == 0: a copy); |n| >= F + 1 or n not finite writes zeros.  Nothing outside the B * rows * F
+ * floats of y is written and nothing outside those of x is read.  16-byte stores when F % 4 == 0 and y is 16-byte aligned, 4-byte stores otherwise.
+ * Null pointers, x == y, B < 0 or > 65535, rows < 1, F < 1, rows * F >= 2^31: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches nothing.
+ * One launch per call each; a2s_augment_launches: launches of the two so far (proof of the path). */
+int a2s_transpose_targets(void* stream, const int* new_key, const int* interval, const int* token_map, int n_rows, int V, const int* semitones,
+                          const float* detune, long long* key, long long* upper, long long* lower, int bars, int U, int L, int bins_per_semitone,
+                          float* eff_bins, int* counters, int B);
+int a2s_shift_bins(void* stream, const float* x, float* y, const float* eff_bins, int B, int rows, int F);
+int a2s_augment_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

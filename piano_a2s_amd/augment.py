@@ -1,0 +1,102 @@
+"""Transposition augmentation of a training batch on the device: per clip a whole number of semitones s and a detuning of
+delta feature bins are drawn on the host; csrc/a2s_augment.hip respells the targets (kern_transpose's tables) and shifts the feature rows by
+bins_per_semitone * s + delta bins.  A clip whose score cannot be respelled keeps its score and key and is only detuned.
+
+The draws come from the object's own numpy Generator: Python's `random`, numpy's global state and torch's generators never advance (the
+teacher-forcing draw protocol of the training step depends on them)."""
+import numpy as np
+import torch
+
+from piano_a2s_amd import kern_transpose
+from piano_a2s_amd.abi import A2SError
+
+MAX_SEMITONES = kern_transpose.MAX_SEMITONES
+MAX_DETUNE_BINS = 2.5
+
+
+def check_range(max_semitones, detune_bins):
+    """(K, D) as numbers, or ValueError: K a whole number in 0 .. 6, 0 <= D <= 2.5."""
+    try:
+        K, D = int(max_semitones), float(detune_bins)
+        whole = K == float(max_semitones)
+    except (TypeError, ValueError):
+        raise ValueError(f"--transpose_augment / --detune_bins must be numbers (got {max_semitones!r}, {detune_bins!r})") from None
+    if not whole or not 0 <= K <= MAX_SEMITONES:
+        raise ValueError(f"--transpose_augment must be a whole number in 0 .. {MAX_SEMITONES} (got {max_semitones!r})")
+    if not 0.0 <= D <= MAX_DETUNE_BINS:
+        raise ValueError(f"--detune_bins must be in 0 .. {MAX_DETUNE_BINS} (got {detune_bins!r})")
+    return K, D
+
+
+class TransposeAugment:
+    """cfg: the transcription module's configuration (freq_bins); max_semitones K in 0 .. 6 and detune_bins D in [0, 2.5]: s uniform in -K .. K,
+    delta uniform in [-D, D] per clip; seed: the run's; device: where the batches live.  bins_per_octave: the features' resolution."""
+
+    def __init__(self, cfg, max_semitones, detune_bins, seed, device, bins_per_octave=60, rank=0):
+        self.K, self.D = check_range(max_semitones, detune_bins)
+        bpo = int(bins_per_octave)
+        if bpo != bins_per_octave or bpo < 12 or bpo % 12:
+            raise ValueError(f"transposition augmentation needs a whole number of feature bins per semitone: bins_per_octave = {bins_per_octave!r} is no multiple of 12")
+        self.bins_per_semitone = bpo // 12
+        self.freq_bins = int(cfg["freq_bins"])
+        if self.freq_bins < bpo or self.freq_bins % self.bins_per_semitone:
+            raise ValueError(f"transposition augmentation: freq_bins = {self.freq_bins} is not a whole number of semitones of {self.bins_per_semitone} bins "
+                             f"spanning at least one octave")
+        self.seed, self.rank = int(seed), int(rank)
+        self.device = torch.device(device)
+        self._rng = None
+        self._tables = None
+        self._counters = None
+        self.reseed(0, self.rank)
+
+    # ------------------------------------------------------------------ host side
+    def reseed(self, epoch, rank=None):
+        """The draws that follow are a function of (seed, rank, epoch) alone."""
+        if rank is not None:
+            self.rank = int(rank)
+        self._rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.seed & 0xFFFFFFFFFFFFFFFF, self.rank, int(epoch or 0)])))
+
+    def draw(self, B):
+        """(semitones (B,) int32, detune (B,) float32) of the next batch; host only."""
+        s = self._rng.integers(-self.K, self.K + 1, size=B).astype(np.int32)
+        d = self._rng.uniform(-self.D, self.D, size=B).astype(np.float32) if self.D > 0 else np.zeros(B, dtype=np.float32)
+        return s, d
+
+    # ------------------------------------------------------------------ device side
+    def _device_state(self):
+        if self._tables is None:
+            self._tables = tuple(torch.from_numpy(np.array(t)).to(self.device) for t in kern_transpose.tables())
+            self._counters = torch.zeros(3, dtype=torch.int32, device=self.device)
+        return self._tables
+
+    def apply(self, batch, semitones, detune):
+        """The batch (features (B, 1, T, F) float32, ts, key (B, bars), upper (B, bars, U), upper lengths, lower (B, bars, L), ... on the device) under
+        the given draws: two launches on the current stream.  Returns the batch with a NEW feature tensor; key, upper and lower are the same tensors,
+        rewritten in place."""
+        from piano_a2s_amd import hip
+        batch = list(batch)
+        x, key, upper, lower = batch[0], batch[2], batch[3], batch[5]
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[-1] != self.freq_bins:
+            raise A2SError(f"TransposeAugment: expects features (B, 1, T, {self.freq_bins}), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        B = x.shape[0]
+        if len(semitones) != B or len(detune) != B:
+            raise A2SError(f"TransposeAugment: {len(semitones)} / {len(detune)} draws for {B} clips")
+        new_key, interval, token_map = self._device_state()
+        # pinned staging from the caching host allocator: it keeps a block until the copy that reads it has run
+        s_dev = torch.from_numpy(np.ascontiguousarray(semitones, dtype=np.int32)).pin_memory().to(self.device, non_blocking=True)
+        d_dev = torch.from_numpy(np.ascontiguousarray(detune, dtype=np.float32)).pin_memory().to(self.device, non_blocking=True)
+        eff = torch.empty(B, dtype=torch.float32, device=self.device)
+        hip.transpose_targets(new_key, interval, token_map, s_dev, d_dev, key, upper, lower, self.bins_per_semitone, eff, self._counters)
+        batch[0] = hip.shift_bins(x.contiguous(), eff)          # one fresh tensor per batch, as the un-augmented path's input is
+        return batch
+
+    def __call__(self, batch):
+        s, d = self.draw(batch[0].shape[0])
+        return self.apply(batch, s, d)
+
+    def counts(self):
+        """{clips, transposed, not_representable} so far: one device-to-host copy."""
+        if self._counters is None:
+            return dict(clips=0, transposed=0, not_representable=0)
+        c = self._counters.tolist()
+        return dict(clips=c[0], transposed=c[1], not_representable=c[2])

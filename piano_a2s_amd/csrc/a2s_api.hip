@@ -254,6 +254,16 @@ int a2s_render_notes(void* stream, const int* programs, int rows_per_clip, int n
     return a2s_render_notes_impl(ST, programs, rows_per_clip, n_samples, wave, wave_bstride, B);
 }
 int a2s_render_launches(void) { return a2s_render_launches_impl(); }
+int a2s_transpose_targets(void* stream, const int* new_key, const int* interval, const int* token_map, int n_rows, int V, const int* semitones,
+                          const float* detune, long long* key, long long* upper, long long* lower, int bars, int U, int L, int bins_per_semitone,
+                          float* eff_bins, int* counters, int B) {
+    return a2s_transpose_targets_impl(ST, new_key, interval, token_map, n_rows, V, semitones, detune, key, upper, lower, bars, U, L, bins_per_semitone, eff_bins,
+                                      counters, B);
+}
+int a2s_shift_bins(void* stream, const float* x, float* y, const float* eff_bins, int B, int rows, int F) {
+    return a2s_shift_bins_impl(ST, x, y, eff_bins, B, rows, F);
+}
+int a2s_augment_launches(void) { return a2s_augment_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

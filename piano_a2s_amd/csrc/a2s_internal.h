@@ -232,6 +232,13 @@ int a2s_note_decoder_fwd_align_impl(hipStream_t st, const a2s_note_dec_args& a, 
 int a2s_render_notes_impl(hipStream_t st, const int* programs, int rows_per_clip, int n_samples, float* wave, long wave_bstride, int B);
 int a2s_render_launches_impl(void);
 
+// ---- a2s_augment.hip
+int a2s_transpose_targets_impl(hipStream_t st, const int* new_key, const int* interval, const int* token_map, int n_rows, int V, const int* semitones,
+    const float* detune, long long* key, long long* upper, long long* lower, int bars, int U, int L, int bins_per_semitone, float* eff_bins, int* counters,
+    int B);
+int a2s_shift_bins_impl(hipStream_t st, const float* x, float* y, const float* eff_bins, int B, int rows, int F);
+int a2s_augment_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -288,6 +288,62 @@ def render_launches():
     return int(lib().a2s_render_launches())
 
 
+def _need(cond, fn, arg, what):
+    if not cond:
+        raise A2SError(f"{fn}: `{arg}` {what}")
+
+
+def transpose_targets(new_key, interval, token_map, semitones, detune, key, upper, lower, bins_per_semitone, eff_bins, counters):
+    """a2s_transpose_targets: the tables of kern_transpose.tables() on the device (int32), the draws semitones (B,) int32 and detune (B,) float32, the
+    batch's key (B, bars), upper (B, bars, U) and lower (B, bars, L) int64, rewritten IN PLACE where the clip is representable; eff_bins (B,) float32
+    receives the feature shift of every clip, counters (3,) int32 grow by [clips, transposed, not representable]."""
+    fn = "transpose_targets"
+    for name, t, dtype in (("new_key", new_key, torch.int32), ("interval", interval, torch.int32), ("token_map", token_map, torch.int32),
+                           ("semitones", semitones, torch.int32), ("detune", detune, torch.float32), ("key", key, torch.int64), ("upper", upper, torch.int64),
+                           ("lower", lower, torch.int64), ("eff_bins", eff_bins, torch.float32), ("counters", counters, torch.int32)):
+        _need(torch.is_tensor(t) and t.dtype == dtype, fn, name, f"must be a {dtype} tensor")
+        _need(t.is_contiguous(), fn, name, "must be contiguous")
+    _need(token_map.dim() == 2, fn, "token_map", "must be (rows, V)")
+    _need(tuple(new_key.shape) == (13, 14), fn, "new_key", "must be (13, 14)")
+    _need(tuple(interval.shape) == (13, 14), fn, "interval", "must be (13, 14)")
+    _need(key.dim() == 2, fn, "key", "must be (B, bars)")
+    B, bars = key.shape
+    _need(upper.dim() == 3 and tuple(upper.shape[:2]) == (B, bars), fn, "upper", f"must be ({B}, {bars}, U) as `key` says")
+    _need(lower.dim() == 3 and tuple(lower.shape[:2]) == (B, bars), fn, "lower", f"must be ({B}, {bars}, L) as `key` says")
+    for name, t in (("semitones", semitones), ("detune", detune), ("eff_bins", eff_bins)):
+        _need(tuple(t.shape) == (B,), fn, name, f"must have one element per clip ({B})")
+    _need(counters.numel() == 3, fn, "counters", "must have 3 elements")
+    if B == 0:
+        return
+    check(lib().a2s_transpose_targets(stream(), _p(new_key), _p(interval), _p(token_map), token_map.shape[0], token_map.shape[1], _p(semitones), _p(detune),
+                                      _p(key), _p(upper), _p(lower), bars, upper.shape[2], lower.shape[2], int(bins_per_semitone), _p(eff_bins), _p(counters), B),
+          "a2s_transpose_targets")
+
+
+def shift_bins(x, eff_bins, y=None):
+    """a2s_shift_bins: x (B, ..., rows, F) float32, contiguous -> y of the same shape (a fresh tensor when not given), every row of clip b shifted
+    by eff_bins[b] bins (float32 on the device; fractional shifts interpolate linearly, what falls outside [0, F) is zero)."""
+    fn = "shift_bins"
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
+    _need(x.is_contiguous(), fn, "x", "must be contiguous")
+    B, F = x.shape[0], x.shape[-1]
+    _need(torch.is_tensor(eff_bins) and eff_bins.dtype == torch.float32 and tuple(eff_bins.shape) == (B,) and eff_bins.is_contiguous(), fn, "eff_bins",
+          f"must be a contiguous float32 tensor with one element per clip ({B})")
+    if y is None:
+        y = torch.empty_like(x)
+    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
+    _need(y.device == x.device, fn, "y", "must be on x's device")
+    if x.numel() == 0:
+        return y
+    check(lib().a2s_shift_bins(stream(), _p(x), _p(y), _p(eff_bins), B, x.numel() // (B * F), F), "a2s_shift_bins")
+    return y
+
+
+def augment_launches():
+    """Launches of the two augmentation kernels in this process (a2s_augment_launches)."""
+    return int(lib().a2s_augment_launches())
+
+
 def align_buffers(R, max_steps, T, device):
     """The outputs of one alignment call (a2s_align_args) over R rows: -> (AlignArgs, dict of the tensors it points to), pre-filled with what a step
     that never runs keeps: peak -1, weight 0, centroid -1."""

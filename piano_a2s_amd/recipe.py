@@ -135,6 +135,37 @@ class ASR(sb.Brain):
                              "`constrained_decoding` attribute")
         model.constrained_decoding = True
 
+    def _transpose_augment(self):
+        """--transpose_augment=K [--detune_bins=D] (optional overrides as --constrained_decoding): every TRAIN batch is transposed on the device by a
+        whole number of semitones in -K .. K per clip (features shifted, score respelled) and detuned by up to D feature bins (piano_a2s_amd.augment).
+        -> the augmenter, or None when both are 0 (the default: nothing is built, nothing is launched).  Values out of range raise ValueError."""
+        if not hasattr(self, "_augment"):
+            from piano_a2s_amd import augment
+            K, D = augment.check_range(getattr(self.hparams, "transpose_augment", 0), getattr(self.hparams, "detune_bins", 0.0))
+            self._augment = None
+            if K or D:
+                model = self.modules.transcription
+                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
+                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
+                    raise ValueError(f"--transpose_augment needs a transcription module that states its `cfg['freq_bins']`; {type(model).__name__} does not")
+                import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                self._augment = augment.TransposeAugment(model.cfg, K, D, getattr(self.hparams, "seed", 0), self.device,
+                                                         bins_per_octave=getattr(self.hparams, "bins_per_octave", 60), rank=rank)
+        return self._augment
+
+    def _train_features(self, batch):
+        """`_features` of a TRAIN batch, augmented when the run asks for it.  The targets are rewritten in place: a tensor that was on the device
+        before (and so is the caller's own) is copied first."""
+        out = _features(batch, self.device)
+        aug = self._transpose_augment()
+        if aug is None:
+            return out
+        for i in (2, 3, 5):
+            if out[i] is batch[i]:
+                out[i] = out[i].clone()
+        return aug(out)
+
     def compute_objectives(self, predictions, batch, stage):
         batch = _to_device(batch, self.device)
         _, ts_t, key_t, up_t, _, lo_t, _, names, versions = batch
@@ -221,6 +252,7 @@ class ASR(sb.Brain):
         reference, whose torch optimizer IS the recoverable).  When the fused step trains, the recoverable is fused.opt: its recovered
         lr is the truth, and the idle torch optimizer (which update_learning_rate also addresses) is brought in line with it -- without
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
+        self._transpose_augment()                 # (a --transpose_augment / --detune_bins out of range is refused before anything else happens)
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
         fused = self._fused_step()
@@ -231,8 +263,12 @@ class ASR(sb.Brain):
     def fit_batch(self, batch):
         fused = self._fused_step()
         if not fused:
+            if self._transpose_augment() is not None:
+                # the generic path reads the batch twice (compute_forward, compute_objectives): both see the augmented device batch, which
+                # `_features` and `_to_device` pass through as it is
+                batch = self._train_features(batch)
             return super().fit_batch(batch)
-        fused(_features(batch, self.device), self.teacher_forcing_ratio)
+        fused(self._train_features(batch), self.teacher_forcing_ratio)
         *terms, applied = fused.report()                              # one small D2H per step (the reference does four)
         self._record_losses(*[torch.tensor(t) for t in terms])
         loss = torch.tensor(sum(terms))
@@ -262,6 +298,8 @@ class ASR(sb.Brain):
                 mkdirs(os.path.join(self.hparams.output_folder, "results", split))
         self.time_sig_list = load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                "data_processing", "metadata", "time_signature_list.json"))
+        if stage == sb.Stage.TRAIN and self._transpose_augment() is not None:
+            self._augment.reseed(epoch)               # the draws of an epoch depend on (seed, rank, epoch) alone: a resumed run repeats them
         if stage != sb.Stage.TRAIN:
             self.teacher_forcing_ratio = 0.
         elif self.finetune:
@@ -276,6 +314,9 @@ class ASR(sb.Brain):
             stats["teacher_forcing_ratio"] = self.teacher_forcing_ratio
         if stage == sb.Stage.TRAIN:
             self.train_stats = stats
+            if self._transpose_augment() is not None:
+                counts = self._augment.counts()                       # one small D2H per epoch; cumulative over the run, logged with the train stats
+                stats.update(augmented_clips=counts["clips"], transposed_clips=counts["transposed"], not_representable_clips=counts["not_representable"])
             return
         if not hasattr(self, "train_stats"):
             self.train_stats = {"loss": -1}
@@ -323,7 +364,11 @@ def write_run_summary(brain, hparams):
         return
     fused = getattr(brain, "_fused", None)
     inited = dist.is_available() and dist.is_initialized()
-    save({"fused_hip_step": bool(fused), "world_size": dist.get_world_size() if inited else 1, "backend": dist.get_backend() if inited else None,
+    aug = getattr(brain, "_augment", None)
+    extra = {}
+    if aug is not None:
+        extra["transpose_augment"] = dict(max_semitones=aug.K, detune_bins=aug.D, **aug.counts())
+    save({**extra, "fused_hip_step": bool(fused), "world_size": dist.get_world_size() if inited else 1, "backend": dist.get_backend() if inited else None,
           "optimizer_steps": int(getattr(brain, "step", 0)), "gradient_allreduces": int(fused.collectives) if fused else 0,
           "nonfinite_steps": int(getattr(brain, "nonfinite_count", 0)), "device": str(brain.device)},
          os.path.join(hparams["output_folder"], "run_summary.json"))
