@@ -587,6 +587,28 @@ int a2s_edit_distance(void* stream, const int* ref, const long long* ref_off, co
                       int n_pairs, int max_ref_len, int max_hyp_len, int* dist);
 int a2s_edit_distance_max_len(void);
 
+/* ---- note-level scoring of decoded bars (csrc/a2s_notes.hip; the definition is piano_a2s_amd/metrics.py: note_events).
+ * n_pairs pairs of bar rows (target, prediction), one workgroup each, one launch.  ref / hyp: the rows' token ids one after the other (int32;
+ * a row counts up to its first <eos>); ref_off / hyp_off: n_pairs + 1 offsets into them.  Vocabulary tables of V int32 each: dur_ticks (ticks of a
+ * duration symbol, 147840 to the whole note; 0: no duration), midi (MIDI number of a pitch symbol, A2S_NOTE_MIDI_REST for the rest, -1: no pitch),
+ * cls (A2S_NOTE_CLS_*).  An id outside [0, V) is ignored like <pad> and indexes no table.  out: 8 ints per pair = n_ref, n_hyp, tp_pitch,
+ * tp_onset, tp_value, tp_spelled, flags (bit 0 / 1: the target / prediction row has events beyond the eighth spine, which are dropped), 0.
+ * A pair with a row of more than a2s_note_match_max_len() (1024) ids is not read and gets -1 in its six counts.  All pointers are device
+ * pointers; nothing is read back or synchronised.  Bad arguments (a null pointer, n_pairs < 0, V < 1) are refused before anything is launched;
+ * n_pairs == 0 launches nothing.  a2s_note_match_launches: launches so far (proof of the path). */
+#define A2S_NOTE_CLS_OTHER 0
+#define A2S_NOTE_CLS_TAB 1
+#define A2S_NOTE_CLS_NL 2
+#define A2S_NOTE_CLS_FERM 3
+#define A2S_NOTE_CLS_CLOSE 4
+#define A2S_NOTE_CLS_EOS 5
+#define A2S_NOTE_CLS_IGNORE 6
+#define A2S_NOTE_MIDI_REST (-2)
+int a2s_note_match(void* stream, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, int n_pairs,
+                   const int* dur_ticks, const int* midi, const int* cls, int V, int* out);
+int a2s_note_match_max_len(void);
+long a2s_note_match_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -413,6 +413,13 @@ int a2s_edit_distance(void* stream, const int* ref, const long long* ref_off, co
 }
 int a2s_edit_distance_max_len(void) { return a2s_edit_distance_max_len_impl(); }
 
+int a2s_note_match(void* stream, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, int n_pairs,
+                   const int* dur_ticks, const int* midi, const int* cls, int V, int* out) {
+    return a2s_note_match_impl(ST, ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, V, out);
+}
+int a2s_note_match_max_len(void) { return a2s_note_match_max_len_impl(); }
+long a2s_note_match_launches(void) { return a2s_note_match_launches_impl(); }
+
 int a2s_bn_bwd_stats(void* stream, const float* g, const float* x, const float* mean, const float* invstd, const float* scale, const float* shift,
                      const uint8_t* keep_mask, float inv_keep, float* partial, float* sums, long rows, int C, int F) {
     return a2s_bn_bwd_stats_impl(ST, g, x, mean, invstd, scale, shift, keep_mask, inv_keep, partial, sums, rows, C, F);

@@ -301,6 +301,12 @@ long a2s_edit_distance_launches(void);
 int a2s_edit_distance_impl(hipStream_t st, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, const int* order,
     int n_pairs, int max_ref_len, int max_hyp_len, int* dist);
 
+// ---- a2s_notes.hip
+int a2s_note_match_max_len_impl(void);
+long a2s_note_match_launches_impl(void);
+int a2s_note_match_impl(hipStream_t st, const int* ref, const long long* ref_off, const int* hyp, const long long* hyp_off, int n_pairs,
+    const int* dur_ticks, const int* midi, const int* cls, int V, int* out);
+
 // ---- a2s_vqt.hip
 int a2s_vqt_logmag_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db);
 int a2s_vqt_decimate_impl(hipStream_t st, const float* ypad, long plen, const float* taps, int ntaps, float* out, long n_out, int B);

@@ -344,6 +344,32 @@ def augment_launches():
     return int(lib().a2s_augment_launches())
 
 
+def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):
+    """a2s_note_match: the note counts of n_pairs pairs of bar rows, one launch on the current stream.  ref / hyp (int32 ids) and ref_off / hyp_off
+    (int64, n_pairs + 1 each) are device tensors or device addresses (ints: parts of one packed buffer, metrics.device_note_counts); dur_ticks, midi, cls
+    the (V,) int32 tables of metrics.note_tables() on the device; out (n_pairs, 8) int32 receives the counts.  Returns out."""
+    fn = "note_match"
+    for name, t, dtype in (("ref", ref, torch.int32), ("hyp", hyp, torch.int32), ("ref_off", ref_off, torch.int64), ("hyp_off", hyp_off, torch.int64)):
+        _need(isinstance(t, int) or (torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous()), fn, name, f"must be a contiguous {dtype} tensor or an address")
+    for name, t in (("ref_off", ref_off), ("hyp_off", hyp_off)):
+        _need(isinstance(t, int) or t.numel() == n_pairs + 1, fn, name, f"must have n_pairs + 1 = {n_pairs + 1} elements")
+    for name, t in (("dur_ticks", dur_ticks), ("midi", midi), ("cls", cls)):
+        _need(torch.is_tensor(t) and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == dur_ticks.numel(), fn, name,
+              "must be a contiguous int32 tensor (V,)")
+    _need(torch.is_tensor(out) and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == 8 * n_pairs, fn, "out",
+          f"must be a contiguous int32 tensor of 8 * n_pairs = {8 * n_pairs} elements")
+    if n_pairs == 0:
+        return out
+    check(lib().a2s_note_match(stream(), _p(ref), _p(ref_off), _p(hyp), _p(hyp_off), n_pairs, _p(dur_ticks), _p(midi), _p(cls), dur_ticks.numel(), _p(out)),
+          "a2s_note_match")
+    return out
+
+
+def note_match_launches():
+    """Launches of the note-matching kernel in this process (a2s_note_match_launches)."""
+    return int(lib().a2s_note_match_launches())
+
+
 def align_buffers(R, max_steps, T, device):
     """The outputs of one alignment call (a2s_align_args) over R rows: -> (AlignArgs, dict of the tensors it points to), pre-filled with what a step
     that never runs keeps: peak -1, weight 0, centroid -1."""

@@ -4,10 +4,14 @@ space-joined Kern symbols (the reference calls jiwer.wer -- third-party, absent 
 
 The distances of corpus_wer come from the device (csrc/a2s_metrics.hip: one launch over all clips of the stage) once the process has the GPU
 open, and from the host loop below otherwise; the floats are the same Python expressions either way.  macro-F1 stays on the host (sklearn per
-clip, a few ms: its float parity with sklearn is not worth risking; a possible follow-up)."""
+clip, a few ms: its float parity with sklearn is not worth risking; a possible follow-up).
+
+Not in the reference: the note-level precision / recall / F1 of the decoded bars (note_events .. corpus_note_f1 below), whose
+counts come from csrc/a2s_notes.hip under the same rule and from the host definition otherwise."""
 import os
 import sys
 import time
+from itertools import chain
 
 import numpy as np
 
@@ -193,3 +197,254 @@ def corpus_f1(pred, target):
     from sklearn.metrics import f1_score
     per = {k: float(f1_score(target[k], pred[k], average="macro")) for k in pred}
     return (sum(per.values()) / max(len(per), 1)), per
+
+
+# ---------------------------------------------------------------------------------------------------------------- note-level F1
+# Prediction and target are aligned bar by bar already (one decoder row per bar and staff): each row is parsed into notes (onset tick, MIDI number,
+# duration ticks, pitch token) and the two multisets of a bar are intersected at four levels.  `note_events` below IS the definition; the device
+# (csrc/a2s_notes.hip) restates it.  Everything up to the final divisions is integer arithmetic, so the two agree exactly.
+NOTE_W = 147840                       # ticks of a whole note = 128 * 3 * 5 * 7 * 11: every duration symbol of the vocabulary is a whole number of ticks
+NOTE_FIELDS = 8                       # spines of a bar row that are timed; events in later ones are dropped and flag the row
+NOTE_REST = -2                        # midi table: the rest (-1: no pitch symbol)
+NOTE_CLS = {"TAB": 1, "NL": 2, "FERM": 3, "CLOSE": 4, "EOS": 5, "PAD": 6, "SOS": 6}          # cls table (A2S_NOTE_CLS_* of include/a2s.h); every other class: 0
+NOTE_COLUMNS = ("n_ref", "n_hyp", "tp_pitch", "tp_onset", "tp_value", "tp_spelled", "flags")
+# corpus_note_f1 takes its counts from the device when this is true AND the rule of the WER holds (_device_ready: the process has the GPU open, the library
+# is built, WER_DEVICE is on).  So A2S_WER_DEVICE=0 sends both metrics to the host: one switch for "scoring on the device", no second variable.
+NOTE_DEVICE = True
+# what the last corpus_note_f1 / note_match call did: {"backend": "device" | "host", "rows" (bar pairs), "device_rows", "host_rows", "seconds"}; on the
+# device path also "pack_seconds" and "device_seconds" (transfers + kernel)
+last_note_stats = {}
+_note_tables = None
+_note_device_tables = {}
+
+
+def note_tables():
+    """{"W", "dur_ticks", "midi", "cls"}: per id of LabelsMultiple(extended=True) the ticks of a duration symbol (0: not one), the MIDI number of a
+    pitch symbol (NOTE_REST for `r`, -1: not one) and the class code of NOTE_CLS, as read-only int32 arrays.  Derived from the symbols by pattern
+    (kern_grammar.token_class, kern_transpose.parse_pitch), never from literal ids."""
+    global _note_tables
+    if _note_tables is None:
+        from data_processing.humdrum import LabelsMultiple
+        from .kern_grammar import token_class
+        from .kern_transpose import parse_pitch
+        labels = LabelsMultiple(extended=True).labels
+        dur, midi, cls = np.zeros(len(labels), dtype=np.int32), np.full(len(labels), -1, dtype=np.int32), np.zeros(len(labels), dtype=np.int32)
+        for i, sym in enumerate(labels):
+            c = token_class(sym)
+            if c == "DUR":                                       # reciprocal r: W / r ticks; dotted: 3 W / (2 r)
+                dotted = sym.endswith(".")
+                num, den = NOTE_W * (3 if dotted else 1), int(sym.rstrip(".")) * (2 if dotted else 1)
+                assert den > 0 and num % den == 0, f"duration symbol {sym!r} is not a whole number of ticks"
+                dur[i] = num // den
+            elif c == "PITCH":
+                midi[i] = NOTE_REST if sym == "r" else parse_pitch(sym)[1]
+            else:
+                cls[i] = NOTE_CLS.get(c, 0)
+        assert dur.max() < 1 << 18 and midi.max() < 1 << 7          # the device packs a note as onset << 25 | midi << 18 | ticks
+        for t in (dur, midi, cls):
+            t.setflags(write=False)
+        _note_tables = {"W": NOTE_W, "dur_ticks": dur, "midi": midi, "cls": cls}
+    return _note_tables
+
+
+note_tables()                         # (the assertions hold at import)
+
+
+def _note_parse(ids_row):
+    """-> (events [(line, field, ticks, midi, token id, continuation)] in row order, line times {line: onset}, overflow)."""
+    tb = note_tables()
+    dur, midi, cls = tb["dur_ticks"], tb["midi"], tb["cls"]
+    V, ign, eos = len(dur), NOTE_CLS["PAD"], NOTE_CLS["EOS"]
+    row = []
+    for t in np.asarray(ids_row, dtype=np.int64).reshape(-1).tolist():
+        if 0 <= t < V:
+            if cls[t] == eos:
+                break
+            if cls[t] != ign:
+                row.append(t)
+    events, line, field = [], 0, 0
+    for i, t in enumerate(row):
+        c = cls[t]
+        if c == NOTE_CLS["NL"]:
+            line, field = line + 1, 0
+        elif c == NOTE_CLS["TAB"]:
+            field += 1
+        elif midi[t] != -1 and i > 0 and dur[row[i - 1]] > 0:
+            nxt = row[i + 1:i + 3]
+            if nxt and cls[nxt[0]] == NOTE_CLS["FERM"]:
+                nxt = nxt[1:]
+            events.append((line, field, int(dur[row[i - 1]]), int(midi[t]), t, bool(nxt) and cls[nxt[0]] == NOTE_CLS["CLOSE"]))
+    overflow = any(e[1] >= NOTE_FIELDS for e in events)
+    end, t, times, i = [0] * NOTE_FIELDS, 0, {}, 0
+    while i < len(events):
+        j, first = i, {}
+        while j < len(events) and events[j][0] == events[i][0]:
+            if events[j][1] < NOTE_FIELDS:
+                first.setdefault(events[j][1], events[j][2])     # per field of this line the ticks of its first event
+            j += 1
+        if first:
+            t = max(t, min(end[f] for f in first))
+            for f, ticks in first.items():
+                end[f] = t + ticks
+        times[events[i][0]] = t
+        i = j
+    return events, times, overflow
+
+
+def note_events(ids_row):
+    """THE DEFINITION.  One bar row of token ids -> (notes [(onset tick, MIDI number, duration ticks, pitch token id)] in row order, overflow).
+    The row ends before its first <eos>; <pad>, <sos> and ids outside the vocabulary are taken out.  An event is a PITCH-class token (the rest
+    included) that directly follows a DUR token; its line is the number of NL tokens before it, its field the number of TAB tokens since the last NL.
+    It is a continuation if the token behind it -- behind one optional fermata -- is `_` or `]`.  A note is an event that is neither a rest nor a
+    continuation.  Time: end[j] = 0 for the fields j < 8; line by line, t = max(t_prev, min of end[j] over the fields of the line that hold an
+    event), then end[j] = t + the ticks of the field's first event; every note of the line starts at t with its own duration.  A line without
+    events changes nothing.  Events in fields >= 8 are dropped and set `overflow`.  Tied chains are not merged: `[4c` then `4c]` is one quarter."""
+    events, times, overflow = _note_parse(ids_row)
+    return [(times[l], m, ticks, tok) for l, f, ticks, m, tok, cont in events if m != NOTE_REST and not cont and f < NOTE_FIELDS], overflow
+
+
+def _multiset_overlap(a, b):
+    from collections import Counter
+    ca, cb = Counter(a), Counter(b)
+    return sum(min(n, cb[k]) for k, n in ca.items())
+
+
+def note_counts(ref_row, hyp_row):
+    """The host counts of one pair of bar rows (target, prediction), as NOTE_COLUMNS: note counts of the two sides, the sizes of the multiset
+    intersections keyed by MIDI number / (onset, MIDI) / (onset, MIDI, ticks) / (onset, pitch token), flags (bit 0: the target row overflowed the
+    eight spines, bit 1: the prediction row)."""
+    r, ro = note_events(ref_row)
+    h, ho = note_events(hyp_row)
+    return (len(r), len(h), _multiset_overlap([n[1] for n in r], [n[1] for n in h]), _multiset_overlap([n[:2] for n in r], [n[:2] for n in h]),
+            _multiset_overlap([n[:3] for n in r], [n[:3] for n in h]), _multiset_overlap([(n[0], n[3]) for n in r], [(n[0], n[3]) for n in h]),
+            int(ro) | int(ho) << 1)
+
+
+def note_match_capacity():
+    """Longest bar row (in ids) the device kernel takes."""
+    from . import hip
+    return int(hip.lib().a2s_note_match_max_len())
+
+
+def _pair_rows(ref_rows_per_clip, hyp_rows_per_clip):
+    """Bars are paired by index; a bar that one side lacks is paired with an empty row.  -> (ref rows, hyp rows, pairs per clip)."""
+    ref, hyp, per_clip = [], [], []
+    for r, h in zip(ref_rows_per_clip, hyp_rows_per_clip):
+        n = max(len(r), len(h))
+        ref += list(r) + [()] * (n - len(r))
+        hyp += list(h) + [()] * (n - len(h))
+        per_clip.append(n)
+    return ref, hyp, np.asarray(per_clip, dtype=np.int64)
+
+
+def _sum_clips(pair_counts, per_clip):
+    """(pairs, 7) counts -> (clips, 7): the six counts summed over a clip's bars, the last column its number of overflowed rows."""
+    c = np.asarray(pair_counts, dtype=np.int64).reshape(-1, len(NOTE_COLUMNS)).copy()
+    c[:, 6] = (c[:, 6] & 1) + (c[:, 6] >> 1 & 1)
+    out = np.zeros((len(per_clip), len(NOTE_COLUMNS)), dtype=np.int64)
+    has = per_clip > 0
+    if has.any():
+        out[has] = np.add.reduceat(c, (np.cumsum(per_clip) - per_clip)[has], axis=0)
+    return out
+
+
+def _csr_rows(rows):
+    """Rows (sequences of ids) -> (ids int32, offsets int64), in one pass over the tokens: an array per row costs four times as much."""
+    lens = np.fromiter(map(len, rows), dtype=np.int64, count=len(rows))
+    ids = np.fromiter(chain.from_iterable(rows), dtype=np.int32, count=int(lens.sum()))
+    return ids, np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+
+
+def device_note_counts(ref_ids, ref_off, hyp_ids, hyp_off, device=None):
+    """Device counts of every pair (ref_ids[ref_off[p]:ref_off[p + 1]], hyp_ids[hyp_off[p]:hyp_off[p + 1]]) as an (n, 8) numpy int32 array (the
+    kernel's rows: NOTE_COLUMNS and a spare; -1 in the six counts of a pair beyond the capacity): one host-to-device copy, one launch on the current
+    stream of `device` (default: the current one), one copy back."""
+    import torch
+    from . import hip
+    L = hip.lib()
+    if not hasattr(L, "a2s_note_match"):
+        raise hip.A2SError(f"{hip.LIB} has no a2s_note_match (a build from before the note-level scoring)")
+    ref_off, hyp_off = np.asarray(ref_off, dtype=np.int64), np.asarray(hyp_off, dtype=np.int64)
+    n = len(ref_off) - 1
+    if n <= 0:
+        return np.zeros((0, 8), dtype=np.int32)
+    nr, nh = int(ref_off[-1]), int(hyp_off[-1])
+    buf = np.empty(4 * (n + 1) + nr + nh, dtype=np.int32)           # [ref_off | hyp_off] as int64, then the ref ids, the hyp ids
+    off64 = buf[:4 * (n + 1)].view(np.int64)
+    off64[:n + 1], off64[n + 1:] = ref_off, hyp_off
+    w = 4 * (n + 1)
+    buf[w:w + nr] = ref_ids[:nr]
+    buf[w + nr:] = hyp_ids[:nh]
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        tabs = _note_device_tables.get(str(dev))
+        if tabs is None:                                             # the three vocabulary tables: uploaded once per device
+            tb = note_tables()
+            tabs = _note_device_tables[str(dev)] = tuple(torch.from_numpy(tb[k].copy()).to(dev) for k in ("dur_ticks", "midi", "cls"))
+        d_in = torch.from_numpy(buf).to(dev)
+        out = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        base = d_in.data_ptr()
+        hip.note_match(base + 4 * w, base, base + 4 * (w + nr), base + 8 * (n + 1), n, *tabs, out)
+        return out.cpu().numpy()                                     # (the copy waits for the launch: d_in stays referenced until here)
+
+
+def note_match(ref_rows_per_clip, hyp_rows_per_clip, device=None):
+    """Per clip the counts of NOTE_COLUMNS (an (n_clips, 7) int64 array; the last column: overflowed rows), summed over its bar pairs on the host
+    -- no atomics, the sums are reproducible.  The pairs go to the device in one call (device_note_counts); a pair the kernel refuses (a row beyond
+    its capacity) is scored by note_counts.  Fills last_note_stats."""
+    global last_note_stats
+    t0 = time.perf_counter()
+    ref, hyp, per_clip = _pair_rows(ref_rows_per_clip, hyp_rows_per_clip)
+    ref_ids, ref_off = _csr_rows(ref)
+    hyp_ids, hyp_off = _csr_rows(hyp)
+    t1 = time.perf_counter()
+    raw = device_note_counts(ref_ids, ref_off, hyp_ids, hyp_off, device)
+    t2 = time.perf_counter()
+    counts = raw[:, :len(NOTE_COLUMNS)].astype(np.int64)
+    host = np.nonzero(raw[:, 0] < 0)[0]
+    for p in host.tolist():
+        counts[p] = note_counts(ref[p], hyp[p])
+    last_note_stats = {"backend": "device", "rows": len(ref), "device_rows": len(ref) - len(host), "host_rows": len(host),
+                       "seconds": time.perf_counter() - t0, "pack_seconds": t1 - t0, "device_seconds": t2 - t1}
+    return _sum_clips(counts, per_clip)
+
+
+def _ratio(num, den):
+    return num / den if den else 1.0
+
+
+def note_scores(c):
+    """One row of NOTE_COLUMNS sums -> the floats of a clip: F1 = 2 tp / (n_ref + n_hyp), precision tp / n_hyp, recall tp / n_ref at the three
+    levels (1.0 where the denominator is 0), spelled_share = tp_spelled / tp_onset, and the integers they come from."""
+    n_ref, n_hyp, tp_pitch, tp_onset, tp_value, tp_spelled, over = (int(v) for v in c)
+    out = {}
+    for level, tp in (("pitch", tp_pitch), ("onset", tp_onset), ("value", tp_value)):
+        out["f1_" + level] = _ratio(2 * tp, n_ref + n_hyp)
+        out["precision_" + level] = _ratio(tp, n_hyp)
+        out["recall_" + level] = _ratio(tp, n_ref)
+    out["spelled_share"] = _ratio(tp_spelled, tp_onset)
+    out.update(n_ref=n_ref, n_hyp=n_hyp, tp_pitch=tp_pitch, tp_onset=tp_onset, tp_value=tp_value, tp_spelled=tp_spelled, overflow_rows=over)
+    return out
+
+
+NOTE_MEAN_KEYS = ("f1_pitch", "f1_onset", "f1_value", "spelled_share", "precision_pitch", "precision_onset", "precision_value", "recall_pitch",
+                  "recall_onset", "recall_value")
+
+
+def corpus_note_f1(pred, target):
+    """pred/target: dict id -> list of per-bar id rows (one staff), as corpus_wer takes them.  Returns (means, per_clip): per clip the dict of
+    note_scores, `means` the means over the clips of its floats and the total of overflow_rows."""
+    global last_note_stats
+    t0 = time.perf_counter()
+    keys = list(pred)
+    if keys and NOTE_DEVICE and _device_ready():
+        sums = note_match([target[k] for k in keys], [pred[k] for k in keys])
+        last_note_stats["seconds"] = time.perf_counter() - t0
+    else:
+        ref, hyp, per_clip = _pair_rows([target[k] for k in keys], [pred[k] for k in keys])
+        sums = _sum_clips([note_counts(r, h) for r, h in zip(ref, hyp)], per_clip)
+        last_note_stats = {"backend": "host", "rows": len(ref), "device_rows": 0, "host_rows": len(ref), "seconds": time.perf_counter() - t0}
+    per = {k: note_scores(row) for k, row in zip(keys, sums)}
+    means = {m: (sum(v[m] for v in per.values()) / len(per) if per else 1.0) for m in NOTE_MEAN_KEYS}
+    means["overflow_rows"] = sum(v["overflow_rows"] for v in per.values())
+    return means, per

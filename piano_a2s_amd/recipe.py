@@ -114,6 +114,12 @@ class ASR(sb.Brain):
         v = getattr(self.hparams, "alignment", False)
         return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
 
+    def _note_metrics(self):
+        """--note_metrics=true (an optional override as --constrained_decoding): VALID / TEST also score the decoded bars note by note
+        (metrics.corpus_note_f1).  Off by default: no key is added and nothing of it runs."""
+        v = getattr(self.hparams, "note_metrics", False)
+        return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
     def _set_alignment(self):
         if not self._alignment():
             return
@@ -326,6 +332,14 @@ class ASR(sb.Brain):
         key_f1, key_f1_d = metrics.corpus_f1(self.key_pred, self.key_target)
         time_f1, time_f1_d = metrics.corpus_f1(self.time_sig_pred, self.time_sig_target)
         stats.update(key_f1=key_f1, time_f1=time_f1, WER_upper=wer_up, WER_lower=wer_lo, WER=(wer_up + wer_lo) / 2)
+        notes_d = None
+        if self._note_metrics():
+            notes_up, notes_up_d = metrics.corpus_note_f1(self.upper_pred, self.upper_target)
+            notes_lo, notes_lo_d = metrics.corpus_note_f1(self.lower_pred, self.lower_target)
+            for staff, m in (("upper", notes_up), ("lower", notes_lo)):
+                stats.update({f"note_f1_{level}_{staff}": m[f"f1_{level}"] for level in ("pitch", "onset", "value")})
+            stats["note_f1"] = (notes_up["f1_onset"] + notes_lo["f1_onset"]) / 2
+            notes_d = {cid: {"upper": notes_up_d[cid], "lower": notes_lo_d[cid]} for cid in self.upper_pred}
         old_lr, new_lr = self.hparams.lr_annealing(stats["WER"])
         sb.nnet.schedulers.update_learning_rate(self.optimizer, new_lr)
         fused = self._fused_step()
@@ -342,6 +356,8 @@ class ASR(sb.Brain):
             record.update(self._clip_record(cid, split))
             if cid in self.alignment_records:
                 record["alignment"] = self.alignment_records[cid]
+            if notes_d is not None:
+                record["notes"] = notes_d[cid]
             save(record, os.path.join(self.hparams.output_folder, "results", split, f"{cid}.json"))
 
     def _clip_record(self, cid, split):

@@ -117,6 +117,35 @@ def make_wer_corpus(n_clips, seed, bars=5, max_length=(398, 189), upper_range=(2
     return out
 
 
+def mutate_row(row, rate, rng):
+    """A copy of the id row with seeded substitutions, deletions and insertions, each at `rate` per token, by ids of the whole vocabulary."""
+    out = []
+    for t in row:
+        u = rng.random()
+        if u < rate:
+            out.append(int(rng.integers(0, VOCAB_SIZE)))               # substitution
+        elif u >= 2 * rate:                                            # (else: deletion)
+            out.append(int(t))
+        if rng.random() < rate:
+            out.append(int(rng.integers(0, VOCAB_SIZE)))               # insertion
+    return out
+
+
+def make_note_corpus(n_clips, rate, seed, cfg=None, first_clip=0):
+    """Seeded inputs of metrics.corpus_note_f1: {"upper": (target, pred), "lower": ...}, each a dict clip id -> list of per-bar id rows as the recipe
+    collects them.  The targets are the well-formed scores of the rendered corpus (scoregen.make_clip, seeds first_clip ..) at cfg's max_length
+    (default: the shipped one), the predictions their mutate_row copies."""
+    from . import scoregen, spec
+    cfg = cfg or spec.default_cfg()
+    rng = np.random.default_rng(seed)
+    clips = [scoregen.make_clip(cfg, first_clip + c, frames=201) for c in range(n_clips)]
+    out = {}
+    for staff in ("upper", "lower"):
+        target = {f"0~score{first_clip + c}": [list(r) for r in clip["ids"][staff]] for c, clip in enumerate(clips)}
+        out[staff] = (target, {k: [mutate_row(r, rate, rng) for r in rows] for k, rows in target.items()})
+    return out
+
+
 def make_waveforms(batch, seed, seconds=12.0, sr=16000, device="cpu"):
     """Synthetic 16 kHz clips for the online VQT front-end: up to 6 simultaneous decaying harmonic tones at MIDI 21-108,
     peak-normalised to 0.9.  Returns (batch, seconds*sr) float32."""

@@ -1,11 +1,13 @@
 """Is the rendered synthetic corpus learnable, and what do the decoders make of it?  (needs the GPU.)
 
-    python tools/rendered_corpus_eval.py --model small|full --steps N [--batch B] [--frames F] [--eval_clips M] [--out profiles/rendered_corpus.json]
+    python tools/rendered_corpus_eval.py --model small|full --steps N [--batch B] [--frames F] [--eval_clips M] [--note_metrics]
+                                         [--out profiles/rendered_corpus.json]
 
 1. trains on rendered clips (datasets.syn.RenderedClips, fresh clips every step) for N fused optimizer steps -- once with every clip's own audio and
    once, as the control, from the same initial weights with the audio permuted among the clips of each batch (uninformative audio);
 2. on held-out rendered clips reports per-staff WER and key / time-signature F1 of greedy, grammar-constrained and beam (K = 2, 4) decoding with the
-   share of well-formed bars, for both models;
+   share of well-formed bars, for both models; with --note_metrics also the note-level F1 (pitch / onset / value, metrics.corpus_note_f1: DESIGN.md
+   section 17) of every decoding mode beside its WER;
 3. reports the mean absolute difference between the forced-alignment centroids (teacher-forced forward over the true score) and the true onsets;
 4. writes the JSON.
 No threshold is applied to anything: the file records what the run shows."""
@@ -78,9 +80,16 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
                 pred["key"][name], target["key"][name] = key_o[b].argmax(-1).cpu().tolist(), batch[2][b].tolist()
                 pred["ts"][name], target["ts"][name] = ts_o[b].argmax(-1).cpu().tolist(), batch[1][b].tolist()
     model.constrained_decoding, model.beam_size = False, 1
-    return {"WER_upper": metrics.corpus_wer(pred["up"], target["up"], inv)[0], "WER_lower": metrics.corpus_wer(pred["lo"], target["lo"], inv)[0],
-            "key_f1": metrics.corpus_f1(pred["key"], target["key"])[0], "time_f1": metrics.corpus_f1(pred["ts"], target["ts"])[0],
-            "legal_share_upper": kern_grammar.legal_share(pred["up"]), "legal_share_lower": kern_grammar.legal_share(pred["lo"])}
+    out = {"WER_upper": metrics.corpus_wer(pred["up"], target["up"], inv)[0], "WER_lower": metrics.corpus_wer(pred["lo"], target["lo"], inv)[0],
+           "key_f1": metrics.corpus_f1(pred["key"], target["key"])[0], "time_f1": metrics.corpus_f1(pred["ts"], target["ts"])[0],
+           "legal_share_upper": kern_grammar.legal_share(pred["up"]), "legal_share_lower": kern_grammar.legal_share(pred["lo"])}
+    if args.note_metrics:
+        for staff, k in (("upper", "up"), ("lower", "lo")):
+            means = metrics.corpus_note_f1(pred[k], target[k])[0]
+            out.update({f"note_f1_{level}_{staff}": means[f"f1_{level}"] for level in ("pitch", "onset", "value")})
+            out[f"spelled_share_{staff}"], out[f"overflow_rows_{staff}"] = means["spelled_share"], means["overflow_rows"]
+        out["note_f1"] = (out["note_f1_onset_upper"] + out["note_f1_onset_lower"]) / 2
+    return out
 
 
 def _alignment_error(model, ds, args, dev, front):
@@ -117,6 +126,7 @@ def main():
     ap.add_argument("--teacher_forcing", type=float, default=1.0)
     ap.add_argument("--log_every", type=int, default=10)
     ap.add_argument("--no_control", action="store_true")
+    ap.add_argument("--note_metrics", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import models
@@ -129,7 +139,7 @@ def main():
     train_set = RenderedClips(cfg, args.steps * args.batch, seed=args.seed, frames=args.frames)
     held_out = RenderedClips(cfg, args.eval_clips, seed=args.seed + 10_000_000, frames=args.frames)
     res = {"model": args.model, "cfg": {k: cfg[k] for k in ("hidden_size", "conv_feature_size", "max_length", "max_bars")}, "steps": args.steps,
-           "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "runs": {}}
+           "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "note_metrics": args.note_metrics, "runs": {}}
     torch.manual_seed(args.seed)
     init = {k: v.clone() for k, v in models.ScoreTranscription(**cfg).state_dict().items()}
     for name, permute in (("matched", False),) + (() if args.no_control else (("control_permuted_audio", True),)):
