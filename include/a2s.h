@@ -391,6 +391,33 @@ int a2s_transpose_targets(void* stream, const int* new_key, const int* interval,
                           float* eff_bins, int* counters, int B);
 int a2s_shift_bins(void* stream, const float* x, float* y, const float* eff_bins, int B, int rows, int F);
 int a2s_augment_launches(void);
+
+/* ---- tempo augmentation of a training batch (csrc/a2s_tempo.hip): every clip's feature rows are resampled along time, the
+ * targets stay.  Both entry points take borrowed device pointers and a stream; they allocate nothing, do not synchronise and read nothing back.
+ * Positions are integers in Q16: step[b] = rint(65536 / c) is the source advance per output row of clip b, c the factor on durations (c > 1: slower).
+ * a2s_tempo_plan, one workgroup per clip of x (B, rows, F) float32, contiguous: content[b] = 1 + the last row that holds a value != 0 (a NaN is
+ * content, -0.0 is not; 0 for an all-zero clip), found by scanning backwards from the last row in chunks of 16 rows up to the first chunk with content.
+ * Then, in fp32 and in this form, with n = content[b] and u[b] in [0, 1) drawn by the host:
+ *     lo = max(1 - R, (float)min_frames / n),  hi = min(1 + R, (float)rows / n);
+ *     n == 0 or lo > hi: step[b] = 65536 and the clip counts as kept;
+ *     otherwise c = fmaf(u[b], hi - lo, lo) and step[b] = clamp((int)rintf(65536.0f / c), 52429, 87381):
+ * a stretched clip still holds at least min_frames rows of content and does not run off its rows.  counters[0 .. 2] (device int32; global atomic
+ * adds) grow by: clips seen, clips with step != 65536, clips kept for want of a feasible interval.  content, step: (B,) int32.  Null pointers, B < 0
+ * or > 65535, rows < 1 or > 16384, F < 1, R outside [0, 0.25] or not finite, min_frames < 1: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and
+ * launches nothing.
+ * a2s_stretch_frames resamples the rows, out of place: x, y = (B, rows, F) float32, contiguous, x != y; step (B,) int32 is read on the device.  For
+ * output row t: pos = t * step, h = max(65536, step), w_k = h - |k * 65536 - pos| where that is > 0, W = the sum of w_k over all integer k, and
+ *     y[b][t][f] = sum_k (w_k / W) * x[b][k][f],   x taken as 0 for k outside [0, rows).
+ * step <= 65536 is linear interpolation between rows pos >> 16 and the next (W = 65536, exact weights); step > 65536 widens the tent to the source
+ * advance (at most three taps), so that no source row is skipped.  A tap of weight 0 is neither read nor added: step == 65536 writes x bit for bit.
+ * step outside [52429, 87381] (c outside 0.75 .. 1.25) writes zeros for that clip.  Nothing outside the B * rows * F floats of y is written and
+ * nothing outside those of x is read.  16-byte loads and stores when F % 4 == 0 and y is 16-byte aligned, 4-byte ones otherwise.  Null pointers,
+ * x == y, B < 0 or > 65535, rows < 1 or > 16384 (pos stays below 2^31), F < 1: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches
+ * nothing.  One launch per call each; a2s_tempo_launches: launches of the two so far (a2s_augment_launches does not count them). */
+int a2s_tempo_plan(void* stream, const float* x, int B, int rows, int F, const float* u, float R, int min_frames, int* content, int* step,
+                   int* counters);
+int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, int B, int rows, int F);
+int a2s_tempo_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

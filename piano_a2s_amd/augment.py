@@ -1,4 +1,6 @@
-"""Transposition augmentation of a training batch on the device: per clip a whole number of semitones s and a detuning of
+"""Augmentation of a training batch on the device: transposition and tempo (section 18, at the end of this file).
+
+Transposition: per clip a whole number of semitones s and a detuning of
 delta feature bins are drawn on the host; csrc/a2s_augment.hip respells the targets (kern_transpose's tables) and shifts the feature rows by
 bins_per_semitone * s + delta bins.  A clip whose score cannot be respelled keeps its score and key and is only detuned.
 
@@ -12,6 +14,8 @@ from piano_a2s_amd.abi import A2SError
 
 MAX_SEMITONES = kern_transpose.MAX_SEMITONES
 MAX_DETUNE_BINS = 2.5
+MAX_TEMPO_CHANGE = 0.25
+_TEMPO_STREAM = 0x74656D70          # "temp": what sets the tempo generator's seed sequence apart from the transposer's
 
 
 def check_range(max_semitones, detune_bins):
@@ -100,3 +104,80 @@ class TransposeAugment:
             return dict(clips=0, transposed=0, not_representable=0)
         c = self._counters.tolist()
         return dict(clips=c[0], transposed=c[1], not_representable=c[2])
+
+
+def check_tempo(max_change):
+    """R as a float, or ValueError: the largest relative change of the durations, 0 <= R <= 0.25."""
+    try:
+        R = float(max_change)
+    except (TypeError, ValueError):
+        raise ValueError(f"--tempo_augment must be a number (got {max_change!r})") from None
+    if not 0.0 <= R <= MAX_TEMPO_CHANGE:          # (also a NaN)
+        raise ValueError(f"--tempo_augment must be in 0 .. {MAX_TEMPO_CHANGE} (got {max_change!r})")
+    return R
+
+
+class TempoAugment:
+    """Tempo augmentation: every clip of a batch is played c times as slowly, c uniform in [1 - R, 1 + R] narrowed per clip so
+    that its content still lasts at least `min_frames` frames and still ends inside the window -- the reference's MIDIProcess.ramdom_scaling with
+    frames for seconds.  The features are resampled along time by csrc/a2s_tempo.hip; no target changes (a **kern score does not state a tempo).
+
+    cfg: the transcription module's configuration (freq_bins); R in [0, 0.25]; seed: the run's; device: where the batches live.  The host draws one
+    u in [0, 1) per clip from the object's own Generator (seeded from (seed, rank, epoch) and a constant, so that its stream is not the transposer's);
+    where a clip's content ends, which interval is feasible and the factor itself are found on the device: nothing is read back."""
+
+    def __init__(self, cfg, R, seed, device, rank=0, min_frames=400):
+        self.R = check_tempo(R)
+        self.freq_bins = int(cfg["freq_bins"])
+        self.min_frames = int(min_frames)
+        if self.min_frames < 1:
+            raise ValueError(f"tempo augmentation: min_frames must be >= 1 (got {min_frames!r})")
+        self.seed, self.rank = int(seed), int(rank)
+        self.device = torch.device(device)
+        self._rng = None
+        self._counters = None
+        self.last_plan = None
+        self.reseed(0, self.rank)
+
+    def reseed(self, epoch, rank=None):
+        """The draws that follow are a function of (seed, rank, epoch) alone."""
+        if rank is not None:
+            self.rank = int(rank)
+        self._rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.seed & 0xFFFFFFFFFFFFFFFF, self.rank, int(epoch or 0), _TEMPO_STREAM])))
+
+    def draw(self, B):
+        """u (B,) float32 in [0, 1) of the next batch; host only."""
+        return self._rng.random(size=B, dtype=np.float32)
+
+    def apply(self, batch, u):
+        """The batch (features (B, 1, T, F) float32 on the device first) under the given draws: two launches on the current stream.  Returns the batch
+        with a NEW feature tensor; everything else is the same objects, untouched."""
+        from piano_a2s_amd import hip
+        batch = list(batch)
+        x = batch[0]
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[-1] != self.freq_bins:
+            raise A2SError(f"TempoAugment: expects features (B, 1, T, {self.freq_bins}), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        B, rows = x.shape[0], x.shape[1] * x.shape[2]
+        if len(u) != B:
+            raise A2SError(f"TempoAugment: {len(u)} draws for {B} clips")
+        if self._counters is None:
+            self._counters = torch.zeros(3, dtype=torch.int32, device=self.device)
+        # pinned staging from the caching host allocator: it keeps a block until the copy that reads it has run
+        u_dev = torch.from_numpy(np.ascontiguousarray(u, dtype=np.float32)).pin_memory().to(self.device, non_blocking=True)
+        content = torch.empty(B, dtype=torch.int32, device=self.device)
+        step = torch.empty(B, dtype=torch.int32, device=self.device)
+        x = x.contiguous()
+        hip.tempo_plan(x, u_dev, self.R, max(1, min(self.min_frames, rows // 3)), content, step, self._counters)      # (short test windows still get stretched)
+        batch[0] = hip.stretch_frames(x, step)          # one fresh tensor per batch, as the un-augmented path's input is
+        self.last_plan = (content, step)                # (device tensors; reading them synchronises -- tests and tools only)
+        return batch
+
+    def __call__(self, batch):
+        return self.apply(batch, self.draw(batch[0].shape[0]))
+
+    def counts(self):
+        """{clips, stretched, kept} so far: one device-to-host copy."""
+        if self._counters is None:
+            return dict(clips=0, stretched=0, kept=0)
+        c = self._counters.tolist()
+        return dict(clips=c[0], stretched=c[1], kept=c[2])

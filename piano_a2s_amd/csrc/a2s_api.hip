@@ -264,6 +264,14 @@ int a2s_shift_bins(void* stream, const float* x, float* y, const float* eff_bins
     return a2s_shift_bins_impl(ST, x, y, eff_bins, B, rows, F);
 }
 int a2s_augment_launches(void) { return a2s_augment_launches_impl(); }
+int a2s_tempo_plan(void* stream, const float* x, int B, int rows, int F, const float* u, float R, int min_frames, int* content, int* step,
+                   int* counters) {
+    return a2s_tempo_plan_impl(ST, x, B, rows, F, u, R, min_frames, content, step, counters);
+}
+int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, int B, int rows, int F) {
+    return a2s_stretch_frames_impl(ST, x, y, step, B, rows, F);
+}
+int a2s_tempo_launches(void) { return a2s_tempo_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

@@ -239,6 +239,12 @@ int a2s_transpose_targets_impl(hipStream_t st, const int* new_key, const int* in
 int a2s_shift_bins_impl(hipStream_t st, const float* x, float* y, const float* eff_bins, int B, int rows, int F);
 int a2s_augment_launches_impl(void);
 
+// ---- a2s_tempo.hip
+int a2s_tempo_plan_impl(hipStream_t st, const float* x, int B, int rows, int F, const float* u, float R, int min_frames, int* content, int* step,
+    int* counters);
+int a2s_stretch_frames_impl(hipStream_t st, const float* x, float* y, const int* step, int B, int rows, int F);
+int a2s_tempo_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -344,6 +344,59 @@ def augment_launches():
     return int(lib().a2s_augment_launches())
 
 
+def tempo_plan(x, u, R, min_frames, content, step, counters):
+    """a2s_tempo_plan: x (B, ..., rows, F) float32, contiguous; u (B,) float32 in [0, 1), the host's draws; R in [0, 0.25] the largest relative change
+    of the durations, min_frames >= 1 the least content a stretched clip keeps.  content (B,) int32 receives 1 + the last non-zero row of every clip,
+    step (B,) int32 the Q16 source advance per output row that a2s_stretch_frames reads; counters (3,) int32 grow by [clips, stretched, kept]."""
+    fn = "tempo_plan"
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
+    _need(x.is_contiguous(), fn, "x", "must be contiguous")
+    B, F = x.shape[0], x.shape[-1]
+    for name, t, dtype in (("u", u, torch.float32), ("content", content, torch.int32), ("step", step, torch.int32)):
+        _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == (B,) and t.is_contiguous(), fn, name,
+              f"must be a contiguous {dtype} tensor with one element per clip ({B})")
+    _need(torch.is_tensor(counters) and counters.dtype == torch.int32 and counters.numel() == 3 and counters.is_contiguous(), fn, "counters",
+          "must be a contiguous int32 tensor of 3 elements")
+    try:
+        Rf, mf = float(R), int(min_frames)
+    except (TypeError, ValueError):
+        raise A2SError(f"{fn}: `R` and `min_frames` must be numbers (got {R!r}, {min_frames!r})") from None
+    _need(0.0 <= Rf <= 0.25, fn, "R", f"must be in 0 .. 0.25 (got {R!r})")
+    _need(mf >= 1 and mf == min_frames, fn, "min_frames", f"must be a whole number >= 1 (got {min_frames!r})")
+    if x.numel() == 0:
+        return
+    rows = x.numel() // (B * F)
+    _need(rows <= 16384, fn, "x", f"has {rows} rows per clip, more than 16384")
+    check(lib().a2s_tempo_plan(stream(), _p(x), B, rows, F, _p(u), Rf, mf, _p(content), _p(step), _p(counters)), "a2s_tempo_plan")
+
+
+def stretch_frames(x, step, y=None):
+    """a2s_stretch_frames: x (B, ..., rows, F) float32, contiguous -> y of the same shape (a fresh tensor when not given), the rows of clip b resampled
+    with the Q16 source advance step[b] per output row (int32 on the device; 65536: a copy; below: linear interpolation, the clip gets longer; above: a
+    widened tent, it gets shorter; outside 52429 .. 87381: zeros)."""
+    fn = "stretch_frames"
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
+    _need(x.is_contiguous(), fn, "x", "must be contiguous")
+    B, F = x.shape[0], x.shape[-1]
+    _need(torch.is_tensor(step) and step.dtype == torch.int32 and tuple(step.shape) == (B,) and step.is_contiguous(), fn, "step",
+          f"must be a contiguous int32 tensor with one element per clip ({B})")
+    if y is None:
+        y = torch.empty_like(x)
+    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
+    _need(y.device == x.device, fn, "y", "must be on x's device")
+    if x.numel() == 0:
+        return y
+    rows = x.numel() // (B * F)
+    _need(rows <= 16384, fn, "x", f"has {rows} rows per clip, more than 16384")
+    check(lib().a2s_stretch_frames(stream(), _p(x), _p(y), _p(step), B, rows, F), "a2s_stretch_frames")
+    return y
+
+
+def tempo_launches():
+    """Launches of the two tempo kernels in this process (a2s_tempo_launches; a2s_augment_launches does not count them)."""
+    return int(lib().a2s_tempo_launches())
+
+
 def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):
     """a2s_note_match: the note counts of n_pairs pairs of bar rows, one launch on the current stream.  ref / hyp (int32 ids) and ref_off / hyp_off
     (int64, n_pairs + 1 each) are device tensors or device addresses (ints: parts of one packed buffer, metrics.device_note_counts); dur_ticks, midi, cls

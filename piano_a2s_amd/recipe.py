@@ -160,17 +160,37 @@ class ASR(sb.Brain):
                                                          bins_per_octave=getattr(self.hparams, "bins_per_octave", 60), rank=rank)
         return self._augment
 
+    def _tempo_augment(self):
+        """--tempo_augment=R (an optional override as --transpose_augment): every TRAIN batch is time-stretched on the device, each clip by a factor
+        drawn in 1 - R .. 1 + R and narrowed so that its content stays inside the window (piano_a2s_amd.augment.TempoAugment; the targets stay).
+        -> the augmenter, or None when R is 0 (the default: nothing is built, nothing is launched).  A value out of range raises ValueError."""
+        if not hasattr(self, "_tempo"):
+            from piano_a2s_amd import augment
+            R = augment.check_tempo(getattr(self.hparams, "tempo_augment", 0.0))
+            self._tempo = None
+            if R:
+                model = self.modules.transcription
+                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
+                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
+                    raise ValueError(f"--tempo_augment needs a transcription module that states its `cfg['freq_bins']`; {type(model).__name__} does not")
+                import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                self._tempo = augment.TempoAugment(model.cfg, R, getattr(self.hparams, "seed", 0), self.device, rank=rank)
+        return self._tempo
+
     def _train_features(self, batch):
-        """`_features` of a TRAIN batch, augmented when the run asks for it.  The targets are rewritten in place: a tensor that was on the device
-        before (and so is the caller's own) is copied first."""
+        """`_features` of a TRAIN batch, augmented when the run asks for it: transposed first, then time-stretched.  The transposition rewrites the
+        targets in place: a tensor that was on the device before (and so is the caller's own) is copied first."""
         out = _features(batch, self.device)
-        aug = self._transpose_augment()
-        if aug is None:
-            return out
-        for i in (2, 3, 5):
-            if out[i] is batch[i]:
-                out[i] = out[i].clone()
-        return aug(out)
+        aug, tempo = self._transpose_augment(), self._tempo_augment()
+        if aug is not None:
+            for i in (2, 3, 5):
+                if out[i] is batch[i]:
+                    out[i] = out[i].clone()
+            out = aug(out)
+        if tempo is not None:
+            out = tempo(out)
+        return out
 
     def compute_objectives(self, predictions, batch, stage):
         batch = _to_device(batch, self.device)
@@ -259,6 +279,7 @@ class ASR(sb.Brain):
         lr is the truth, and the idle torch optimizer (which update_learning_rate also addresses) is brought in line with it -- without
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
         self._transpose_augment()                 # (a --transpose_augment / --detune_bins out of range is refused before anything else happens)
+        self._tempo_augment()                     # (and a --tempo_augment)
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
         fused = self._fused_step()
@@ -269,7 +290,7 @@ class ASR(sb.Brain):
     def fit_batch(self, batch):
         fused = self._fused_step()
         if not fused:
-            if self._transpose_augment() is not None:
+            if self._transpose_augment() is not None or self._tempo_augment() is not None:
                 # the generic path reads the batch twice (compute_forward, compute_objectives): both see the augmented device batch, which
                 # `_features` and `_to_device` pass through as it is
                 batch = self._train_features(batch)
@@ -306,6 +327,8 @@ class ASR(sb.Brain):
                                                "data_processing", "metadata", "time_signature_list.json"))
         if stage == sb.Stage.TRAIN and self._transpose_augment() is not None:
             self._augment.reseed(epoch)               # the draws of an epoch depend on (seed, rank, epoch) alone: a resumed run repeats them
+        if stage == sb.Stage.TRAIN and self._tempo_augment() is not None:
+            self._tempo.reseed(epoch)
         if stage != sb.Stage.TRAIN:
             self.teacher_forcing_ratio = 0.
         elif self.finetune:
@@ -323,6 +346,9 @@ class ASR(sb.Brain):
             if self._transpose_augment() is not None:
                 counts = self._augment.counts()                       # one small D2H per epoch; cumulative over the run, logged with the train stats
                 stats.update(augmented_clips=counts["clips"], transposed_clips=counts["transposed"], not_representable_clips=counts["not_representable"])
+            if self._tempo_augment() is not None:
+                counts = self._tempo.counts()                         # likewise: one small D2H per epoch, cumulative over the run
+                stats.update(tempo_clips=counts["clips"], tempo_stretched_clips=counts["stretched"], tempo_kept_clips=counts["kept"])
             return
         if not hasattr(self, "train_stats"):
             self.train_stats = {"loss": -1}
@@ -384,6 +410,9 @@ def write_run_summary(brain, hparams):
     extra = {}
     if aug is not None:
         extra["transpose_augment"] = dict(max_semitones=aug.K, detune_bins=aug.D, **aug.counts())
+    tempo = getattr(brain, "_tempo", None)
+    if tempo is not None:
+        extra["tempo_augment"] = dict(max_change=tempo.R, **tempo.counts())
     save({**extra, "fused_hip_step": bool(fused), "world_size": dist.get_world_size() if inited else 1, "backend": dist.get_backend() if inited else None,
           "optimizer_steps": int(getattr(brain, "step", 0)), "gradient_allreduces": int(fused.collectives) if fused else 0,
           "nonfinite_steps": int(getattr(brain, "nonfinite_count", 0)), "device": str(brain.device)},
