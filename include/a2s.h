@@ -418,6 +418,29 @@ int a2s_tempo_plan(void* stream, const float* x, int B, int rows, int F, const f
                    int* counters);
 int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, int B, int rows, int F);
 int a2s_tempo_launches(void);
+
+/* ---- room acoustics of the rendered synthetic corpus (csrc/a2s_room.hip): every clip's waveform is convolved with a synthetic
+ * impulse response of its own, between the synthesiser and the VQT.  Both entry points take borrowed device pointers and a stream; they allocate
+ * nothing, do not synchronise and read nothing back.  `params` = device, (B, 4) int32 per clip, computed by the host in float64:
+ *     [pre >= 1 (pre-delay in samples), L (taps), wet (float32 bits), decay per sample (float32 bits)];  the device clamps L to [1, L_max].
+ * a2s_room_ir writes ir[b * ir_bstride + k], k in [0, L_max), from `params` and the clips' 32-bit seeds (room_seed: device, B words):
+ *     1 at k = 0;  0 at 0 < k < pre and at k >= L;  wet * u(k) * exp(-(k - pre) * decay) at pre <= k < L,
+ *     u(k) = (hash32(room_seed[b] + (k + 3) * 0x9E3779B9) >> 8) * 2^-23 - 1  (hash32 as for a2s_render_notes).
+ * a2s_fir_rows is the direct-form convolution, out of place, in fp32 products and sums (FMAs, k ascending, one thread per sample's whole sum):
+ *     y[b * y_bstride + n] = sum_{k = 0 .. min(L - 1, n)} ir[b * ir_bstride + k] * x[b * x_bstride + n - k],   n in [0, n_samples),
+ * L = clamp(params[b * 4 + 1], 1, L_max): the history before sample 0 is zero and never read, ir at and behind L never reaches the result (it may hold
+ * anything), a short room costs less.  The output is not rescaled: |y| <= sum|ir| * max|x|.  ir is expected to be finite in [0, L): a tile skips the
+ * taps that meet nothing but the zero history.  A sample's bits do not depend on B, on the other clips, on n_samples or on the alignment of x and y
+ * (16-byte accesses where a row allows them, 4-byte ones otherwise).  Nothing outside [0, n_samples) of a clip's row of y is written, nothing outside
+ * [0, n_samples) of its row of x and [0, L) of its row of ir is read.  a2s_fir_tile_samples: samples per workgroup; a2s_fir_tap_chunk: taps per staged
+ * window of x.  Null pointers, B < 0 or > 65535, n_samples < 1, L_max < 1, x_bstride or y_bstride < n_samples, ir_bstride < L_max, x == y: A2S_ERR_ARG,
+ * nothing is launched; B = 0 returns 0 and launches nothing.  One launch per call each; a2s_room_launches: launches of the two so far. */
+int a2s_room_ir(void* stream, const unsigned* room_seed, const int* params, int B, float* ir, long ir_bstride, int L_max);
+int a2s_fir_rows(void* stream, const float* x, long x_bstride, const float* ir, long ir_bstride, const int* params, float* y, long y_bstride, int B,
+                 int n_samples, int L_max);
+int a2s_fir_tile_samples(void);
+int a2s_fir_tap_chunk(void);
+int a2s_room_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

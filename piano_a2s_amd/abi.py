@@ -13,7 +13,7 @@ class A2SError(RuntimeError):
 
 
 _SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
-_POINTEES = set(_SCALARS) | {"void", "uint8_t", "signed char"}          # what a data pointer may point to
+_POINTEES = set(_SCALARS) | {"void", "uint8_t", "signed char", "unsigned"}          # what a data pointer may point to
 _PROTO = re.compile(r"([\w\s*]+?)\b(a2s_\w+)\s*\(([^()]*)\)")
 _STRUCT = re.compile(r"typedef\s+struct\s+(a2s_\w+)\s*\{(.*?)\}\s*\1\s*;", re.S)
 _DECL = re.compile(r"(.*?)(\w+(?:\s*,\s*\w+)*)")                         # "<type> <name>[, <name>...]"

@@ -272,6 +272,16 @@ int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, 
     return a2s_stretch_frames_impl(ST, x, y, step, B, rows, F);
 }
 int a2s_tempo_launches(void) { return a2s_tempo_launches_impl(); }
+int a2s_room_ir(void* stream, const unsigned* room_seed, const int* params, int B, float* ir, long ir_bstride, int L_max) {
+    return a2s_room_ir_impl(ST, room_seed, params, B, ir, ir_bstride, L_max);
+}
+int a2s_fir_rows(void* stream, const float* x, long x_bstride, const float* ir, long ir_bstride, const int* params, float* y, long y_bstride, int B,
+                 int n_samples, int L_max) {
+    return a2s_fir_rows_impl(ST, x, x_bstride, ir, ir_bstride, params, y, y_bstride, B, n_samples, L_max);
+}
+int a2s_fir_tile_samples(void) { return a2s_fir_tile_samples_impl(); }
+int a2s_fir_tap_chunk(void) { return a2s_fir_tap_chunk_impl(); }
+int a2s_room_launches(void) { return a2s_room_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

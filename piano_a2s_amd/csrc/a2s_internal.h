@@ -245,6 +245,14 @@ int a2s_tempo_plan_impl(hipStream_t st, const float* x, int B, int rows, int F, 
 int a2s_stretch_frames_impl(hipStream_t st, const float* x, float* y, const int* step, int B, int rows, int F);
 int a2s_tempo_launches_impl(void);
 
+// ---- a2s_room.hip
+int a2s_room_ir_impl(hipStream_t st, const unsigned* room_seed, const int* params, int B, float* ir, long ir_bstride, int L_max);
+int a2s_fir_rows_impl(hipStream_t st, const float* x, long x_bstride, const float* ir, long ir_bstride, const int* params, float* y, long y_bstride, int B,
+                      int n_samples, int L_max);
+int a2s_fir_tile_samples_impl(void);
+int a2s_fir_tap_chunk_impl(void);
+int a2s_room_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

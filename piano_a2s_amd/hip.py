@@ -397,6 +397,75 @@ def tempo_launches():
     return int(lib().a2s_tempo_launches())
 
 
+def _room_table(fn, params, seeds=None):
+    _need(torch.is_tensor(params) and params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous() and params.is_cuda,
+          fn, "params", "must be a contiguous (B, 4) int32 tensor on the device: [pre, L, wet f32 bits, decay f32 bits] per clip")
+    if seeds is not None:
+        _need(torch.is_tensor(seeds) and seeds.dtype == torch.int32 and tuple(seeds.shape) == (params.shape[0],) and seeds.is_contiguous()
+              and seeds.device == params.device, fn, "seeds", f"must be a contiguous int32 tensor (the 32 bits of every clip's seed) of {params.shape[0]} elements on the table's device")
+    return params.shape[0]
+
+
+def _rows(fn, name, t, B, n, device):
+    _need(torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] >= B and t.shape[1] >= n and t.device == device
+          and (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= n), fn, name,
+          f"must be a float32 tensor of at least {B} rows of at least {n} elements with unit stride on the table's device")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), n)
+
+
+def room_ir(seeds, params, L_max, ir=None):
+    """a2s_room_ir: seeds (B,) int32 (the bits of the clips' 32-bit room seeds) and params (B, 4) int32 on the device -> ir (B, L_max) float32, the
+    impulse response of every clip (written into `ir`, a 2-D float32 tensor of at least L_max columns with unit column stride, when given)."""
+    fn = "room_ir"
+    B = _room_table(fn, params, seeds)
+    L_max = int(L_max)
+    _need(L_max >= 1, fn, "L_max", f"must be >= 1 (got {L_max})")
+    if ir is None:
+        ir = torch.empty((B, L_max), dtype=torch.float32, device=params.device)
+    stride = _rows(fn, "ir", ir, B, L_max, params.device)
+    if B == 0:
+        return ir
+    check(lib().a2s_room_ir(stream(), _p(seeds), _p(params), B, _p(ir), stride, L_max), "a2s_room_ir")
+    return ir
+
+
+def fir_rows(x, ir, params, L_max, y=None, n_samples=None):
+    """a2s_fir_rows: x (B, N) float32 waveforms, ir (B, >= L_max) float32 and params (B, 4) int32 on the device -> y (B, n_samples) float32 (a fresh
+    tensor when not given), y[b][n] = sum_{k <= min(L[b] - 1, n)} ir[b][k] x[b][n - k] with L[b] = clamp(params[b][1], 1, L_max).  Out of place."""
+    fn = "fir_rows"
+    B = _room_table(fn, params)
+    L_max = int(L_max)
+    _need(L_max >= 1, fn, "L_max", f"must be >= 1 (got {L_max})")
+    _need(torch.is_tensor(x) and x.dim() == 2, fn, "x", "must be a 2-D float32 tensor")
+    n = x.shape[1] if n_samples is None else int(n_samples)
+    _need(n >= 1 or B == 0, fn, "n_samples", f"must be >= 1 (got {n})")
+    xs = _rows(fn, "x", x, B, n, params.device)
+    irs = _rows(fn, "ir", ir, B, L_max, params.device)
+    if y is None:
+        y = torch.empty((B, n), dtype=torch.float32, device=params.device)
+    ys = _rows(fn, "y", y, B, n, params.device)
+    if B == 0:
+        return y
+    _need(x.data_ptr() != y.data_ptr(), fn, "y", "must not be x (the convolution works out of place)")
+    check(lib().a2s_fir_rows(stream(), _p(x), xs, _p(ir), irs, _p(params), _p(y), ys, B, n, L_max), "a2s_fir_rows")
+    return y
+
+
+def fir_tile_samples():
+    """Samples per workgroup of a2s_fir_rows."""
+    return int(lib().a2s_fir_tile_samples())
+
+
+def fir_tap_chunk():
+    """Taps per staged window of a2s_fir_rows."""
+    return int(lib().a2s_fir_tap_chunk())
+
+
+def room_launches():
+    """Launches of the two room kernels in this process (a2s_room_launches)."""
+    return int(lib().a2s_room_launches())
+
+
 def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):
     """a2s_note_match: the note counts of n_pairs pairs of bar rows, one launch on the current stream.  ref / hyp (int32 ids) and ref_off / hyp_off
     (int64, n_pairs + 1 each) are device tensors or device addresses (ints: parts of one packed buffer, metrics.device_note_counts); dur_ticks, midi, cls

@@ -27,25 +27,51 @@ def _to_device(batch, device):
 _VQT = {}
 
 
-def _features(batch, device):
+def _features(batch, device, room=None):
     """Online front-end: when the loader yields raw 16 kHz waveforms (B, N) instead of cached spectrograms
     (B, 1, T, F), the VQT runs on the GPU in front of the model (piano_a2s_amd.vqt; the reference caches librosa features offline).  When it yields
-    render programs (B, 1 + E, 8) int32, the waveforms are synthesised on the GPU first (piano_a2s_amd.render)."""
+    render programs (B, 1 + E, 8) int32, the waveforms are synthesised on the GPU first (piano_a2s_amd.render) and, with a `room`
+    (piano_a2s_amd.room.Room, --synthetic_room), convolved with every clip's own impulse response before the VQT."""
     rendered = torch.is_tensor(batch[0]) and batch[0].dim() == 3 and batch[0].dtype == torch.int32
     if rendered:
         # rendered synthetic corpus (datasets.syn.RenderedClips): render programs (B, 1 + E, 8) -> waveforms, synthesised on the GPU; the clip length
-        # is taken from the headers while the programs are still on the host (nothing is read back from the device)
+        # and the room seeds are taken from the headers while the programs are still on the host (nothing is read back from the device)
         from piano_a2s_amd.render import program_samples, render
         n_samples = program_samples(batch[0])
+        if room is not None:
+            from piano_a2s_amd.room import room_seeds
+            seeds = room_seeds(batch[0])
     batch = _to_device(batch, device)
     if rendered:
         batch[0] = render(batch[0], n_samples)
+        if room is not None:
+            batch[0] = room.apply(batch[0], seeds)
     if torch.is_tensor(batch[0]) and batch[0].dim() == 2:
         from piano_a2s_amd.vqt import VQT
         if device not in _VQT:
             _VQT[device] = VQT(torch.device(device))
         batch[0] = _VQT[device](batch[0])
     return batch
+
+
+def _hp(hparams, key, default=None):
+    return hparams.get(key, default) if isinstance(hparams, dict) else getattr(hparams, key, default)
+
+
+def synthetic_room(hparams):
+    """--synthetic_room=none|train|eval|all [--room_rt60="(lo, hi)" --room_drr_db="(lo, hi)" --room_predelay_ms="(lo, hi)"] (optional overrides, like
+    --synthetic_scores): the clips of the rendered corpus are heard in a synthetic room of their own in the TRAIN stage, in VALID and TEST, or in all
+    three (piano_a2s_amd.room).  -> (mode, Room), or None for none (the default: nothing is built, nothing is launched).  A value
+    out of range, or a room without --synthetic_scores=rendered, raises ValueError."""
+    from piano_a2s_amd import room
+    mode = room.check_stages(_hp(hparams, "synthetic_room"))
+    if mode == "none":
+        return None
+    if str(_hp(hparams, "synthetic_scores") or "random").strip().lower() != "rendered" or not int(_hp(hparams, "synthetic_clips", 0) or 0):
+        raise ValueError(f"--synthetic_room={mode} needs the rendered corpus (--synthetic_clips=N --synthetic_scores=rendered): only its clips have a waveform "
+                         "that is made on the device")
+    ranges = {k: _hp(hparams, "room_" + k) for k in ("rt60", "drr_db", "predelay_ms")}
+    return mode, room.Room(sample_rate=int(_hp(hparams, "sample_rate", 16000)), **{k: v for k, v in ranges.items() if v is not None})
 
 
 def synthetic_sets(hparams, n_syn, test_offset=20_000, online_vqt=True):
@@ -67,6 +93,7 @@ def synthetic_sets(hparams, n_syn, test_offset=20_000, online_vqt=True):
             syn.update(upper_range=tuple(hparams["synthetic_lengths"][0]), lower_range=tuple(hparams["synthetic_lengths"][1]))
     else:
         raise ValueError(f"--synthetic_scores must be 'random' or 'rendered' (got {scores!r})")
+    synthetic_room(hparams)                   # (a --synthetic_room that is out of range or lacks the rendered corpus is refused before any set is made)
     train_set = cls(cfg, n_syn, seed=hparams["seed"], **syn)
     valid_set = cls(cfg, max(1, n_syn // 8), seed=hparams["seed"] + 10_000, **syn)
     test_set = valid_set if test_offset is None else cls(cfg, max(1, n_syn // 8), seed=hparams["seed"] + test_offset, **syn)
@@ -78,7 +105,7 @@ class ASR(sb.Brain):
 
     # ------------------------------------------------------------------ forward / objective
     def compute_forward(self, batch, stage):
-        batch = _features(batch, self.device)
+        batch = _features(batch, self.device, room=self._room(stage))
         spectrogram, ts_t, key_t, up_t, up_len, lo_t, lo_len = batch[:7]
         if stage == sb.Stage.TRAIN:
             return self.modules.transcription(spectrogram=spectrogram, inference=False,
@@ -178,10 +205,22 @@ class ASR(sb.Brain):
                 self._tempo = augment.TempoAugment(model.cfg, R, getattr(self.hparams, "seed", 0), self.device, rank=rank)
         return self._tempo
 
+    def _room(self, stage):
+        """--synthetic_room (`synthetic_room` above): the Room the batches of `stage` go through, or None.  Built on first use and kept: its count of
+        clips and its device buffers belong to the run."""
+        if not hasattr(self, "_synthetic_room"):
+            self._synthetic_room = synthetic_room(self.hparams)
+        if self._synthetic_room is None:
+            return None
+        from piano_a2s_amd.room import STAGES
+        mode, room = self._synthetic_room
+        name = {sb.Stage.TRAIN: "train", sb.Stage.VALID: "valid", sb.Stage.TEST: "test"}[stage]
+        return room if name in STAGES[mode] else None
+
     def _train_features(self, batch):
         """`_features` of a TRAIN batch, augmented when the run asks for it: transposed first, then time-stretched.  The transposition rewrites the
         targets in place: a tensor that was on the device before (and so is the caller's own) is copied first."""
-        out = _features(batch, self.device)
+        out = _features(batch, self.device, room=self._room(sb.Stage.TRAIN))
         aug, tempo = self._transpose_augment(), self._tempo_augment()
         if aug is not None:
             for i in (2, 3, 5):
@@ -280,6 +319,7 @@ class ASR(sb.Brain):
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
         self._transpose_augment()                 # (a --transpose_augment / --detune_bins out of range is refused before anything else happens)
         self._tempo_augment()                     # (and a --tempo_augment)
+        self._room(sb.Stage.TRAIN)                # (and a --synthetic_room)
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
         fused = self._fused_step()
@@ -413,6 +453,9 @@ def write_run_summary(brain, hparams):
     tempo = getattr(brain, "_tempo", None)
     if tempo is not None:
         extra["tempo_augment"] = dict(max_change=tempo.R, **tempo.counts())
+    room = getattr(brain, "_synthetic_room", None)
+    if room is not None:
+        extra["room"] = dict(stages=room[0], clips=room[1].clips, **room[1].describe())
     save({**extra, "fused_hip_step": bool(fused), "world_size": dist.get_world_size() if inited else 1, "backend": dist.get_backend() if inited else None,
           "optimizer_steps": int(getattr(brain, "step", 0)), "gradient_allreduces": int(fused.collectives) if fused else 0,
           "nonfinite_steps": int(getattr(brain, "nonfinite_count", 0)), "device": str(brain.device)},

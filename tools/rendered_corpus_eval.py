@@ -10,7 +10,13 @@
    section 17) of every decoding mode beside its WER;
 3. reports the mean absolute difference between the forced-alignment centroids (teacher-forced forward over the true score) and the true onsets;
 4. writes the JSON.
-No threshold is applied to anything: the file records what the run shows."""
+No threshold is applied to anything: the file records what the run shows.
+
+    python tools/rendered_corpus_eval.py --room [--model small --steps 200 --batch 32 ...] [--out profiles/rendered_corpus_room.json]
+
+--room replaces 1 to 3: from the same initial weights and on the same training clips one model is trained dry and one with every
+clip in its own synthetic room (piano_a2s_amd.room.Room, the default ranges); each model is then scored on the same held-out clips, once dry and
+once in their rooms: the teacher-forced loss (its four terms summed, evaluation mode) and the key F1 of greedy decoding."""
 import argparse
 import json
 import os
@@ -29,26 +35,30 @@ def _batches(ds, batch, workers):
     return DataLoader(ds, batch_size=batch, shuffle=False, num_workers=workers, drop_last=True)
 
 
-def _features(batch, dev, front, permute=False):
+def _features(batch, dev, front, permute=False, room=None):
     from piano_a2s_amd.render import render
-    x = front(render(batch[0].to(dev)))
+    wave = render(batch[0].to(dev))
+    if room is not None:
+        from piano_a2s_amd.room import room_seeds
+        wave = room.apply(wave, room_seeds(batch[0]))
+    x = front(wave)
     if permute:
         x = torch.roll(x, 1, dims=0)                                       # clip b hears clip b - 1
     return [x] + [t.to(dev) for t in batch[1:7]]
 
 
-def _train(model, ds, args, dev, front, permute):
+def _train(model, ds, args, dev, front, permute, room=None, tag=None):
     from piano_a2s_amd import train
     model.train()
     step = train.TrainStep(model)
     rng = random.Random(args.seed)
     curve, t0 = [], time.perf_counter()
     for k, batch in enumerate(_batches(ds, args.batch, args.workers)):
-        terms = step(_features(batch, dev, front, permute), args.teacher_forcing, rng=rng)
+        terms = step(_features(batch, dev, front, permute, room), args.teacher_forcing, rng=rng)
         if k % args.log_every == 0 or k == args.steps - 1:
             t = terms[:, 0].tolist()
             curve.append({"step": k, "time_sig": t[0], "key": t[1], "upper": t[2], "lower": t[3], "loss": sum(t)})
-            print(f"{'control' if permute else 'matched'} step {k}: loss {sum(t):.4f} (ts {t[0]:.3f} key {t[1]:.3f} up {t[2]:.3f} lo {t[3]:.3f})", flush=True)
+            print(f"{tag or ('control' if permute else 'matched')} step {k}: loss {sum(t):.4f} (ts {t[0]:.3f} key {t[1]:.3f} up {t[2]:.3f} lo {t[3]:.3f})", flush=True)
     torch.cuda.synchronize()
     return curve, time.perf_counter() - t0
 
@@ -113,6 +123,46 @@ def _alignment_error(model, ds, args, dev, front):
     return {k: (float(np.mean(v)) if v else None) for k, v in err.items()} | {"tokens": len(err["upper"]) + len(err["lower"])}
 
 
+def _room_score(model, ds, args, dev, front, room):
+    """Teacher-forced loss (mean over the batches of the four NLL terms summed, evaluation mode) and key F1 of greedy decoding on the clips of `ds`,
+    dry (room None) or each in its own room."""
+    import torch.nn.functional as F
+    from piano_a2s_amd import metrics
+    model.eval()
+    model.constrained_decoding, model.beam_size, model.alignment = False, 1, False
+    losses, pred, target = [], {}, {}
+    flat = lambda o, t: (o.reshape(-1, o.shape[-1]), t.reshape(-1))
+    with torch.no_grad():
+        for batch in _batches(ds, args.eval_batch, 0):
+            f = _features(batch, dev, front, room=room)
+            outs = model(f[0], inference=False, ground_truth=f[1:7], teacher_forcing_ratio=1.0)
+            targets = (f[1], f[2], f[3], f[5])
+            # the recipe's objective (hparams/pretrain.yaml): NLL of the four outputs, the score terms without their padding (id 147)
+            losses.append(sum(float(F.nll_loss(*flat(o, t), ignore_index=pad)) for o, t, pad in zip(outs, targets, (-100, -100, 147, 147))))
+            key_o = model(f[0], inference=True)[1]
+            for b, name in enumerate(batch[7]):
+                pred[name], target[name] = key_o[b].argmax(-1).cpu().tolist(), batch[2][b].tolist()
+    return {"teacher_forced_loss": float(np.mean(losses)), "key_f1": metrics.corpus_f1(pred, target)[0]}
+
+
+def _room_runs(args, cfg, init, train_set, held_out, dev, front, res):
+    import models
+    from piano_a2s_amd import hip
+    from piano_a2s_amd.room import Room
+    res["room"] = Room().describe()
+    for name, trained_in_rooms in (("trained_dry", False), ("trained_in_rooms", True)):
+        model = models.ScoreTranscription(**cfg)
+        model.load_state_dict(init)
+        model = model.to(dev)
+        curve, seconds = _train(model, train_set, args, dev, front, False, room=Room() if trained_in_rooms else None, tag=name)
+        run = {"loss_curve": curve, "train_seconds": seconds}
+        for cond, room in (("held_out_dry", None), ("held_out_in_rooms", Room())):
+            run[cond] = _room_score(model, held_out, args, dev, front, room)
+            print(name, cond, json.dumps(run[cond]), flush=True)
+        res["runs"][name] = run
+    res["room_launches"] = hip.room_launches()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("small", "full"), default="small")
@@ -127,6 +177,7 @@ def main():
     ap.add_argument("--log_every", type=int, default=10)
     ap.add_argument("--no_control", action="store_true")
     ap.add_argument("--note_metrics", action="store_true")
+    ap.add_argument("--room", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import models
@@ -142,7 +193,9 @@ def main():
            "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "note_metrics": args.note_metrics, "runs": {}}
     torch.manual_seed(args.seed)
     init = {k: v.clone() for k, v in models.ScoreTranscription(**cfg).state_dict().items()}
-    for name, permute in (("matched", False),) + (() if args.no_control else (("control_permuted_audio", True),)):
+    if args.room:
+        _room_runs(args, cfg, init, train_set, held_out, dev, front, res)
+    for name, permute in () if args.room else (("matched", False),) + (() if args.no_control else (("control_permuted_audio", True),)):
         model = models.ScoreTranscription(**cfg)
         model.load_state_dict(init)
         model = model.to(dev)
