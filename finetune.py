@@ -5,7 +5,9 @@ As the reference's finetune.py (:230-294): starts from the pre-training checkpoi
 output folder and resetting their recorded WER so that the first fine-tuned epoch is kept; fixed teacher-forcing ratio; the test
 split doubles as validation split.  ``--constrained_decoding=true``, ``--beam_size=K [--beam_length_penalty=A]``, ``--note_metrics=true``, ``--synthetic_scores=rendered`` and
 ``--transpose_augment=K [--detune_bins=D]`` as in pretrain.py;
-``--tempo_augment=R`` likewise: the one variation a fine-tuning corpus of recordings otherwise lacks, each clip being heard at exactly one tempo.
+``--tempo_augment=R`` likewise: the one variation a fine-tuning corpus of recordings otherwise lacks, each clip being heard at exactly one tempo;
+``--eq_augment_db=E --noise_augment_db="(lo, hi)" --mask_time=Wt --mask_freq=Wf [--mask_count=m]`` likewise: microphone and instrument response, noise floor and missing stretches
+of time or frequency, applied to the precomputed feature files' rows on the GPU (TRAIN batches only).
 Optional override of the rendered corpus: ``--synthetic_room=none|train|eval|all [--room_rt60="(lo, hi)" --room_drr_db="(lo, hi)" --room_predelay_ms="(lo, hi)"]``
 (with ``--synthetic_scores=rendered`` only: every clip is heard in a synthetic room of its own -- direct path, pre-delay, decaying diffuse tail, drawn from the
 clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none)."""

@@ -419,6 +419,35 @@ int a2s_tempo_plan(void* stream, const float* x, int B, int rows, int F, const f
 int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, int B, int rows, int F);
 int a2s_tempo_launches(void);
 
+/* ---- spectrogram augmentation of a training batch (csrc/a2s_specaug.hip): per clip a per-bin gain that respects the front
+ * end's floor, an additive noise floor, the front end's re-normalisation, and masks along time and frequency; the targets stay.  Both entry points take
+ * borrowed device pointers and a stream; they allocate nothing, do not synchronise and read nothing back.  x (B, rows, F) float32, contiguous, holds
+ * dB / 80 + 1 relative to the clip's peak: P(x) = 10^(8 (x - 1)) is a cell's power relative to that peak.  Per clip b:
+ *     n = content[b] = 1 + the last row that holds a value != 0 (a2s_tempo_plan's rule: a NaN is content, -0.0 is not, 0 for an all-zero clip);
+ *     x_min = min of x over rows < n;  a cell is at the floor iff x - x_min <= 2^-18 (in fp32);  p_min = P(x_min);
+ *     y = max(p_min, q + v_k),  q = 0 for a floor cell, else G_k * P(x);  M = max of y over rows < n;
+ *     out = clamp(1 + log10(y / M) / 8, 0, 1): the cell that attains M comes out as exactly 1.0;
+ *     then exact 0.0 in the rows >= n, in the rows [t0_i, t0_i + w_i) and, in rows < n, in the bins [k0_i, k0_i + wk_i), i < 4.
+ * table (B, 2, F) float32: per clip the power gains G_k > 0, then the noise powers v_k >= 0 (relative to the clip's peak).
+ * a2s_specaug_plan, one workgroup per clip, which sweeps its clip twice (x_min, then M): content (B,) int32, stats (B, 2) float32 = [x_min, M]
+ * ([0, 0] for an all-zero clip), plan (B, 16) int32 = 4 x [t0, w] then 4 x [k0, wk], from draws (B, 16) 32-bit words, four per mask (u0 .. u3),
+ * in integer arithmetic with 64-bit products:
+ *     wmax_t = min(Wt, n / 5),  w  = (u0 * (wmax_t + 1)) >> 32,  t0 = (u1 * (n - w  + 1)) >> 32;
+ *     wmax_f = min(Wf, F / 5),  wk = (u2 * (wmax_f + 1)) >> 32,  k0 = (u3 * (F - wk + 1)) >> 32;     masks i >= m: [0, 0].
+ * counters[0 .. 2] (device int32; global atomic adds) grow by: clips seen, clips with a time mask of width > 0, clips with a frequency mask of width
+ * > 0.  Null pointers, B < 0 or > 65535, rows < 1, F < 1, Wt < 0, Wf < 0, m < 0 or > 4: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches
+ * nothing.
+ * a2s_specaug_apply writes out (above) to y, out of place: x != y, same shape; table, content, plan and stats as the plan left them (content[b] is
+ * clamped to [0, rows] before it bounds a load).  Nothing outside the B * rows * F floats of y is written and nothing outside those of x is read.
+ * 16-byte loads and stores when F % 4 == 0 and y is 16-byte aligned, 4-byte ones otherwise.  A clip's output bits do not depend on B or on its
+ * position in the batch.  Null pointers, x == y, B < 0 or > 65535, rows < 1, F < 1: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches
+ * nothing.  One launch per call each; a2s_specaug_launches: launches of the two so far (a2s_augment_launches and a2s_tempo_launches do not count them). */
+int a2s_specaug_plan(void* stream, const float* x, int B, int rows, int F, const float* table, const unsigned* draws, int Wt, int Wf, int m,
+                     int* content, int* plan, float* stats, int* counters);
+int a2s_specaug_apply(void* stream, const float* x, float* y, const float* table, const int* content, const int* plan, const float* stats, int B,
+                      int rows, int F);
+int a2s_specaug_launches(void);
+
 /* ---- room acoustics of the rendered synthetic corpus (csrc/a2s_room.hip): every clip's waveform is convolved with a synthetic
  * impulse response of its own, between the synthesiser and the VQT.  Both entry points take borrowed device pointers and a stream; they allocate
  * nothing, do not synchronise and read nothing back.  `params` = device, (B, 4) int32 per clip, computed by the host in float64:

@@ -1,4 +1,5 @@
-"""Augmentation of a training batch on the device: transposition and tempo (section 18, at the end of this file).
+"""Augmentation of a training batch on the device: transposition, tempo (section 18) and the spectrogram's colour, noise floor and
+masks (section 20, at the end of this file).
 
 Transposition: per clip a whole number of semitones s and a detuning of
 delta feature bins are drawn on the host; csrc/a2s_augment.hip respells the targets (kern_transpose's tables) and shifts the feature rows by
@@ -181,3 +182,144 @@ class TempoAugment:
             return dict(clips=0, stretched=0, kept=0)
         c = self._counters.tolist()
         return dict(clips=c[0], stretched=c[1], kept=c[2])
+
+
+MAX_EQ_DB = 12.0
+NOISE_DB_RANGE = (20.0, 80.0)
+MAX_MASK_TIME, MAX_MASK_FREQ, MAX_MASKS = 100, 60, 4
+NOISE_TILT_DB_PER_OCTAVE = 3.0
+_SPECAUG_STREAM = 0x73706563          # "spec": the third augmenter's seed sequence is neither the transposer's nor the tempo generator's
+
+
+def _whole(flag, value, lo, hi):
+    try:
+        n = int(value)
+        ok = n == float(value)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"--{flag} must be a whole number (got {value!r})") from None
+    if not ok or not lo <= n <= hi:
+        raise ValueError(f"--{flag} must be a whole number in {lo} .. {hi} (got {value!r})")
+    return n
+
+
+def check_specaug(eq_db=0.0, noise_db=None, mask_time=0, mask_freq=0, mask_count=2):
+    """(E, (lo, hi) or None, Wt, Wf, m) as numbers, or ValueError naming the flag: 0 <= E <= 12 dB; the noise floor lo .. hi dB below the clip's peak,
+    20 <= lo <= hi <= 80 (a string "(lo, hi)" or two numbers; None: off); Wt in 0 .. 100 frames; Wf in 0 .. 60 bins; m in 1 .. 4."""
+    try:
+        E = float(eq_db)
+    except (TypeError, ValueError):
+        raise ValueError(f"--eq_augment_db must be a number (got {eq_db!r})") from None
+    if not 0.0 <= E <= MAX_EQ_DB:          # (also a NaN)
+        raise ValueError(f"--eq_augment_db must be in 0 .. {MAX_EQ_DB} (got {eq_db!r})")
+    noise = None
+    if noise_db is not None:
+        value = noise_db.strip().strip("()[]").split(",") if isinstance(noise_db, str) else noise_db
+        try:
+            lo, hi = (float(v) for v in value)
+        except (TypeError, ValueError):
+            raise ValueError(f"--noise_augment_db must be a range \"(lo, hi)\" of two numbers (got {noise_db!r})") from None
+        if not NOISE_DB_RANGE[0] <= lo <= hi <= NOISE_DB_RANGE[1]:
+            raise ValueError(f"--noise_augment_db must be a range (lo, hi) with {NOISE_DB_RANGE[0]} <= lo <= hi <= {NOISE_DB_RANGE[1]} (got ({lo}, {hi}))")
+        noise = (lo, hi)
+    return E, noise, _whole("mask_time", mask_time, 0, MAX_MASK_TIME), _whole("mask_freq", mask_freq, 0, MAX_MASK_FREQ), _whole("mask_count", mask_count, 1, MAX_MASKS)
+
+
+def specaug_table(F, e, phi, level_db, tilt, bins_per_octave, eq=True, noise=True):
+    """One clip's table (2, F) float32 from its draws, formed in float64 (tests/specaug_oracle.py restates it): row 0 the power
+    gains G_k = 10^(g_k / 10), g_k = e0 (2z - 1) + e1 cos 2 pi (z + phi1) + e2 cos 2 pi (2z + phi2) dB with z = k / (F - 1); row 1 the noise powers
+    v_k = 10^((-level_db + tilt (k - (F - 1) / 2) / bins_per_octave) / 10).  eq / noise False: G = 1 / v = 0."""
+    k = np.arange(F, dtype=np.float64)
+    z = k / (F - 1) if F > 1 else np.full(1, 0.5)
+    out = np.empty((2, F), dtype=np.float64)
+    g = e[0] * (2.0 * z - 1.0) + e[1] * np.cos(2.0 * np.pi * (z + phi[0])) + e[2] * np.cos(2.0 * np.pi * (2.0 * z + phi[1]))
+    out[0] = 10.0 ** (g / 10.0) if eq else 1.0
+    out[1] = 10.0 ** ((-level_db + tilt * (k - (F - 1) / 2.0) / bins_per_octave) / 10.0) if noise else 0.0
+    return out.astype(np.float32)
+
+
+class SpecAugment:
+    """Spectrogram augmentation: per clip a smooth equaliser curve of at most eq_db dB applied as a per-bin gain that respects
+    the front end's floor, a tilted noise floor noise_db = (lo, hi) dB below the clip's peak, the front end's re-normalisation to the new peak, and
+    mask_count masks of up to mask_time frames and mask_freq bins each (SpecAugment), by csrc/a2s_specaug.hip.  No target changes.
+
+    cfg: the transcription module's configuration (freq_bins); seed: the run's; device: where the batches live.  The host draws the curve, the noise
+    level and tilt and sixteen 32-bit words per clip from the object's own Generator (seeded from (seed, rank, epoch) and a constant of its own), every
+    quantity for every clip whether its component is on or not; content, floor, peak and the masks' places are found on the device: nothing is read
+    back."""
+
+    def __init__(self, cfg, eq_db=0.0, noise_db=None, mask_time=0, mask_freq=0, mask_count=2, seed=0, device="cpu", bins_per_octave=60, rank=0):
+        self.E, self.noise, self.Wt, self.Wf, self.m = check_specaug(eq_db, noise_db, mask_time, mask_freq, mask_count)
+        self.freq_bins = int(cfg["freq_bins"])
+        self.bins_per_octave = float(bins_per_octave)
+        if not self.bins_per_octave >= 1:
+            raise ValueError(f"spectrogram augmentation: bins_per_octave must be >= 1 (got {bins_per_octave!r})")
+        self.seed, self.rank = int(seed), int(rank)
+        self.device = torch.device(device)
+        self._rng = None
+        self._counters = None
+        self.last_plan = None
+        self.reseed(0, self.rank)
+
+    @property
+    def active(self):
+        """Whether any component is on (the recipe builds no augmenter otherwise)."""
+        return bool(self.E > 0 or self.noise is not None or self.Wt > 0 or self.Wf > 0)
+
+    def reseed(self, epoch, rank=None):
+        """The draws that follow are a function of (seed, rank, epoch) alone."""
+        if rank is not None:
+            self.rank = int(rank)
+        self._rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.seed & 0xFFFFFFFFFFFFFFFF, self.rank, int(epoch or 0), _SPECAUG_STREAM])))
+
+    def draw_raw(self, B):
+        """The next batch's draws as they leave the generator, in this fixed order: e (B, 3) in [-1, 1), phi (B, 2) in [0, 1), the noise level's
+        u (B,) in [0, 1), the tilt's (B,) in [-1, 1), words (B, 16) uint32.  Nothing depends on which components are on."""
+        rng = self._rng
+        return (rng.uniform(-1.0, 1.0, size=(B, 3)), rng.random(size=(B, 2)), rng.random(size=B), rng.uniform(-1.0, 1.0, size=B),
+                rng.integers(0, 2 ** 32, size=(B, 16), dtype=np.uint32))
+
+    def draw(self, B):
+        """(table (B, 2, F) float32, draws (B, 16) uint32) of the next batch; host only."""
+        e, phi, ul, ut, words = self.draw_raw(B)
+        lo, hi = self.noise if self.noise is not None else NOISE_DB_RANGE
+        table = np.empty((B, 2, self.freq_bins), dtype=np.float32)
+        for b in range(B):
+            table[b] = specaug_table(self.freq_bins, e[b] * (self.E / 3.0), phi[b], lo + ul[b] * (hi - lo), ut[b] * NOISE_TILT_DB_PER_OCTAVE,
+                                     self.bins_per_octave, eq=self.E > 0, noise=self.noise is not None)
+        return table, words
+
+    def apply(self, batch, table, draws):
+        """The batch (features (B, 1, T, F) float32 on the device first) under the given table and draws: two launches on the current stream.  Returns
+        the batch with a NEW feature tensor; everything else is the same objects, untouched."""
+        from piano_a2s_amd import hip
+        batch = list(batch)
+        x = batch[0]
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[-1] != self.freq_bins:
+            raise A2SError(f"SpecAugment: expects features (B, 1, T, {self.freq_bins}), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        B = x.shape[0]
+        table, draws = np.asarray(table), np.asarray(draws)
+        if table.shape != (B, 2, self.freq_bins) or draws.shape != (B, 16):
+            raise A2SError(f"SpecAugment: a table of shape {table.shape} and draws of shape {draws.shape} for {B} clips of {self.freq_bins} bins")
+        if self._counters is None:
+            self._counters = torch.zeros(3, dtype=torch.int32, device=self.device)
+        # pinned staging from the caching host allocator: it keeps a block until the copy that reads it has run
+        t_dev = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)).pin_memory().to(self.device, non_blocking=True)
+        d_dev = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.uint32).view(np.int32)).pin_memory().to(self.device, non_blocking=True)
+        content = torch.empty(B, dtype=torch.int32, device=self.device)
+        plan = torch.empty((B, 16), dtype=torch.int32, device=self.device)
+        stats = torch.empty((B, 2), dtype=torch.float32, device=self.device)
+        x = x.contiguous()
+        hip.specaug_plan(x, t_dev, d_dev, self.Wt, self.Wf, self.m, content, plan, stats, self._counters)
+        batch[0] = hip.specaug_apply(x, t_dev, content, plan, stats)          # one fresh tensor per batch, as the un-augmented path's input is
+        self.last_plan = (content, plan, stats)          # (device tensors; reading them synchronises -- tests and tools only)
+        return batch
+
+    def __call__(self, batch):
+        return self.apply(batch, *self.draw(batch[0].shape[0]))
+
+    def counts(self):
+        """{clips, time_masked, freq_masked} so far: one device-to-host copy."""
+        if self._counters is None:
+            return dict(clips=0, time_masked=0, freq_masked=0)
+        c = self._counters.tolist()
+        return dict(clips=c[0], time_masked=c[1], freq_masked=c[2])

@@ -272,6 +272,15 @@ int a2s_stretch_frames(void* stream, const float* x, float* y, const int* step, 
     return a2s_stretch_frames_impl(ST, x, y, step, B, rows, F);
 }
 int a2s_tempo_launches(void) { return a2s_tempo_launches_impl(); }
+int a2s_specaug_plan(void* stream, const float* x, int B, int rows, int F, const float* table, const unsigned* draws, int Wt, int Wf, int m,
+                     int* content, int* plan, float* stats, int* counters) {
+    return a2s_specaug_plan_impl(ST, x, B, rows, F, table, draws, Wt, Wf, m, content, plan, stats, counters);
+}
+int a2s_specaug_apply(void* stream, const float* x, float* y, const float* table, const int* content, const int* plan, const float* stats, int B,
+                      int rows, int F) {
+    return a2s_specaug_apply_impl(ST, x, y, table, content, plan, stats, B, rows, F);
+}
+int a2s_specaug_launches(void) { return a2s_specaug_launches_impl(); }
 int a2s_room_ir(void* stream, const unsigned* room_seed, const int* params, int B, float* ir, long ir_bstride, int L_max) {
     return a2s_room_ir_impl(ST, room_seed, params, B, ir, ir_bstride, L_max);
 }

@@ -245,6 +245,41 @@ int a2s_tempo_plan_impl(hipStream_t st, const float* x, int B, int rows, int F, 
 int a2s_stretch_frames_impl(hipStream_t st, const float* x, float* y, const int* step, int B, int rows, int F);
 int a2s_tempo_launches_impl(void);
 
+// the backward content scan of tempo_plan and specaug_plan, one workgroup of THREADS threads per clip xb (rows, F): 1 + the last row that holds a value
+// != 0 (true for a NaN, false for -0.0), 0 for an all-zero clip, the same in every thread.  Chunks of A2S_CONTENT_CHUNK rows from the last row backwards,
+// up to the first chunk with content.  Loads at [0, rows * F) of xb only; s_last is one int of the caller's LDS.
+#define A2S_CONTENT_CHUNK 16
+#ifdef __HIPCC__
+template <int THREADS>
+__device__ __forceinline__ int a2s_content_rows(const float* __restrict__ xb, int rows, int F, int* s_last) {
+    const int tid = threadIdx.x;
+    for (int r1 = rows; r1 > 0; r1 -= A2S_CONTENT_CHUNK) {
+        const int r0 = r1 > A2S_CONTENT_CHUNK ? r1 - A2S_CONTENT_CHUNK : 0;
+        const float* xc = xb + (long)r0 * F;
+        const long len = (long)(r1 - r0) * F;
+        long last = -1;
+#pragma unroll 4
+        for (long i = tid; i < len; i += THREADS)
+            if (xc[i] != 0.0f) last = i;          // (true for a NaN, false for -0.0)
+        if (tid == 0) *s_last = -1;
+        __syncthreads();
+        if (last >= 0) atomicMax(s_last, (int)(last / F));
+        __syncthreads();
+        const int got = *s_last;
+        __syncthreads();                          // (thread 0 resets s_last in the next chunk)
+        if (got >= 0) return r0 + got + 1;
+    }
+    return 0;
+}
+#endif
+
+// ---- a2s_specaug.hip
+int a2s_specaug_plan_impl(hipStream_t st, const float* x, int B, int rows, int F, const float* table, const unsigned* draws, int Wt, int Wf, int m,
+    int* content, int* plan, float* stats, int* counters);
+int a2s_specaug_apply_impl(hipStream_t st, const float* x, float* y, const float* table, const int* content, const int* plan, const float* stats, int B,
+    int rows, int F);
+int a2s_specaug_launches_impl(void);
+
 // ---- a2s_room.hip
 int a2s_room_ir_impl(hipStream_t st, const unsigned* room_seed, const int* params, int B, float* ir, long ir_bstride, int L_max);
 int a2s_fir_rows_impl(hipStream_t st, const float* x, long x_bstride, const float* ir, long ir_bstride, const int* params, float* y, long y_bstride, int B,

@@ -31,7 +31,7 @@
 #define TP_MIN_STEP 52429      // rint(65536 / 1.25)
 #define TP_MAX_STEP 87381      // rint(65536 / 0.75)
 #define TP_THREADS 256
-#define TP_CHUNK 16
+#define TP_CHUNK A2S_CONTENT_CHUNK          // (the scan itself: a2s_content_rows, a2s_internal.h)
 #define SF_TX 128
 #define SF_TY 2
 #define SF_ROWS 16
@@ -45,23 +45,7 @@ __global__ __launch_bounds__(TP_THREADS) void tempo_plan(const float* __restrict
     __shared__ int s_last;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* xb = x + (long)b * rows * F;
-    int n = 0;
-    for (int r1 = rows; r1 > 0; r1 -= TP_CHUNK) {
-        const int r0 = r1 > TP_CHUNK ? r1 - TP_CHUNK : 0;
-        const float* xc = xb + (long)r0 * F;
-        const long len = (long)(r1 - r0) * F;
-        long last = -1;
-#pragma unroll 4
-        for (long i = tid; i < len; i += TP_THREADS)
-            if (xc[i] != 0.0f) last = i;          // (true for a NaN, false for -0.0)
-        if (tid == 0) s_last = -1;
-        __syncthreads();
-        if (last >= 0) atomicMax(&s_last, (int)(last / F));
-        __syncthreads();
-        const int got = s_last;
-        __syncthreads();                          // (thread 0 resets s_last in the next chunk)
-        if (got >= 0) { n = r0 + got + 1; break; }
-    }
+    const int n = a2s_content_rows<TP_THREADS>(xb, rows, F, &s_last);
     if (tid != 0) return;
     int st = TP_ONE, kept = 1;
     if (n > 0) {

@@ -397,6 +397,67 @@ def tempo_launches():
     return int(lib().a2s_tempo_launches())
 
 
+def _specaug_args(fn, x, table, content, plan, stats):
+    """The checks specaug_plan and specaug_apply share -> (B, rows, F)."""
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
+    _need(x.is_contiguous(), fn, "x", "must be contiguous")
+    _need(x.is_cuda, fn, "x", "must be on the device")
+    B, F = x.shape[0], x.shape[-1]
+    for name, t, dtype, shape in (("table", table, torch.float32, (B, 2, F)), ("content", content, torch.int32, (B,)), ("plan", plan, torch.int32, (B, 16)),
+                                  ("stats", stats, torch.float32, (B, 2))):
+        _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), fn, name,
+              f"must be a contiguous {dtype} tensor of shape {shape}")
+        _need(t.device == x.device, fn, name, "must be on x's device")
+    return B, (x.numel() // (B * F) if x.numel() else 0), F
+
+
+def specaug_plan(x, table, draws, Wt, Wf, m, content, plan, stats, counters):
+    """a2s_specaug_plan: x (B, ..., rows, F) float32, contiguous; table (B, 2, F) float32, per clip the power gains G_k > 0 and the noise powers
+    v_k >= 0; draws (B, 16) int32, the host's 32-bit draws (the bits of its uint32 words), four per mask; Wt, Wf >= 0 the largest mask widths in rows
+    and bins, m in 0 .. 4 the masks of each kind.  content (B,) int32 receives 1 + the last non-zero row of every clip, plan (B, 16) int32
+    4 x [t0, w] then 4 x [k0, wk], stats (B, 2) float32 [x_min, M]; counters (3,) int32 grow by [clips, time-masked, frequency-masked]."""
+    fn = "specaug_plan"
+    B, rows, F = _specaug_args(fn, x, table, content, plan, stats)
+    _need(torch.is_tensor(draws) and draws.dtype == torch.int32 and tuple(draws.shape) == (B, 16) and draws.is_contiguous(), fn, "draws",
+          f"must be a contiguous {torch.int32} tensor of shape {(B, 16)} (the bits of the 32-bit draws)")
+    _need(draws.device == x.device, fn, "draws", "must be on x's device")
+    _need(torch.is_tensor(counters) and counters.dtype == torch.int32 and counters.numel() == 3 and counters.is_contiguous(), fn, "counters",
+          "must be a contiguous int32 tensor of 3 elements")
+    _need(counters.device == x.device, fn, "counters", "must be on x's device")
+    try:
+        wt, wf, mi = int(Wt), int(Wf), int(m)
+    except (TypeError, ValueError):
+        raise A2SError(f"{fn}: `Wt`, `Wf` and `m` must be whole numbers (got {Wt!r}, {Wf!r}, {m!r})") from None
+    _need(wt >= 0 and wt == Wt, fn, "Wt", f"must be a whole number >= 0 (got {Wt!r})")
+    _need(wf >= 0 and wf == Wf, fn, "Wf", f"must be a whole number >= 0 (got {Wf!r})")
+    _need(0 <= mi <= 4 and mi == m, fn, "m", f"must be a whole number in 0 .. 4 (got {m!r})")
+    if x.numel() == 0:
+        return
+    check(lib().a2s_specaug_plan(stream(), _p(x), B, rows, F, _p(table), _p(draws), wt, wf, mi, _p(content), _p(plan), _p(stats), _p(counters)),
+          "a2s_specaug_plan")
+
+
+def specaug_apply(x, table, content, plan, stats, y=None):
+    """a2s_specaug_apply: x (B, ..., rows, F) float32, contiguous -> y of the same shape (a fresh tensor when not given): every clip coloured by its
+    table (B, 2, F), re-normalised to its new peak and masked, with content, plan and stats as specaug_plan left them."""
+    fn = "specaug_apply"
+    B, rows, F = _specaug_args(fn, x, table, content, plan, stats)
+    if y is None:
+        y = torch.empty_like(x)
+    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
+    _need(y.device == x.device, fn, "y", "must be on x's device")
+    _need(y.data_ptr() != x.data_ptr() or x.numel() == 0, fn, "y", "must not be x: the kernel works out of place")
+    if x.numel() == 0:
+        return y
+    check(lib().a2s_specaug_apply(stream(), _p(x), _p(y), _p(table), _p(content), _p(plan), _p(stats), B, rows, F), "a2s_specaug_apply")
+    return y
+
+
+def specaug_launches():
+    """Launches of the two spectrogram-augmentation kernels in this process (a2s_specaug_launches; the other augmenters' counters do not count them)."""
+    return int(lib().a2s_specaug_launches())
+
+
 def _room_table(fn, params, seeds=None):
     _need(torch.is_tensor(params) and params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous() and params.is_cuda,
           fn, "params", "must be a contiguous (B, 4) int32 tensor on the device: [pre, L, wet f32 bits, decay f32 bits] per clip")

@@ -205,6 +205,30 @@ class ASR(sb.Brain):
                 self._tempo = augment.TempoAugment(model.cfg, R, getattr(self.hparams, "seed", 0), self.device, rank=rank)
         return self._tempo
 
+    def _spec_augment(self):
+        """--eq_augment_db=E, --noise_augment_db="(lo, hi)", --mask_time=Wt, --mask_freq=Wf [--mask_count=m] (optional overrides as --tempo_augment):
+        every TRAIN batch gets, per clip, an equaliser curve of at most E dB, a noise floor lo .. hi dB below its peak and m masks of up to Wt frames and
+        Wf bins, and is re-normalised as the front end does (piano_a2s_amd.augment.SpecAugment; the targets stay).
+        -> the augmenter, or None when every component is off (the default: nothing is built, nothing is launched).  A value out of range raises
+        ValueError."""
+        if not hasattr(self, "_specaug"):
+            from piano_a2s_amd import augment
+            hp = self.hparams
+            E, noise, Wt, Wf, m = augment.check_specaug(getattr(hp, "eq_augment_db", 0.0), getattr(hp, "noise_augment_db", None), getattr(hp, "mask_time", 0),
+                                                        getattr(hp, "mask_freq", 0), getattr(hp, "mask_count", 2))
+            self._specaug = None
+            if E or noise is not None or Wt or Wf:
+                model = self.modules.transcription
+                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
+                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
+                    raise ValueError(f"--eq_augment_db / --noise_augment_db / --mask_time / --mask_freq need a transcription module that states its "
+                                     f"`cfg['freq_bins']`; {type(model).__name__} does not")
+                import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                self._specaug = augment.SpecAugment(model.cfg, E, noise, Wt, Wf, m, seed=getattr(hp, "seed", 0), device=self.device,
+                                                    bins_per_octave=getattr(hp, "bins_per_octave", 60), rank=rank)
+        return self._specaug
+
     def _room(self, stage):
         """--synthetic_room (`synthetic_room` above): the Room the batches of `stage` go through, or None.  Built on first use and kept: its count of
         clips and its device buffers belong to the run."""
@@ -218,10 +242,10 @@ class ASR(sb.Brain):
         return room if name in STAGES[mode] else None
 
     def _train_features(self, batch):
-        """`_features` of a TRAIN batch, augmented when the run asks for it: transposed first, then time-stretched.  The transposition rewrites the
-        targets in place: a tensor that was on the device before (and so is the caller's own) is copied first."""
+        """`_features` of a TRAIN batch, augmented when the run asks for it: transposed first, then time-stretched, then coloured and masked.  The
+        transposition rewrites the targets in place: a tensor that was on the device before (and so is the caller's own) is copied first."""
         out = _features(batch, self.device, room=self._room(sb.Stage.TRAIN))
-        aug, tempo = self._transpose_augment(), self._tempo_augment()
+        aug, tempo, specaug = self._transpose_augment(), self._tempo_augment(), self._spec_augment()
         if aug is not None:
             for i in (2, 3, 5):
                 if out[i] is batch[i]:
@@ -229,6 +253,8 @@ class ASR(sb.Brain):
             out = aug(out)
         if tempo is not None:
             out = tempo(out)
+        if specaug is not None:
+            out = specaug(out)
         return out
 
     def compute_objectives(self, predictions, batch, stage):
@@ -319,6 +345,7 @@ class ASR(sb.Brain):
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
         self._transpose_augment()                 # (a --transpose_augment / --detune_bins out of range is refused before anything else happens)
         self._tempo_augment()                     # (and a --tempo_augment)
+        self._spec_augment()                      # (and the spectrogram augmentation's five flags)
         self._room(sb.Stage.TRAIN)                # (and a --synthetic_room)
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
@@ -330,7 +357,7 @@ class ASR(sb.Brain):
     def fit_batch(self, batch):
         fused = self._fused_step()
         if not fused:
-            if self._transpose_augment() is not None or self._tempo_augment() is not None:
+            if self._transpose_augment() is not None or self._tempo_augment() is not None or self._spec_augment() is not None:
                 # the generic path reads the batch twice (compute_forward, compute_objectives): both see the augmented device batch, which
                 # `_features` and `_to_device` pass through as it is
                 batch = self._train_features(batch)
@@ -369,6 +396,8 @@ class ASR(sb.Brain):
             self._augment.reseed(epoch)               # the draws of an epoch depend on (seed, rank, epoch) alone: a resumed run repeats them
         if stage == sb.Stage.TRAIN and self._tempo_augment() is not None:
             self._tempo.reseed(epoch)
+        if stage == sb.Stage.TRAIN and self._spec_augment() is not None:
+            self._specaug.reseed(epoch)
         if stage != sb.Stage.TRAIN:
             self.teacher_forcing_ratio = 0.
         elif self.finetune:
@@ -389,6 +418,9 @@ class ASR(sb.Brain):
             if self._tempo_augment() is not None:
                 counts = self._tempo.counts()                         # likewise: one small D2H per epoch, cumulative over the run
                 stats.update(tempo_clips=counts["clips"], tempo_stretched_clips=counts["stretched"], tempo_kept_clips=counts["kept"])
+            if self._spec_augment() is not None:
+                counts = self._specaug.counts()                       # likewise
+                stats.update(specaug_clips=counts["clips"], specaug_time_masked_clips=counts["time_masked"], specaug_freq_masked_clips=counts["freq_masked"])
             return
         if not hasattr(self, "train_stats"):
             self.train_stats = {"loss": -1}
@@ -453,6 +485,10 @@ def write_run_summary(brain, hparams):
     tempo = getattr(brain, "_tempo", None)
     if tempo is not None:
         extra["tempo_augment"] = dict(max_change=tempo.R, **tempo.counts())
+    specaug = getattr(brain, "_specaug", None)
+    if specaug is not None:
+        extra["spec_augment"] = dict(eq_db=specaug.E, noise_db=list(specaug.noise) if specaug.noise is not None else None, mask_time=specaug.Wt,
+                                     mask_freq=specaug.Wf, mask_count=specaug.m, **specaug.counts())
     room = getattr(brain, "_synthetic_room", None)
     if room is not None:
         extra["room"] = dict(stages=room[0], clips=room[1].clips, **room[1].describe())

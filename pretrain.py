@@ -7,7 +7,10 @@ piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic c
 ``--synthetic_scores=rendered`` their audio is the sound of their (well-formed) score, synthesised on the GPU.  Optional overrides of the
 VALID / TEST decoder: ``--constrained_decoding=true`` (kern grammar), ``--beam_size=K [--beam_length_penalty=A]`` (beam search, K in 1 .. 4); of their scoring: ``--note_metrics=true`` (note-level F1 beside the WER).  Optional override of the TRAIN stage:
 ``--transpose_augment=K [--detune_bins=D]`` (every clip transposed by -K .. K semitones, K in 0 .. 6, and detuned by up to D feature bins, D <= 2.5, on the GPU),
-``--tempo_augment=R`` (every clip played 1 - R .. 1 + R times as slowly, R <= 0.25, its content kept inside the window; the features are time-stretched on the GPU, the score stays).
+``--tempo_augment=R`` (every clip played 1 - R .. 1 + R times as slowly, R <= 0.25, its content kept inside the window; the features are time-stretched on the GPU, the score stays),
+``--eq_augment_db=E --noise_augment_db="(lo, hi)" --mask_time=Wt --mask_freq=Wf [--mask_count=m]`` (the colour of the recording, each part on its own: an equaliser curve of at most
+E <= 12 dB per clip that leaves the front end's floor where it is, a noise floor lo .. hi dB below the clip's peak with 20 <= lo <= hi <= 80, and m in 1 .. 4 SpecAugment masks of up to
+Wt <= 100 frames and Wf <= 60 bins; the features are re-normalised to their new peak on the GPU, after transposition and tempo; the score stays).
 Optional override of the rendered corpus: ``--synthetic_room=none|train|eval|all [--room_rt60="(lo, hi)" --room_drr_db="(lo, hi)" --room_predelay_ms="(lo, hi)"]``
 (with ``--synthetic_scores=rendered`` only: every clip is heard in a synthetic room of its own -- direct path, pre-delay, decaying diffuse tail, drawn from the
 clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none)."""
