@@ -470,6 +470,26 @@ int a2s_fir_rows(void* stream, const float* x, long x_bstride, const float* ir, 
 int a2s_fir_tile_samples(void);
 int a2s_fir_tap_chunk(void);
 int a2s_room_launches(void);
+
+/* ---- sample-rate conversion of recordings (csrc/a2s_resample.hip): a rational polyphase resampler with the mono mix in front of
+ * it, between an audio file and the VQT.  Borrowed device pointers and a stream; allocates nothing, does not synchronise, reads nothing back.
+ *     y[b * y_bstride + n] = sum_{i = 0 .. K-1} table[p * K + i] * mono_b[m0 + Hh - i],        n in [0, n_out[b]),
+ *       q = n * M (64-bit),  p = q mod L,  m0 = q div L,
+ *       mono_b[m] = (sum_{c = 0 .. C-1, ascending} x[b * x_bstride + m * C + c]) * (1.0f / C)  for m in [0, n_in[b]),  0 elsewhere,
+ *       n_out[b] = ceil(n_in[b] * L / M) (64-bit);   y[b * y_bstride + n] = 0 for n in [n_out[b], n_out_max).
+ * x: rows of interleaved frames, C channels (1 .. 8) each; n_in: device, B int32, frames per clip, clamped to [0, n_in_max] on the device; table:
+ * device, (L, K) float32, row p = the taps of phase p; 0 <= Hh < K.  The sum is an fp32 FMA chain with i ascending and one thread forms the whole
+ * sum of an output: its bits do not depend on B, on the other clips, on n_out_max, on the tiling or on the alignment of x, table and y (16-byte
+ * accesses where a row allows them, 4-byte ones otherwise).  Nothing of x at or behind n_in[b] frames reaches a result (it may hold NaN) and nothing
+ * outside [0, n_in_max * C) of a clip's row of x is read; nothing outside [0, n_out_max) of a clip's row of y is written.  A workgroup keeps the
+ * window of mono its a2s_resample_tile_samples() outputs need in LDS: (tile - 1) * M / L + K + 8 may not exceed 15104 samples.
+ * Null pointers, B < 0 or > 65535, C outside 1 .. 8, L or M outside 1 .. 4096, K outside 1 .. 8192, Hh outside 0 .. K - 1, a window beyond the
+ * limit above, n_in_max < 0, n_out_max < 1, x_bstride < n_in_max * C, y_bstride < n_out_max, x == y: A2S_ERR_ARG, nothing is launched; B = 0
+ * returns 0 and launches nothing.  One launch per call; a2s_resample_launches: launches so far. */
+int a2s_resample_rows(void* stream, const float* x, long x_bstride, const int* n_in, int n_in_max, int C, const float* table, int L, int M, int K, int Hh,
+                      float* y, long y_bstride, int n_out_max, int B);
+int a2s_resample_tile_samples(void);
+int a2s_resample_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

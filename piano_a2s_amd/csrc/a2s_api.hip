@@ -291,6 +291,12 @@ int a2s_fir_rows(void* stream, const float* x, long x_bstride, const float* ir, 
 int a2s_fir_tile_samples(void) { return a2s_fir_tile_samples_impl(); }
 int a2s_fir_tap_chunk(void) { return a2s_fir_tap_chunk_impl(); }
 int a2s_room_launches(void) { return a2s_room_launches_impl(); }
+int a2s_resample_rows(void* stream, const float* x, long x_bstride, const int* n_in, int n_in_max, int C, const float* table, int L, int M, int K, int Hh,
+                      float* y, long y_bstride, int n_out_max, int B) {
+    return a2s_resample_rows_impl(ST, x, x_bstride, n_in, n_in_max, C, table, L, M, K, Hh, y, y_bstride, n_out_max, B);
+}
+int a2s_resample_tile_samples(void) { return a2s_resample_tile_samples_impl(); }
+int a2s_resample_launches(void) { return a2s_resample_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

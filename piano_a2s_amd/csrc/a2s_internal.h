@@ -288,6 +288,12 @@ int a2s_fir_tile_samples_impl(void);
 int a2s_fir_tap_chunk_impl(void);
 int a2s_room_launches_impl(void);
 
+// ---- a2s_resample.hip
+int a2s_resample_rows_impl(hipStream_t st, const float* x, long x_bstride, const int* n_in, int n_in_max, int C, const float* table, int L, int M, int K,
+                           int Hh, float* y, long y_bstride, int n_out_max, int B);
+int a2s_resample_tile_samples_impl(void);
+int a2s_resample_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -527,6 +527,53 @@ def room_launches():
     return int(lib().a2s_room_launches())
 
 
+def resample_rows(x, n_in, table, M, Hh, channels=1, y=None, n_out_max=None, n_in_max=None):
+    """a2s_resample_rows: x (B, >= n_in_max * channels) float32 rows of interleaved frames, n_in (B,) int32 frames per clip and table (L, K) float32 on the
+    device -> y (B, n_out_max) float32 (a fresh tensor when not given): the mono mix of every clip resampled by L / M, y[b][n] = sum_i table[p][i] *
+    mono_b[m0 + Hh - i] with p = n M mod L, m0 = n M div L, zero at and behind ceil(n_in[b] L / M).  n_in_max (default: the frames a row of x holds)
+    bounds n_in on the device, n_out_max defaults to ceil(n_in_max L / M).  Out of place."""
+    fn = "resample_rows"
+    _need(torch.is_tensor(table) and table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous() and table.is_cuda and table.numel() > 0, fn,
+          "table", "must be a contiguous (L, K) float32 tensor on the device")
+    L, K = table.shape
+    try:
+        M, Hh, C = int(M), int(Hh), int(channels)
+    except (TypeError, ValueError):
+        raise A2SError(f"{fn}: `M`, `Hh` and `channels` must be whole numbers (got {M!r}, {Hh!r}, {channels!r})") from None
+    _need(1 <= C <= 8, fn, "channels", f"must be in 1 .. 8 (got {C})")
+    _need(1 <= L <= 4096, fn, "table", f"must have 1 .. 4096 rows (got {L})")
+    _need(1 <= K <= 8192, fn, "table", f"must have 1 .. 8192 columns (got {K})")
+    _need(1 <= M <= 4096, fn, "M", f"must be in 1 .. 4096 (got {M})")
+    _need(0 <= Hh < K, fn, "Hh", f"must be in 0 .. K - 1 = {K - 1} (got {Hh})")
+    _need(torch.is_tensor(n_in) and n_in.dtype == torch.int32 and n_in.dim() == 1 and n_in.is_contiguous() and n_in.device == table.device, fn, "n_in",
+          "must be a contiguous int32 tensor of one element per clip on the table's device")
+    B = n_in.shape[0]
+    _need(torch.is_tensor(x) and x.dim() == 2, fn, "x", "must be a 2-D float32 tensor of interleaved frames")
+    nim = x.shape[1] // C if n_in_max is None else int(n_in_max)
+    _need(nim >= 0, fn, "n_in_max", f"must be >= 0 (got {nim})")
+    nom = -(-nim * L // M) if n_out_max is None else int(n_out_max)
+    _need(nom >= 1 or B == 0, fn, "n_out_max", f"must be >= 1 (got {nom})")
+    xs = _rows(fn, "x", x, B, nim * C, table.device)
+    if y is None:
+        y = torch.empty((B, max(nom, 0)), dtype=torch.float32, device=table.device)
+    ys = _rows(fn, "y", y, B, nom, table.device)
+    if B == 0:
+        return y
+    _need(x.data_ptr() != y.data_ptr(), fn, "y", "must not be x (the resampler works out of place)")
+    check(lib().a2s_resample_rows(stream(), _p(x), xs, _p(n_in), nim, C, _p(table), L, M, K, Hh, _p(y), ys, nom, B), "a2s_resample_rows")
+    return y
+
+
+def resample_tile_samples():
+    """Outputs per workgroup of a2s_resample_rows."""
+    return int(lib().a2s_resample_tile_samples())
+
+
+def resample_launches():
+    """Launches of the resampler in this process (a2s_resample_launches)."""
+    return int(lib().a2s_resample_launches())
+
+
 def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):
     """a2s_note_match: the note counts of n_pairs pairs of bar rows, one launch on the current stream.  ref / hyp (int32 ids) and ref_off / hyp_off
     (int64, n_pairs + 1 each) are device tensors or device addresses (ints: parts of one packed buffer, metrics.device_note_counts); dur_ticks, midi, cls

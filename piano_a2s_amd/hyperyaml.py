@@ -178,3 +178,19 @@ def load_hyperpyyaml(stream, overrides=None):
             raw[k] = v
     res = _Resolver(raw)
     return {k: res.key(k) for k in raw}
+
+
+def load_keys(stream, keys, overrides=None):
+    """Only the top-level `keys` of a hparams file and what they refer to (the seeding ``!apply`` lines first, as load_hyperpyyaml runs them): a tool
+    that needs the model and the feature geometry builds neither the recipe's loggers and checkpointer nor asks for its !PLACEHOLDER folders."""
+    text = stream.read() if hasattr(stream, "read") else stream
+    raw = yaml.load(text, Loader=_Loader) or {}
+    if overrides:
+        if isinstance(overrides, str):
+            overrides = yaml.load(overrides, Loader=_Loader) or {}
+        raw.update(overrides)
+    res = _Resolver(raw)
+    for k in raw:
+        if k.startswith("__set_seed"):
+            res.key(k)
+    return {k: res.key(k) for k in keys}

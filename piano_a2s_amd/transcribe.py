@@ -1,0 +1,199 @@
+"""From a recording to decoded kern bars: resample (piano_a2s_amd.audio, csrc/a2s_resample.hip), cut into the clips the model
+takes, GPU VQT, the model exactly as the recipe's evaluation runs it, ids -> kern text per bar and staff.
+
+A joined two-staff Humdrum file is out of scope: it needs spine-split bookkeeping across bars, which the reference leaves to humextra.  The result is a
+dict per recording; the command line (transcribe.py at the root of the repository) writes it as JSON."""
+import json
+import os
+
+import numpy as np
+import torch
+import yaml
+
+from data_processing.humdrum import LabelsMultiple
+
+from . import audio, metrics
+
+labels = LabelsMultiple(extended=True)
+_VQT = {}
+_TIME_SIGNATURES = []
+
+
+def time_signatures():
+    if not _TIME_SIGNATURES:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data_processing", "metadata", "time_signature_list.json")
+        with open(path) as f:
+            _TIME_SIGNATURES.extend(json.load(f))
+    return _TIME_SIGNATURES
+
+
+def _hp(hparams, key, default=None):
+    return hparams.get(key, default) if isinstance(hparams, dict) else getattr(hparams, key, default)
+
+
+def _vqt(device, hparams):
+    key = (str(device), int(_hp(hparams, "sample_rate", 16000)), int(_hp(hparams, "hop_length", 160)), int(_hp(hparams, "bins_per_octave", 60)),
+           int(_hp(hparams, "n_octaves", 8)), float(_hp(hparams, "gamma", 20)))
+    if key not in _VQT:
+        from .vqt import VQT
+        _VQT[key] = VQT(device, sr=key[1], hop=key[2], n_bins=key[3] * key[4], bins_per_octave=key[3], gamma=key[5])
+    return _VQT[key]
+
+
+def to_16k(x, sr, device, hparams):
+    """x: (frames,) or (frames, channels) samples at the rate sr, numpy or torch -> (wave (n,) float32 on the device at the hparams' rate, its rate)."""
+    x = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(torch.float32)
+    if x.dim() == 1:
+        x = x[:, None]
+    if x.dim() != 2:
+        raise ValueError(f"transcribe: the samples must be (frames,) or (frames, channels) (got {tuple(x.shape)})")
+    rate = int(_hp(hparams, "sample_rate", 16000))
+    y, n_out = audio.Resampler(device, sr, rate)(x.to(device)[None].contiguous())
+    return y[0], rate
+
+
+def transcribe_waveform(model, x, sr, *, downbeats=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams):
+    """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
+    mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
+    honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
+    Windows: audio.plan_windows -- with `downbeats` (seconds) groups of max_bars bars as in the reference's test protocol, without them fixed windows
+    every hop_seconds (the model was trained on bar-aligned clips: expect less of the second).
+    -> {"sample_rate_in", "sample_rate", "frames_per_second", "windows": [{"start_s", "stop_s", "n_bars", "flags", "time_signature", "key",
+        "bars": [{"upper", "lower", "upper_ids", "lower_ids"}], ["alignment"]}]};  time_signature and key hold one entry per kept bar (key as in the
+        recipe's result files: class - 6), bars the first n_bars decoded bars."""
+    core = getattr(model, "module", model)
+    device = next(core.parameters()).device
+    hop = int(_hp(hparams, "hop_length", 160))
+    max_bars = int(_hp(hparams, "max_bars", 5))
+    length = (int(_hp(hparams, "max_frame_num", 1201)) - 1) * hop
+    wave, rate = to_16k(x, sr, device, hparams)
+    fps = rate / hop
+    plan = audio._plan(wave.shape[0], rate, downbeats, window_seconds, hop_seconds, max_bars, length)
+    result = {"sample_rate_in": int(sr), "sample_rate": rate, "frames_per_second": fps, "windows": []}
+    if not plan:
+        return result
+    feats = _vqt(device, hparams)(audio.cut_windows(wave, plan, length))
+    inv, ts_list = labels.labels_map_inv, time_signatures()
+    was_training = core.training
+    model.eval()
+    try:
+        for w0 in range(0, len(plan), int(batch_size)):
+            with torch.no_grad():
+                ts_o, key_o, up_o, lo_o = model(spectrogram=feats[w0:w0 + int(batch_size)], inference=True, ground_truth=None, teacher_forcing_ratio=0.,
+                                                device=device)
+            if getattr(core, "constrained_decoding", False) or int(getattr(core, "beam_size", 1)) >= 2:
+                # the ids the constrained / beam decoder EMITTED (the log-probabilities stay the unconstrained ones)
+                up_ids, lo_ids = core.last_decoded["up"][0].cpu().numpy(), core.last_decoded["lo"][0].cpu().numpy()
+            else:
+                up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
+            ts_ids, key_ids = ts_o.argmax(-1).cpu().numpy(), key_o.argmax(-1).cpu().numpy()
+            al = None
+            if getattr(core, "alignment", False) and core.last_alignment is not None:
+                al = {k: {f: t.cpu().numpy() for f, t in v.items()} for k, v in core.last_alignment.items()}
+            for b, (start, stop, n_bars, flags) in enumerate(plan[w0:w0 + int(batch_size)]):
+                n_bars = min(n_bars, up_ids.shape[1])
+                up = [metrics.unpad(r) for r in up_ids[b][:n_bars]]
+                lo = [metrics.unpad(r) for r in lo_ids[b][:n_bars]]
+                win = {"start_s": start / rate, "stop_s": stop / rate, "n_bars": n_bars, "flags": list(flags),
+                       "time_signature": [ts_list[int(i)] for i in ts_ids[b][:n_bars]], "key": [int(i) - 6 for i in key_ids[b][:n_bars]],
+                       "bars": [{"upper": metrics.ids_to_text([u], inv), "lower": metrics.ids_to_text([l], inv), "upper_ids": u.tolist(), "lower_ids": l.tolist()}
+                                for u, l in zip(up, lo)]}
+                if al is not None:
+                    win["alignment"] = _alignment_record(al, b, start / rate, fps, up, lo)
+                result["windows"].append(win)
+    finally:
+        model.train(was_training)
+    return result
+
+
+def _alignment_record(al, b, start_s, fps, up, lo):
+    """The record of the recipe's result files for one window, its frame positions as seconds in the recording (None where no
+    step ran), trimmed to the kept bars and tokens."""
+    sec = lambda v: [None if f < 0 else start_s + float(f) / fps for f in v]
+    n_bars = len(up)
+    rec = {"unit": "seconds", "bar": sec(al["bar"]["centroid"][b][:n_bars]), "bar_weight": al["bar"]["weight"][b][:n_bars].tolist()}
+    for key, k, rows in (("upper", "up", up), ("lower", "lo", lo)):
+        rec[key] = [sec(al[k]["centroid"][b, i, :len(r)]) for i, r in enumerate(rows)]
+        rec[key + "_weight"] = [al[k]["weight"][b, i, :len(r)].tolist() for i, r in enumerate(rows)]
+    return rec
+
+
+def read_downbeats(path):
+    """One time per line, the first whitespace-separated column (ASAP's annotation files: time, time, label); where a third column exists only the
+    lines whose third column starts with `db` count."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            cols = line.split()
+            if not cols or cols[0].startswith("#"):
+                continue
+            if len(cols) >= 3 and not cols[2].startswith("db"):
+                continue
+            out.append(float(cols[0]))
+    return out
+
+
+def load_model(hparams_file, checkpoint, device, overrides=None):
+    """(model on the device in evaluation mode, the geometry keys of the yaml).  The model is the yaml's `transcription`; `checkpoint` is a state_dict
+    file or a checkpoint directory holding transcription.ckpt."""
+    from .hyperyaml import load_keys
+    keys = ("transcription", "sample_rate", "hop_length", "max_frame_num", "max_bars", "bins_per_octave", "n_octaves", "gamma")
+    with open(hparams_file) as f:
+        hp = load_keys(f, keys, overrides)
+    path = os.path.join(checkpoint, "transcription.ckpt") if os.path.isdir(checkpoint) else checkpoint
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"no checkpoint at {path}")
+    model = hp.pop("transcription")
+    model.load_state_dict(torch.load(path, map_location="cpu"))
+    return model.to(device).eval(), hp
+
+
+HELP = """Transcribe WAV recordings (any sample rate, any number of channels) into kern bars, one JSON file per recording.
+
+With --downbeats the recording is cut into groups of max_bars bars, the reference's test protocol.  Without it the tool works on fixed windows, but the
+model was trained on bar-aligned clips: expect less.  The output holds the decoded bars of every window per staff; a joined two-staff Humdrum file is out
+of scope (it needs spine-split bookkeeping across bars, which the reference leaves to humextra)."""
+
+
+def main(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog="transcribe.py", description=HELP, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("hparams", help="hparams yaml (hparams/finetune.yaml): the model is its `transcription` key")
+    ap.add_argument("audio", nargs="+", help="WAV files: PCM 8/16/24/32 bits, IEEE float 32/64 bits, extensible headers")
+    ap.add_argument("--checkpoint", required=True, help="a state_dict file, or a checkpoint directory holding transcription.ckpt")
+    ap.add_argument("--downbeats", help="one downbeat time (s) per line, first column; with a third column only lines whose third column starts with `db`")
+    ap.add_argument("--out", default=".", help="output folder: DIR/NAME.json per recording")
+    ap.add_argument("--window_seconds", type=float, default=12.0)
+    ap.add_argument("--hop_seconds", type=float, default=None)
+    ap.add_argument("--batch_size", type=int, default=16)
+    ap.add_argument("--constrained_decoding", action="store_true", help="decode under the kern token grammar")
+    ap.add_argument("--beam_size", type=int, default=1, help="1 .. 4 hypotheses per clip, 1 = greedy")
+    ap.add_argument("--beam_length_penalty", type=float, default=0.0)
+    ap.add_argument("--alignment", action="store_true", help="also report where in the recording every decoded bar and token lies")
+    ap.add_argument("--device", default="cuda:0")
+    a, extra = ap.parse_known_args(argv)
+    overrides = {}
+    for item in extra:                                                     # hparams overrides as the recipes take them: --key=value
+        if not item.startswith("--") or "=" not in item:
+            ap.error(f"unrecognised argument {item!r} (hparams overrides are written --key=value)")
+        k, v = item[2:].split("=", 1)
+        overrides[k] = yaml.safe_load(v)
+    if not 1 <= a.beam_size <= 4:
+        ap.error(f"--beam_size must be in 1 .. 4 (got {a.beam_size})")
+    if len(a.audio) > 1 and a.downbeats:
+        ap.error("--downbeats belongs to one recording")
+    model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
+    model.constrained_decoding, model.alignment = bool(a.constrained_decoding), bool(a.alignment)
+    model.beam_size, model.beam_length_penalty = a.beam_size, a.beam_length_penalty
+    downbeats = read_downbeats(a.downbeats) if a.downbeats else None
+    os.makedirs(a.out, exist_ok=True)
+    for path in a.audio:
+        x, sr = audio.read_wav(path)
+        result = transcribe_waveform(model, x, sr, downbeats=downbeats, window_seconds=a.window_seconds, hop_seconds=a.hop_seconds,
+                                     batch_size=a.batch_size, hparams=hp)
+        result["audio"] = os.path.basename(path)
+        out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(f"{path}: {len(result['windows'])} windows -> {out}")
+    return 0
