@@ -190,7 +190,7 @@ int a2s_shift_bins_impl(hipStream_t st, const float* x, float* y, const float* e
     A2S_REQUIRE((long long)rows * F < (1LL << 31), "shift_bins: a clip of %d rows x %d bins is too large", rows, F);
     if (B == 0) return A2S_OK;
     const dim3 grid(a2s_cdiv(rows, SB_ROWS), B), block(SB_TX, SB_TY);
-    if (F % 4 == 0 && ((uintptr_t)y & 15) == 0) {
+    if (a2s_row_vec_width(F, y) == 4) {
         hipLaunchKernelGGL(shift_bins<4>, grid, block, 0, st, x, y, eff_bins, rows, F);
     } else {
         hipLaunchKernelGGL(shift_bins<1>, grid, block, 0, st, x, y, eff_bins, rows, F);

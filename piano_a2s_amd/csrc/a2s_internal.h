@@ -239,6 +239,31 @@ int a2s_transpose_targets_impl(hipStream_t st, const int* new_key, const int* in
 int a2s_shift_bins_impl(hipStream_t st, const float* x, float* y, const float* eff_bins, int B, int rows, int F);
 int a2s_augment_launches_impl(void);
 
+// ---- the tile frame of the row-streaming augmentation kernels (shift_bins, stretch_frames, specaug_apply): a workgroup of (A2S_ROW_TX, A2S_ROW_TY)
+// threads works on A2S_ROW_TILE consecutive rows of one clip, threadIdx.y on A2S_ROW_NR of them; a thread moves VEC floats at once, four where
+// F % 4 == 0 and y is 16-byte aligned, else one.
+#define A2S_ROW_TX 128
+#define A2S_ROW_TY 2
+#define A2S_ROW_TILE 16
+#define A2S_ROW_NR (A2S_ROW_TILE / A2S_ROW_TY)
+#ifdef __HIPCC__
+template <int VEC> struct a2s_row_vec { typedef float type; };
+template <> struct a2s_row_vec<4> { typedef f32x4 type; };
+static inline int a2s_row_vec_width(int F, const void* y) { return (F % 4 == 0 && ((uintptr_t)y & 15) == 0) ? 4 : 1; }
+// the grid (row tiles, B, column tiles) of a kernel whose threads each own `vec` columns and do not loop over them; false where F has more column tiles
+// than a grid's z extent
+static inline bool a2s_row_grid(int B, int rows, int F, int vec, dim3* grid) {
+    *grid = dim3(a2s_cdiv(rows, A2S_ROW_TILE), B, a2s_cdiv(F, A2S_ROW_TX * vec));
+    return grid->z <= 65535;
+}
+// kernel<4> or kernel<1>, as `vec` says, on the frame's block
+#define A2S_ROW_LAUNCH(kernel, vec, grid, st, ...)                                                                   \
+    do {                                                                                                             \
+        if ((vec) == 4) hipLaunchKernelGGL(kernel<4>, grid, dim3(A2S_ROW_TX, A2S_ROW_TY), 0, st, __VA_ARGS__);       \
+        else hipLaunchKernelGGL(kernel<1>, grid, dim3(A2S_ROW_TX, A2S_ROW_TY), 0, st, __VA_ARGS__);                  \
+    } while (0)
+#endif
+
 // ---- a2s_tempo.hip
 int a2s_tempo_plan_impl(hipStream_t st, const float* x, int B, int rows, int F, const float* u, float R, int min_frames, int* content, int* step,
     int* counters);

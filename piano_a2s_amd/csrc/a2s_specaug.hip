@@ -33,10 +33,6 @@
 #define SA_FLOOR_EPS 0x1p-18f
 #define SA_8_LOG2_10 26.575424759098897f          // P(x) = 2^(8 log2(10) (x - 1))
 #define SA_LOG10_2_8TH 0.037628749457997640f      // log10(r) / 8 = log2(r) * log10(2) / 8
-#define SA_TX 128
-#define SA_TY 2
-#define SA_ROWS 16
-#define SA_NR (SA_ROWS / SA_TY)
 
 static long long specaug_launches = 0;
 
@@ -145,19 +141,16 @@ __global__ __launch_bounds__(SA_PLAN_THREADS) void specaug_plan(const float* __r
     if (any_f) atomicAdd(&counters[2], 1);
 }
 
-template <int VEC> struct sa_vec { typedef float type; };
-template <> struct sa_vec<4> { typedef f32x4 type; };
-
 template <int VEC>
-__global__ __launch_bounds__(SA_TX * SA_TY) void specaug_apply(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ table,
+__global__ __launch_bounds__(A2S_ROW_TX * A2S_ROW_TY) void specaug_apply(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ table,
                                                                const int* __restrict__ content, const int* __restrict__ plan,
                                                                const float* __restrict__ stats, int rows, int F) {
-    typedef typename sa_vec<VEC>::type V;
-    const int b = blockIdx.y, j = (blockIdx.z * SA_TX + threadIdx.x) * VEC;          // this thread's columns j .. j + VEC - 1, in every row
+    typedef typename a2s_row_vec<VEC>::type V;
+    const int b = blockIdx.y, j = (blockIdx.z * A2S_ROW_TX + threadIdx.x) * VEC;          // this thread's columns j .. j + VEC - 1, in every row
     const int ty = __builtin_amdgcn_readfirstlane(threadIdx.y);          // (a wave has one threadIdx.y: everything per row below is scalar)
-    const int t0 = blockIdx.x * SA_ROWS + ty * SA_NR;
+    const int t0 = blockIdx.x * A2S_ROW_TILE + ty * A2S_ROW_NR;
     if (t0 >= rows || j >= F) return;
-    const int nr = rows - t0 < SA_NR ? rows - t0 : SA_NR;                // output rows of this thread that exist
+    const int nr = rows - t0 < A2S_ROW_NR ? rows - t0 : A2S_ROW_NR;                // output rows of this thread that exist
     int n = content[b];
     n = n < 0 ? 0 : (n > rows ? rows : n);                               // (it bounds the loads below)
     const float x_min = stats[2 * b], M = stats[2 * b + 1];
@@ -178,10 +171,10 @@ __global__ __launch_bounds__(SA_TX * SA_TY) void specaug_apply(const float* __re
             masked[e] = masked[e] || (j + e >= k0 && j + e - k0 < wk);
         }
     }
-    float c[SA_NR][VEC];
-    bool live[SA_NR];
+    float c[A2S_ROW_NR][VEC];
+    bool live[A2S_ROW_NR];
 #pragma unroll
-    for (int r = 0; r < SA_NR; ++r) {                                    // all loads are issued together
+    for (int r = 0; r < A2S_ROW_NR; ++r) {                                    // all loads are issued together
         const int t = t0 + r;
         live[r] = r < nr && t < n;
 #pragma unroll
@@ -194,7 +187,7 @@ __global__ __launch_bounds__(SA_TX * SA_TY) void specaug_apply(const float* __re
         if (live[r]) __builtin_memcpy(c[r], xb + (long)t * F + j, 4 * VEC);          // 4-byte aligned: x need not be aligned as y is
     }
 #pragma unroll
-    for (int r = 0; r < SA_NR; ++r) {
+    for (int r = 0; r < A2S_ROW_NR; ++r) {
         if (r >= nr) break;
         float o[VEC];
 #pragma unroll
@@ -226,14 +219,10 @@ int a2s_specaug_apply_impl(hipStream_t st, const float* x, float* y, const float
     A2S_REQUIRE(B >= 0 && B <= 65535, "specaug_apply: needs 0 <= B <= 65535 (got %d)", B);
     A2S_REQUIRE(rows >= 1 && F >= 1, "specaug_apply: needs rows >= 1 and F >= 1 (got rows = %d, F = %d)", rows, F);
     if (B == 0) return A2S_OK;
-    const int vec = (F % 4 == 0 && ((uintptr_t)y & 15) == 0) ? 4 : 1;
-    A2S_REQUIRE(a2s_cdiv(F, SA_TX * vec) <= 65535, "specaug_apply: %d columns are too many", F);
-    const dim3 grid(a2s_cdiv(rows, SA_ROWS), B, a2s_cdiv(F, SA_TX * vec)), block(SA_TX, SA_TY);
-    if (vec == 4) {
-        hipLaunchKernelGGL(specaug_apply<4>, grid, block, 0, st, x, y, table, content, plan, stats, rows, F);
-    } else {
-        hipLaunchKernelGGL(specaug_apply<1>, grid, block, 0, st, x, y, table, content, plan, stats, rows, F);
-    }
+    const int vec = a2s_row_vec_width(F, y);
+    dim3 grid;
+    A2S_REQUIRE(a2s_row_grid(B, rows, F, vec, &grid), "specaug_apply: %d columns are too many", F);
+    A2S_ROW_LAUNCH(specaug_apply, vec, grid, st, x, y, table, content, plan, stats, rows, F);
     A2S_CHECK_LAUNCH("specaug_apply");
     __atomic_fetch_add(&specaug_launches, 1LL, __ATOMIC_RELAXED);
     return A2S_OK;

@@ -32,10 +32,6 @@
 #define TP_MAX_STEP 87381      // rint(65536 / 0.75)
 #define TP_THREADS 256
 #define TP_CHUNK A2S_CONTENT_CHUNK          // (the scan itself: a2s_content_rows, a2s_internal.h)
-#define SF_TX 128
-#define SF_TY 2
-#define SF_ROWS 16
-#define SF_NR (SF_ROWS / SF_TY)
 #define SF_SRC 13
 
 static long long tempo_launches = 0;
@@ -65,12 +61,9 @@ __global__ __launch_bounds__(TP_THREADS) void tempo_plan(const float* __restrict
     if (kept) atomicAdd(&counters[2], 1);
 }
 
-template <int VEC> struct sf_vec { typedef float type; };
-template <> struct sf_vec<4> { typedef f32x4 type; };
-
 template <int VEC>
-__device__ __forceinline__ typename sf_vec<VEC>::type sf_load(const float* p) {
-    typename sf_vec<VEC>::type v;
+__device__ __forceinline__ typename a2s_row_vec<VEC>::type sf_load(const float* p) {
+    typename a2s_row_vec<VEC>::type v;
     __builtin_memcpy(&v, p, 4 * VEC);            // 4-byte aligned: x need not be aligned as y is
     return v;
 }
@@ -87,15 +80,15 @@ __device__ __forceinline__ V sf_taps(const V& a, const V& b, const V& c, const i
 }
 
 template <int VEC>
-__global__ __launch_bounds__(SF_TX * SF_TY) void stretch_frames(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ step_of, int rows,
+__global__ __launch_bounds__(A2S_ROW_TX * A2S_ROW_TY) void stretch_frames(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ step_of, int rows,
                                                                 int F) {
-    typedef typename sf_vec<VEC>::type V;
-    const int b = blockIdx.y, j = (blockIdx.z * SF_TX + threadIdx.x) * VEC;          // this thread's columns j .. j + VEC - 1, in every row
+    typedef typename a2s_row_vec<VEC>::type V;
+    const int b = blockIdx.y, j = (blockIdx.z * A2S_ROW_TX + threadIdx.x) * VEC;          // this thread's columns j .. j + VEC - 1, in every row
     const int ty = __builtin_amdgcn_readfirstlane(threadIdx.y);          // (a wave has one threadIdx.y: everything per row below is scalar)
     const int step = step_of[b];
-    const int t0 = blockIdx.x * SF_ROWS + ty * SF_NR;
+    const int t0 = blockIdx.x * A2S_ROW_TILE + ty * A2S_ROW_NR;
     if (t0 >= rows || j >= F) return;
-    const int nr = rows - t0 < SF_NR ? rows - t0 : SF_NR;                // output rows of this thread that exist
+    const int nr = rows - t0 < A2S_ROW_NR ? rows - t0 : A2S_ROW_NR;                // output rows of this thread that exist
     const float* xb = x + (long)b * rows * F;
     float* y0 = y + (long)b * rows * F + (long)t0 * F;
     if (step < TP_MIN_STEP || step > TP_MAX_STEP) {
@@ -114,7 +107,7 @@ __global__ __launch_bounds__(SF_TX * SF_TY) void stretch_frames(const float* __r
         if (i <= need && kfirst + i >= 0) v[i] = sf_load<VEC>(xb + (long)(kfirst + i) * F + j);
     }
 #pragma unroll
-    for (int r = 0; r < SF_NR; ++r) {
+    for (int r = 0; r < A2S_ROW_NR; ++r) {
         if (r >= nr) break;
         const int pos = (t0 + r) * step;
         const int klo = (pos - h + TP_ONE) >> 16;
@@ -160,14 +153,10 @@ int a2s_stretch_frames_impl(hipStream_t st, const float* x, float* y, const int*
     A2S_REQUIRE(B >= 0 && B <= 65535, "stretch_frames: needs 0 <= B <= 65535 (got %d)", B);
     A2S_REQUIRE(rows >= 1 && rows <= 16384 && F >= 1, "stretch_frames: needs 1 <= rows <= 16384 and F >= 1 (got rows = %d, F = %d)", rows, F);
     if (B == 0) return A2S_OK;
-    const int vec = (F % 4 == 0 && ((uintptr_t)y & 15) == 0) ? 4 : 1;
-    A2S_REQUIRE(a2s_cdiv(F, SF_TX * vec) <= 65535, "stretch_frames: %d columns are too many", F);
-    const dim3 grid(a2s_cdiv(rows, SF_ROWS), B, a2s_cdiv(F, SF_TX * vec)), block(SF_TX, SF_TY);
-    if (vec == 4) {
-        hipLaunchKernelGGL(stretch_frames<4>, grid, block, 0, st, x, y, step, rows, F);
-    } else {
-        hipLaunchKernelGGL(stretch_frames<1>, grid, block, 0, st, x, y, step, rows, F);
-    }
+    const int vec = a2s_row_vec_width(F, y);
+    dim3 grid;
+    A2S_REQUIRE(a2s_row_grid(B, rows, F, vec, &grid), "stretch_frames: %d columns are too many", F);
+    A2S_ROW_LAUNCH(stretch_frames, vec, grid, st, x, y, step, rows, F);
     A2S_CHECK_LAUNCH("stretch_frames");
     __atomic_fetch_add(&tempo_launches, 1LL, __ATOMIC_RELAXED);
     return A2S_OK;

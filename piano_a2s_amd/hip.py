@@ -293,6 +293,39 @@ def _need(cond, fn, arg, what):
         raise A2SError(f"{fn}: `{arg}` {what}")
 
 
+def _features(fn, x):
+    """`x` as the augmentation kernels take the features, a contiguous float32 tensor (B, ..., rows, F) on the device -> (B, rows, F); rows = 0 for an
+    empty one."""
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
+    _need(x.is_contiguous(), fn, "x", "must be contiguous")
+    _need(x.is_cuda, fn, "x", "must be on the device")
+    B, F = x.shape[0], x.shape[-1]
+    return B, (x.numel() // (B * F) if x.numel() else 0), F
+
+
+def _per_clip(fn, name, t, dtype, x, *trailing):
+    """`t` holds something per clip of the features x: a contiguous `dtype` tensor (B, *trailing) on x's device."""
+    shape = (x.shape[0],) + trailing
+    _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), fn, name,
+          f"must be a contiguous {dtype} tensor " + (f"of shape {shape}" if trailing else f"with one element per clip ({shape[0]})"))
+    _need(t.device == x.device, fn, name, "must be on x's device")
+
+
+def _counters(fn, counters, x):
+    _need(torch.is_tensor(counters) and counters.dtype == torch.int32 and counters.numel() == 3 and counters.is_contiguous(), fn, "counters",
+          "must be a contiguous int32 tensor of 3 elements")
+    _need(counters.device == x.device, fn, "counters", "must be on x's device")
+
+
+def _like(fn, x, y):
+    """`y`, the output of x's shape (a fresh tensor when None): contiguous float32 on x's device."""
+    if y is None:
+        y = torch.empty_like(x)
+    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
+    _need(y.device == x.device, fn, "y", "must be on x's device")
+    return y
+
+
 def transpose_targets(new_key, interval, token_map, semitones, detune, key, upper, lower, bins_per_semitone, eff_bins, counters):
     """a2s_transpose_targets: the tables of kern_transpose.tables() on the device (int32), the draws semitones (B,) int32 and detune (B,) float32, the
     batch's key (B, bars), upper (B, bars, U) and lower (B, bars, L) int64, rewritten IN PLACE where the clip is representable; eff_bins (B,) float32
@@ -324,18 +357,12 @@ def shift_bins(x, eff_bins, y=None):
     """a2s_shift_bins: x (B, ..., rows, F) float32, contiguous -> y of the same shape (a fresh tensor when not given), every row of clip b shifted
     by eff_bins[b] bins (float32 on the device; fractional shifts interpolate linearly, what falls outside [0, F) is zero)."""
     fn = "shift_bins"
-    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
-    _need(x.is_contiguous(), fn, "x", "must be contiguous")
-    B, F = x.shape[0], x.shape[-1]
-    _need(torch.is_tensor(eff_bins) and eff_bins.dtype == torch.float32 and tuple(eff_bins.shape) == (B,) and eff_bins.is_contiguous(), fn, "eff_bins",
-          f"must be a contiguous float32 tensor with one element per clip ({B})")
-    if y is None:
-        y = torch.empty_like(x)
-    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
-    _need(y.device == x.device, fn, "y", "must be on x's device")
+    B, rows, F = _features(fn, x)
+    _per_clip(fn, "eff_bins", eff_bins, torch.float32, x)
+    y = _like(fn, x, y)
     if x.numel() == 0:
         return y
-    check(lib().a2s_shift_bins(stream(), _p(x), _p(y), _p(eff_bins), B, x.numel() // (B * F), F), "a2s_shift_bins")
+    check(lib().a2s_shift_bins(stream(), _p(x), _p(y), _p(eff_bins), B, rows, F), "a2s_shift_bins")
     return y
 
 
@@ -349,14 +376,10 @@ def tempo_plan(x, u, R, min_frames, content, step, counters):
     of the durations, min_frames >= 1 the least content a stretched clip keeps.  content (B,) int32 receives 1 + the last non-zero row of every clip,
     step (B,) int32 the Q16 source advance per output row that a2s_stretch_frames reads; counters (3,) int32 grow by [clips, stretched, kept]."""
     fn = "tempo_plan"
-    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
-    _need(x.is_contiguous(), fn, "x", "must be contiguous")
-    B, F = x.shape[0], x.shape[-1]
+    B, rows, F = _features(fn, x)
     for name, t, dtype in (("u", u, torch.float32), ("content", content, torch.int32), ("step", step, torch.int32)):
-        _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == (B,) and t.is_contiguous(), fn, name,
-              f"must be a contiguous {dtype} tensor with one element per clip ({B})")
-    _need(torch.is_tensor(counters) and counters.dtype == torch.int32 and counters.numel() == 3 and counters.is_contiguous(), fn, "counters",
-          "must be a contiguous int32 tensor of 3 elements")
+        _per_clip(fn, name, t, dtype, x)
+    _counters(fn, counters, x)
     try:
         Rf, mf = float(R), int(min_frames)
     except (TypeError, ValueError):
@@ -365,7 +388,6 @@ def tempo_plan(x, u, R, min_frames, content, step, counters):
     _need(mf >= 1 and mf == min_frames, fn, "min_frames", f"must be a whole number >= 1 (got {min_frames!r})")
     if x.numel() == 0:
         return
-    rows = x.numel() // (B * F)
     _need(rows <= 16384, fn, "x", f"has {rows} rows per clip, more than 16384")
     check(lib().a2s_tempo_plan(stream(), _p(x), B, rows, F, _p(u), Rf, mf, _p(content), _p(step), _p(counters)), "a2s_tempo_plan")
 
@@ -375,18 +397,11 @@ def stretch_frames(x, step, y=None):
     with the Q16 source advance step[b] per output row (int32 on the device; 65536: a copy; below: linear interpolation, the clip gets longer; above: a
     widened tent, it gets shorter; outside 52429 .. 87381: zeros)."""
     fn = "stretch_frames"
-    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
-    _need(x.is_contiguous(), fn, "x", "must be contiguous")
-    B, F = x.shape[0], x.shape[-1]
-    _need(torch.is_tensor(step) and step.dtype == torch.int32 and tuple(step.shape) == (B,) and step.is_contiguous(), fn, "step",
-          f"must be a contiguous int32 tensor with one element per clip ({B})")
-    if y is None:
-        y = torch.empty_like(x)
-    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
-    _need(y.device == x.device, fn, "y", "must be on x's device")
+    B, rows, F = _features(fn, x)
+    _per_clip(fn, "step", step, torch.int32, x)
+    y = _like(fn, x, y)
     if x.numel() == 0:
         return y
-    rows = x.numel() // (B * F)
     _need(rows <= 16384, fn, "x", f"has {rows} rows per clip, more than 16384")
     check(lib().a2s_stretch_frames(stream(), _p(x), _p(y), _p(step), B, rows, F), "a2s_stretch_frames")
     return y
@@ -399,16 +414,12 @@ def tempo_launches():
 
 def _specaug_args(fn, x, table, content, plan, stats):
     """The checks specaug_plan and specaug_apply share -> (B, rows, F)."""
-    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 3, fn, "x", "must be a float32 tensor (B, ..., rows, F)")
-    _need(x.is_contiguous(), fn, "x", "must be contiguous")
-    _need(x.is_cuda, fn, "x", "must be on the device")
-    B, F = x.shape[0], x.shape[-1]
-    for name, t, dtype, shape in (("table", table, torch.float32, (B, 2, F)), ("content", content, torch.int32, (B,)), ("plan", plan, torch.int32, (B, 16)),
-                                  ("stats", stats, torch.float32, (B, 2))):
-        _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), fn, name,
-              f"must be a contiguous {dtype} tensor of shape {shape}")
-        _need(t.device == x.device, fn, name, "must be on x's device")
-    return B, (x.numel() // (B * F) if x.numel() else 0), F
+    B, rows, F = _features(fn, x)
+    _per_clip(fn, "table", table, torch.float32, x, 2, F)
+    _per_clip(fn, "content", content, torch.int32, x)
+    _per_clip(fn, "plan", plan, torch.int32, x, 16)
+    _per_clip(fn, "stats", stats, torch.float32, x, 2)
+    return B, rows, F
 
 
 def specaug_plan(x, table, draws, Wt, Wf, m, content, plan, stats, counters):
@@ -418,12 +429,8 @@ def specaug_plan(x, table, draws, Wt, Wf, m, content, plan, stats, counters):
     4 x [t0, w] then 4 x [k0, wk], stats (B, 2) float32 [x_min, M]; counters (3,) int32 grow by [clips, time-masked, frequency-masked]."""
     fn = "specaug_plan"
     B, rows, F = _specaug_args(fn, x, table, content, plan, stats)
-    _need(torch.is_tensor(draws) and draws.dtype == torch.int32 and tuple(draws.shape) == (B, 16) and draws.is_contiguous(), fn, "draws",
-          f"must be a contiguous {torch.int32} tensor of shape {(B, 16)} (the bits of the 32-bit draws)")
-    _need(draws.device == x.device, fn, "draws", "must be on x's device")
-    _need(torch.is_tensor(counters) and counters.dtype == torch.int32 and counters.numel() == 3 and counters.is_contiguous(), fn, "counters",
-          "must be a contiguous int32 tensor of 3 elements")
-    _need(counters.device == x.device, fn, "counters", "must be on x's device")
+    _per_clip(fn, "draws", draws, torch.int32, x, 16)          # (the bits of the 32-bit draws)
+    _counters(fn, counters, x)
     try:
         wt, wf, mi = int(Wt), int(Wf), int(m)
     except (TypeError, ValueError):
@@ -442,10 +449,7 @@ def specaug_apply(x, table, content, plan, stats, y=None):
     table (B, 2, F), re-normalised to its new peak and masked, with content, plan and stats as specaug_plan left them."""
     fn = "specaug_apply"
     B, rows, F = _specaug_args(fn, x, table, content, plan, stats)
-    if y is None:
-        y = torch.empty_like(x)
-    _need(torch.is_tensor(y) and y.dtype == torch.float32 and y.shape == x.shape and y.is_contiguous(), fn, "y", "must be a contiguous float32 tensor of x's shape")
-    _need(y.device == x.device, fn, "y", "must be on x's device")
+    y = _like(fn, x, y)
     _need(y.data_ptr() != x.data_ptr() or x.numel() == 0, fn, "y", "must not be x: the kernel works out of place")
     if x.numel() == 0:
         return y

@@ -14,10 +14,14 @@ except Exception:                       # noqa: BLE001
     from piano_a2s_amd import sb_compat as sb
 
 from data_processing.humdrum import LabelsMultiple
-from piano_a2s_amd import metrics
+from piano_a2s_amd import augment, metrics
 from utilities import load, mkdirs, save
 
 labels = LabelsMultiple(extended=True)
+
+# the augmenters of a TRAIN batch in the order they are applied (DESIGN.md sections 16, 18, 20).  This table is all the wiring there is: every class states
+# its switches, the attribute that keeps it, its stat keys and its run_summary.json block itself (piano_a2s_amd/augment.py)
+AUGMENTERS = _TRANSPOSE, _TEMPO, _SPECAUG = (augment.TransposeAugment, augment.TempoAugment, augment.SpecAugment)
 
 
 def _to_device(batch, device):
@@ -168,66 +172,42 @@ class ASR(sb.Brain):
                              "`constrained_decoding` attribute")
         model.constrained_decoding = True
 
+    def _augmenter(self, cls):
+        """The augmenter of class `cls` (one of AUGMENTERS) that the run's switches ask for, built on first use and kept in the attribute `cls.cache`, or
+        None when its switches are off (the default: nothing is built, nothing is launched).  Values out of range raise ValueError, from the values
+        alone: no module, no device is touched before."""
+        if not hasattr(self, cls.cache):
+            settings = cls.read(self.hparams)
+            setattr(self, cls.cache, None)
+            if settings is not None:
+                model = self.modules.transcription
+                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
+                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
+                    raise ValueError(f"{cls.needs} a transcription module that states its `cfg['freq_bins']`; {type(model).__name__} does not")
+                import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                setattr(self, cls.cache, cls(model.cfg, **settings, seed=getattr(self.hparams, "seed", 0), device=self.device, rank=rank))
+        return getattr(self, cls.cache)
+
+    def _augmenters(self):
+        """[(class, augmenter)] of the augmenters that are on, in the order of AUGMENTERS."""
+        return [(cls, aug) for cls, aug in ((cls, self._augmenter(cls)) for cls in AUGMENTERS) if aug is not None]
+
     def _transpose_augment(self):
         """--transpose_augment=K [--detune_bins=D] (optional overrides as --constrained_decoding): every TRAIN batch is transposed on the device by a
-        whole number of semitones in -K .. K per clip (features shifted, score respelled) and detuned by up to D feature bins (piano_a2s_amd.augment).
-        -> the augmenter, or None when both are 0 (the default: nothing is built, nothing is launched).  Values out of range raise ValueError."""
-        if not hasattr(self, "_augment"):
-            from piano_a2s_amd import augment
-            K, D = augment.check_range(getattr(self.hparams, "transpose_augment", 0), getattr(self.hparams, "detune_bins", 0.0))
-            self._augment = None
-            if K or D:
-                model = self.modules.transcription
-                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
-                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
-                    raise ValueError(f"--transpose_augment needs a transcription module that states its `cfg['freq_bins']`; {type(model).__name__} does not")
-                import torch.distributed as dist
-                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-                self._augment = augment.TransposeAugment(model.cfg, K, D, getattr(self.hparams, "seed", 0), self.device,
-                                                         bins_per_octave=getattr(self.hparams, "bins_per_octave", 60), rank=rank)
-        return self._augment
+        whole number of semitones in -K .. K per clip (features shifted, score respelled) and detuned by up to D feature bins."""
+        return self._augmenter(_TRANSPOSE)
 
     def _tempo_augment(self):
-        """--tempo_augment=R (an optional override as --transpose_augment): every TRAIN batch is time-stretched on the device, each clip by a factor
-        drawn in 1 - R .. 1 + R and narrowed so that its content stays inside the window (piano_a2s_amd.augment.TempoAugment; the targets stay).
-        -> the augmenter, or None when R is 0 (the default: nothing is built, nothing is launched).  A value out of range raises ValueError."""
-        if not hasattr(self, "_tempo"):
-            from piano_a2s_amd import augment
-            R = augment.check_tempo(getattr(self.hparams, "tempo_augment", 0.0))
-            self._tempo = None
-            if R:
-                model = self.modules.transcription
-                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
-                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
-                    raise ValueError(f"--tempo_augment needs a transcription module that states its `cfg['freq_bins']`; {type(model).__name__} does not")
-                import torch.distributed as dist
-                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-                self._tempo = augment.TempoAugment(model.cfg, R, getattr(self.hparams, "seed", 0), self.device, rank=rank)
-        return self._tempo
+        """--tempo_augment=R: every TRAIN batch is time-stretched on the device, each clip by a factor drawn in 1 - R .. 1 + R and narrowed so that its
+        content stays inside the window (the targets stay)."""
+        return self._augmenter(_TEMPO)
 
     def _spec_augment(self):
-        """--eq_augment_db=E, --noise_augment_db="(lo, hi)", --mask_time=Wt, --mask_freq=Wf [--mask_count=m] (optional overrides as --tempo_augment):
-        every TRAIN batch gets, per clip, an equaliser curve of at most E dB, a noise floor lo .. hi dB below its peak and m masks of up to Wt frames and
-        Wf bins, and is re-normalised as the front end does (piano_a2s_amd.augment.SpecAugment; the targets stay).
-        -> the augmenter, or None when every component is off (the default: nothing is built, nothing is launched).  A value out of range raises
-        ValueError."""
-        if not hasattr(self, "_specaug"):
-            from piano_a2s_amd import augment
-            hp = self.hparams
-            E, noise, Wt, Wf, m = augment.check_specaug(getattr(hp, "eq_augment_db", 0.0), getattr(hp, "noise_augment_db", None), getattr(hp, "mask_time", 0),
-                                                        getattr(hp, "mask_freq", 0), getattr(hp, "mask_count", 2))
-            self._specaug = None
-            if E or noise is not None or Wt or Wf:
-                model = self.modules.transcription
-                model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
-                if not isinstance(getattr(model, "cfg", None), dict) or "freq_bins" not in model.cfg:
-                    raise ValueError(f"--eq_augment_db / --noise_augment_db / --mask_time / --mask_freq need a transcription module that states its "
-                                     f"`cfg['freq_bins']`; {type(model).__name__} does not")
-                import torch.distributed as dist
-                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-                self._specaug = augment.SpecAugment(model.cfg, E, noise, Wt, Wf, m, seed=getattr(hp, "seed", 0), device=self.device,
-                                                    bins_per_octave=getattr(hp, "bins_per_octave", 60), rank=rank)
-        return self._specaug
+        """--eq_augment_db=E, --noise_augment_db="(lo, hi)", --mask_time=Wt, --mask_freq=Wf [--mask_count=m]: every TRAIN batch gets, per clip, an
+        equaliser curve of at most E dB, a noise floor lo .. hi dB below its peak and m masks of up to Wt frames and Wf bins, and is re-normalised as
+        the front end does (the targets stay)."""
+        return self._augmenter(_SPECAUG)
 
     def _room(self, stage):
         """--synthetic_room (`synthetic_room` above): the Room the batches of `stage` go through, or None.  Built on first use and kept: its count of
@@ -242,19 +222,16 @@ class ASR(sb.Brain):
         return room if name in STAGES[mode] else None
 
     def _train_features(self, batch):
-        """`_features` of a TRAIN batch, augmented when the run asks for it: transposed first, then time-stretched, then coloured and masked.  The
-        transposition rewrites the targets in place: a tensor that was on the device before (and so is the caller's own) is copied first."""
+        """`_features` of a TRAIN batch, augmented when the run asks for it, in the order of AUGMENTERS: transposed first, then time-stretched, then
+        coloured and masked.  Where an augmenter rewrites the targets in place, a tensor that was on the device before (and so is the caller's own) is
+        copied first."""
         out = _features(batch, self.device, room=self._room(sb.Stage.TRAIN))
-        aug, tempo, specaug = self._transpose_augment(), self._tempo_augment(), self._spec_augment()
-        if aug is not None:
-            for i in (2, 3, 5):
-                if out[i] is batch[i]:
-                    out[i] = out[i].clone()
+        for cls, aug in self._augmenters():
+            if cls.rewrites_targets:
+                for i in (2, 3, 5):
+                    if out[i] is batch[i]:
+                        out[i] = out[i].clone()
             out = aug(out)
-        if tempo is not None:
-            out = tempo(out)
-        if specaug is not None:
-            out = specaug(out)
         return out
 
     def compute_objectives(self, predictions, batch, stage):
@@ -343,9 +320,7 @@ class ASR(sb.Brain):
         reference, whose torch optimizer IS the recoverable).  When the fused step trains, the recoverable is fused.opt: its recovered
         lr is the truth, and the idle torch optimizer (which update_learning_rate also addresses) is brought in line with it -- without
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
-        self._transpose_augment()                 # (a --transpose_augment / --detune_bins out of range is refused before anything else happens)
-        self._tempo_augment()                     # (and a --tempo_augment)
-        self._spec_augment()                      # (and the spectrogram augmentation's five flags)
+        self._augmenters()                        # (an augmentation switch out of range is refused before anything else happens)
         self._room(sb.Stage.TRAIN)                # (and a --synthetic_room)
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
@@ -357,7 +332,7 @@ class ASR(sb.Brain):
     def fit_batch(self, batch):
         fused = self._fused_step()
         if not fused:
-            if self._transpose_augment() is not None or self._tempo_augment() is not None or self._spec_augment() is not None:
+            if self._augmenters():
                 # the generic path reads the batch twice (compute_forward, compute_objectives): both see the augmented device batch, which
                 # `_features` and `_to_device` pass through as it is
                 batch = self._train_features(batch)
@@ -392,12 +367,9 @@ class ASR(sb.Brain):
                 mkdirs(os.path.join(self.hparams.output_folder, "results", split))
         self.time_sig_list = load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                "data_processing", "metadata", "time_signature_list.json"))
-        if stage == sb.Stage.TRAIN and self._transpose_augment() is not None:
-            self._augment.reseed(epoch)               # the draws of an epoch depend on (seed, rank, epoch) alone: a resumed run repeats them
-        if stage == sb.Stage.TRAIN and self._tempo_augment() is not None:
-            self._tempo.reseed(epoch)
-        if stage == sb.Stage.TRAIN and self._spec_augment() is not None:
-            self._specaug.reseed(epoch)
+        if stage == sb.Stage.TRAIN:
+            for _, aug in self._augmenters():
+                aug.reseed(epoch)                     # the draws of an epoch depend on (seed, rank, epoch) alone: a resumed run repeats them
         if stage != sb.Stage.TRAIN:
             self.teacher_forcing_ratio = 0.
         elif self.finetune:
@@ -412,15 +384,9 @@ class ASR(sb.Brain):
             stats["teacher_forcing_ratio"] = self.teacher_forcing_ratio
         if stage == sb.Stage.TRAIN:
             self.train_stats = stats
-            if self._transpose_augment() is not None:
-                counts = self._augment.counts()                       # one small D2H per epoch; cumulative over the run, logged with the train stats
-                stats.update(augmented_clips=counts["clips"], transposed_clips=counts["transposed"], not_representable_clips=counts["not_representable"])
-            if self._tempo_augment() is not None:
-                counts = self._tempo.counts()                         # likewise: one small D2H per epoch, cumulative over the run
-                stats.update(tempo_clips=counts["clips"], tempo_stretched_clips=counts["stretched"], tempo_kept_clips=counts["kept"])
-            if self._spec_augment() is not None:
-                counts = self._specaug.counts()                       # likewise
-                stats.update(specaug_clips=counts["clips"], specaug_time_masked_clips=counts["time_masked"], specaug_freq_masked_clips=counts["freq_masked"])
+            for cls, aug in self._augmenters():
+                counts = aug.counts()                                 # one small D2H per epoch each; cumulative over the run, logged with the train stats
+                stats.update({stat: counts[name] for stat, name in zip(cls.stats, cls.count_names)})
             return
         if not hasattr(self, "train_stats"):
             self.train_stats = {"loss": -1}
@@ -478,17 +444,11 @@ def write_run_summary(brain, hparams):
         return
     fused = getattr(brain, "_fused", None)
     inited = dist.is_available() and dist.is_initialized()
-    aug = getattr(brain, "_augment", None)
     extra = {}
-    if aug is not None:
-        extra["transpose_augment"] = dict(max_semitones=aug.K, detune_bins=aug.D, **aug.counts())
-    tempo = getattr(brain, "_tempo", None)
-    if tempo is not None:
-        extra["tempo_augment"] = dict(max_change=tempo.R, **tempo.counts())
-    specaug = getattr(brain, "_specaug", None)
-    if specaug is not None:
-        extra["spec_augment"] = dict(eq_db=specaug.E, noise_db=list(specaug.noise) if specaug.noise is not None else None, mask_time=specaug.Wt,
-                                     mask_freq=specaug.Wf, mask_count=specaug.m, **specaug.counts())
+    for cls in AUGMENTERS:
+        aug = getattr(brain, cls.cache, None)
+        if aug is not None:
+            extra[cls.summary] = dict(**aug.settings(), **aug.counts())
     room = getattr(brain, "_synthetic_room", None)
     if room is not None:
         extra["room"] = dict(stages=room[0], clips=room[1].clips, **room[1].describe())
