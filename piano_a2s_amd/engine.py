@@ -12,26 +12,9 @@ import threading
 
 import torch
 
-from . import hip
+from . import decode_plan, hip
+from .decode_plan import draw_plan, plan_note_steps, plan_segments
 from .spec import EOS, PAD, SOS, VOCAB_SIZE
-
-
-def plan_note_steps(gt_rows, max_steps):
-    """Host replay of the reference's loop bookkeeping for one (bar, staff) with ground truth
-    (models.py:388-419): returns (steps executed, lengths per row).
-
-    The loop breaks at the first t where every row has shown <eos> in gt[:, :t]; lengths[b] is overwritten by
-    every <eos> seen at t < steps (so it ends as the LAST such position + 1), default max_steps.
-    """
-    B = gt_rows.shape[0]
-    is_eos = gt_rows == EOS                                      # (B, max_steps) CPU bool
-    first = torch.where(is_eos.any(1), is_eos.float().argmax(1), torch.full((B,), max_steps))
-    steps = int(first.max()) + 1 if bool((first < max_steps).all()) else max_steps
-    steps = min(steps, max_steps)
-    idx = torch.arange(1, steps + 1, dtype=torch.long)
-    last = (is_eos[:, :steps].long() * idx).amax(dim=1)          # last <eos> position + 1 among the executed steps, 0 = none
-    lengths = torch.where(last > 0, last, torch.full((B,), max_steps, dtype=torch.long))
-    return steps, lengths
 
 
 import os as _os
@@ -177,32 +160,6 @@ def staves_concurrent(gidx, n_groups):
     return gidx == 0 or (gidx == 1 and n_groups == 2)
 
 
-def draw_plan(gt_cpu, bars, maxlen, rng, teacher_forcing_ratio):
-    """The host plan of a forward pass with ground truth: executed steps of every (bar, staff) and EVERY coin of the reference's protocol, drawn in the
-    reference's order (one per executed note step, upper then lower, then one per bar: models.py:404,289).  gt_cpu: (upper, lower, ...) host tensors
-    (B, bars, len); the step counts are batch-wide maxima, so the clip order does not matter."""
-    plan = []
-    for bar in range(bars):
-        p = {}
-        for gi_idx in (0, 1):
-            steps, _ = plan_note_steps(gt_cpu[gi_idx][:, bar, :], maxlen[gi_idx])
-            p[gi_idx] = (steps, [rng.random() < teacher_forcing_ratio for _ in range(steps)])
-        p["tf"] = rng.random() < teacher_forcing_ratio
-        plan.append(p)
-    return plan
-
-
-def plan_segments(plan, bars, fuse, inference=False):
-    """Bars decoded in one call each: consecutive bars whose predecessor's bar-level coin says "teacher-force" (at most 5 = A2S_ATTN_MAX_GROUPS)."""
-    segments = [[0]]
-    for bar in range(1, bars):
-        if fuse and plan[bar - 1]["tf"] and not inference and len(segments[-1]) < 5:
-            segments[-1].append(bar)
-        else:
-            segments.append([bar])
-    return segments
-
-
 def group_views(t, clip_groups, gidx):
     """Bar-major staff tensor (bars, B, len, V) as ONE flat buffer in which every clip group owns a contiguous bar-major block:
     returns group gidx's block as (bars, clips of the group, len, V).  With a single group that is `t` itself."""
@@ -317,6 +274,15 @@ def _dist_world():
 _NOTE_DEC_WEIGHTS = (("attn_w", ".attn.attn.weight"), ("attn_b", ".attn.attn.bias"), ("attn_v", ".attn.v.weight"), ("w_ih", ".gru.weight_ih_l0"),
                      ("w_hh", ".gru.weight_hh_l0"), ("b_ih", ".gru.bias_ih_l0"), ("b_hh", ".gru.bias_hh_l0"), ("out_w", ".out.weight"),
                      ("out_b", ".out.bias"), ("emb", ".embedding.weight"))
+
+
+def _kernel_plan(host, upload):
+    """A host plan of decode_plan.staff_rows / pair_rows as the kernels take it: the tensors on the device (staged by `upload`), the per-step counts
+    as C int arrays the launching loops read on the host; everything else as it is."""
+    p = dict(host)
+    p.update({k: upload(p[k]) for k in ("until", "order", "rank", "live_idx", "row_list") if p.get(k) is not None})
+    p.update({k: (C.c_int * max(len(p[k]), 1))(*p[k]) for k in ("n_active", "m_active", "n_rows_active") if p.get(k) is not None})
+    return p
 
 
 def _set_note_dec_weights(a, S, prefix):
@@ -587,20 +553,12 @@ class Engine:
         _set_note_dec_weights(a, S, prefix)
         for name, t in (("keys", keys), ("enc", enc), ("h", h), ("x", x), ("q", q),
                         ("gates", gates), ("attw", attw), ("o", o), ("gh", gh), ("gi", gi), ("logits", logits),
-                        ("argmax_out", ids), ("eos_seen", eos_seen), ("lengths", lengths), ("n_done", n_done), ("steps_exec", steps_exec), ("drop", drop), ("attn_ws", attn_ws), ("gemm_ws", gemm_ws), ("t_base", t_base),
-                        ("clip_order", active and active["order"]), ("clip_rank", active and active["rank"]),
-                        ("row_until", active and active["until"])):
+                        ("argmax_out", ids), ("eos_seen", eos_seen), ("lengths", lengths), ("n_done", n_done), ("steps_exec", steps_exec), ("drop", drop), ("attn_ws", attn_ws), ("gemm_ws", gemm_ws), ("t_base", t_base)):
             setattr(a, name, t.data_ptr() if t is not None else None)
         a.gemm_ws_bytes = gemm_ws.numel() * 4 if gemm_ws is not None else 0
         step_ws = hip.step_workspace(H, E, dev)
         a.step_ws, a.step_ws_floats = step_ws.data_ptr(), step_ws.numel()
-        a.n_active = C.cast(active["n_active"], C.c_void_p).value if active else None
-        a.n_clips = active["n_clips"] if active else 0
-        a.m_active = C.cast(active["m_active"], C.c_void_p).value if (active and active.get("m_active") is not None) else None
-        if active and active.get("row_list") is not None:
-            a.row_list, a.n_rows_active = active["row_list"].data_ptr(), C.cast(active["n_rows_active"], C.c_void_p).value
-        else:
-            a.row_list, a.n_rows_active = None, None
+        hip.set_row_plan(a, active)
         a.probs, a.probs_bstride = probs_bar.data_ptr(), probs_bar.stride(0)
         if gt_bar is not None:
             a.gt, a.gt_bstride = gt_bar.data_ptr(), gt_bar.stride(0)
@@ -814,12 +772,7 @@ class Engine:
         skip = plan is not None and training and getattr(self, "skip_finished_rows", False)
         fuse = skip and getattr(self, "fuse_bars", False)
         segments = plan_segments(plan, bars, fuse, inference) if plan is not None else [[bar] for bar in range(bars)]
-        until_all = None
-        if skip:
-            until_all = []
-            for g in gt_cpu[:2]:
-                idx = torch.arange(1, g.shape[-1] + 1, dtype=torch.int32)
-                until_all.append(((g != PAD).to(torch.int32) * idx).amax(dim=-1).to(torch.int32).t().contiguous())   # (bars, B): last real target + 1
+        until_all = [decode_plan.row_limits(g).to(torch.int32).t().contiguous() for g in gt_cpu[:2]] if skip else None     # (bars, B): last real target + 1
         clip_groups = getattr(self, "clip_groups", None) if fuse else None
         if not clip_groups or len(clip_groups) < 2:
             clip_groups = [(0, B)]
@@ -891,84 +844,34 @@ class Engine:
             def rand(shape):
                 return torch.rand(shape, device=dev, generator=gen)
 
-            # steps of this group's calls: the loop of a (bar, staff) ends when every row OF THE GROUP has shown <eos> (a group with no
-            # full-length row does not run to the cap because another group has one); the coins are the plan's (global step index)
-            gsteps = None
-            if plan is not None:
-                gsteps = [{gi_idx: min(plan[bar][gi_idx][0], plan_note_steps(gt_cpu_g[gi_idx][:, bar, :], maxlen[gi_idx])[0]) for gi_idx in (0, 1)}
-                          for bar in range(bars)]
-
+            gsteps = decode_plan.group_steps(plan, gt_cpu_g, maxlen) if plan is not None else None          # steps of THIS group's calls
             _trace(f"g{gidx} step counts planned")
 
-            def active_rows(gi_idx, seg, n):
-                """Row / clip bookkeeping of one decoder call over the bars `seg` (n steps launched)."""
-                until = torch.stack([until_all[gi_idx][bar][b0:b1].clamp(max=gsteps[bar][gi_idx]) for bar in seg])   # the bar's loop ends at its own step count
-                clip_until = until.amax(dim=0)
-                order = torch.argsort(clip_until, descending=True, stable=True).to(torch.int32)                     # clips that finish last come first
-                rank = torch.empty_like(order)
-                rank[order.long()] = torch.arange(Bg, dtype=torch.int32)
-                cnt = torch.bincount(clip_until.long(), minlength=n + 1)
-                n_act = Bg - torch.cumsum(cnt, 0)[:n]                                                               # clips with until > t
-                self.attn_clip_steps.append(int(n_act.sum()))          # (clip, step) pairs whose keys / encoder outputs this call streams: bench.py's step roofline
-                # 1 + the largest clip POSITION still unfinished at step t (the per-step products of the tail run on that prefix of every
-                # fused bar only: a2s_note_dec_args.m_active; train.plan_clip_groups puts the clips with the longest rows first)
-                last = torch.zeros(n + 1, dtype=torch.long)
-                cu = clip_until.long().clamp(max=n)
-                last.scatter_reduce_(0, cu, torch.arange(1, Bg + 1), reduce="amax")                                 # last[u] = 1 + max position with until == u
-                m_act = torch.flip(torch.cummax(torch.flip(last, [0]), 0)[0], [0])[1:n + 1]                          # max over until > t
-                # the rows themselves, latest-finishing first: the few-row step kernels cover the rows still running (a2s_note_dec_args.row_list)
-                uflat = until.reshape(-1)
-                row_list = torch.argsort(uflat, descending=True, stable=True).to(torch.int32)
-                rcnt = torch.bincount(uflat.long().clamp(max=n), minlength=n + 1)
-                n_rows = uflat.numel() - torch.cumsum(rcnt, 0)[:n]                                                  # rows with until > t
-                live_idx = None
-                if _LIVE_ROWS:
-                    live_idx = (torch.arange(n).unsqueeze(1) < uflat.unsqueeze(0)).reshape(-1).nonzero().squeeze(1).to(torch.int32)    # k = step * rows + row
-                return dict(until=upload(uflat), order=upload(order), rank=upload(rank),
-                            live_idx=upload(live_idx) if live_idx is not None else None, live_steps=n,
-                            n_active=(C.c_int * max(n, 1))(*n_act.tolist()), n_clips=Bg,
-                            m_active=(C.c_int * max(n, 1))(*m_act.tolist()) if _TAIL_PREFIX else None,
-                            row_list=upload(row_list) if _TAIL_ROWS else None,
-                            n_rows_active=(C.c_int * max(n, 1))(*n_rows.tolist()) if _TAIL_ROWS else None)
-
-            # Every host-side decision of the decoder and every small upload happens HERE, while the GPU is busy with the ConvStack and
-            # the encoder enqueued above -- not once per (segment, staff) in the middle of the decoder.
+            # Every host-side decision of the decoder (decode_plan: pure host code) and every small upload happens HERE, while the GPU is busy with the
+            # ConvStack and the encoder enqueued above -- not once per (segment, staff) in the middle of the decoder.
             _trace(f"g{gidx} planning starts")
-            def pair_rows(seg, n):
-                """Clip bookkeeping of BOTH staves of a segment together (a2s_note_decoder_fwd_pair): the clips sorted by the step their last row of
-                either staff finishes at."""
-                until = torch.stack([until_all[gi_idx][bar][b0:b1].clamp(max=gsteps[bar][gi_idx]) for gi_idx in (0, 1) for bar in seg])
-                clip_until = until.amax(dim=0)
-                order = torch.argsort(clip_until, descending=True, stable=True).to(torch.int32)
-                rank = torch.empty_like(order)
-                rank[order.long()] = torch.arange(Bg, dtype=torch.int32)
-                n_act = Bg - torch.cumsum(torch.bincount(clip_until.long(), minlength=n + 1), 0)[:n]
-                # (clip, step) pairs whose encoder outputs ONE pass serves for both staves: steps both staves run on the launch-per-step loop (more rows
-                # still running than the few-row kernels take), clips with an unfinished row of each staff -- bench.py's step roofline
-                nb_, fmax, t_ = len(seg), L.a2s_debug_get(b"attn_pair_fused_rows"), torch.arange(n).unsqueeze(1)
-                rows_live = [(until[k * nb_:(k + 1) * nb_].reshape(1, -1) > t_).sum(1) for k in (0, 1)]
-                clip_live = [until[k * nb_:(k + 1) * nb_].amax(dim=0).unsqueeze(0) > t_ for k in (0, 1)]
-                joint = (rows_live[0] > fmax) & (rows_live[1] > fmax)
-                self.attn_shared_clip_steps.append(int(((clip_live[0] & clip_live[1]).sum(1) * joint).sum()))
-                return dict(order=upload(order), rank=upload(rank), n_active=(C.c_int * max(n, 1))(*n_act.tolist()))
-
             seg_plan = []
             for seg in segments:
-                sp = {}
+                sp, until = {}, {}
                 for gi_idx in (0, 1):
                     if plan is None:
                         sp[gi_idx] = (maxlen[gi_idx], None, None, None)
                         continue
-                    steps = max(gsteps[bar][gi_idx] for bar in seg)
-                    flags = [sum(int(t < gsteps[bar][gi_idx] and plan[bar][gi_idx][1][t]) << j for j, bar in enumerate(seg)) for t in range(steps)]
+                    steps, flags = decode_plan.segment_flags(plan, gsteps, seg, gi_idx)
                     # the backward pass needs the flags on the device (which token each step consumed)
                     flags_dev = upload(torch.tensor(flags[:steps], dtype=torch.int32)) if training and steps > 0 else None
-                    sp[gi_idx] = (steps, flags, active_rows(gi_idx, seg, steps) if skip else None, flags_dev)
+                    active = None
+                    if skip:
+                        until[gi_idx] = decode_plan.segment_until(until_all[gi_idx], gsteps, seg, gi_idx, b0, b1)
+                        active = _kernel_plan(decode_plan.staff_rows(until[gi_idx], steps, _TAIL_PREFIX, _TAIL_ROWS, _LIVE_ROWS), upload)
+                        self.attn_clip_steps.append(active["clip_steps"])          # (clip, step) pairs this call streams: bench.py's step roofline
+                    sp[gi_idx] = (steps, flags, active, flags_dev)
                 # both staves' step loops issued as one (the sweeps of a step share the pass over the encoder outputs): training, two streams
                 # (the bulk group only, and only calls over more rows than the few-row step kernels take: those loops are bound by the host's launch rate)
                 if (plan is not None and skip and training and concurrent_g and gidx == 0 and _PAIR_STAVES and sp[0][0] > 0 and sp[1][0] > 0 and H == 256
                         and len(seg) * Bg > L.a2s_debug_get(b"attn_pair_fused_rows") and L.a2s_debug_get(b"attn_pair")):
-                    sp["pair"] = pair_rows(seg, max(sp[0][0], sp[1][0]))
+                    sp["pair"] = _kernel_plan(decode_plan.pair_rows(until[0], until[1], max(sp[0][0], sp[1][0]), L.a2s_debug_get(b"attn_pair_fused_rows")), upload)
+                    self.attn_shared_clip_steps.append(sp["pair"]["shared_clip_steps"])
                 seg_plan.append(sp)
 
             sos_ids = torch.full((Bg, 2), SOS, dtype=torch.long, device=dev)

@@ -141,7 +141,6 @@ def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc,
     dq_all = torch.empty((n, B, H), dtype=torch.float32, device=dev)
     ds_all = torch.empty((n, B, T), dtype=torch.float32, device=dev)
     dctx_all = torch.empty((n, B, H2), dtype=torch.float32, device=dev)
-    m_active = sv["active"].get("m_active") if sv.get("active") else None
     # (with m_active the per-step products skip the rows of finished clips: their dx rows are never written and must read as zero)
     dx = torch.empty((n, B, ldx), dtype=torch.float32, device=dev)          # (zero-filled by a2s_note_decoder_bwd when rows are skipped)
     dh = torch.empty((2, B, H2), dtype=torch.float32, device=dev)
@@ -149,20 +148,12 @@ def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc,
     for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_v", S[prefix + ".attn.v.weight"]), ("w_ih", S[prefix + ".gru.weight_ih_l0"]),
                     ("w_hh", S[prefix + ".gru.weight_hh_l0"]), ("keys", keys), ("enc", enc), ("h", sv["h"]), ("x", sv["x"]), ("q", sv["q"]),
                     ("gates", sv["gates"]), ("attw", sv["attw"]), ("do_all", do_all), ("dgi_all", dgi_all), ("dgh_all", dgh_all),
-                    ("dq_all", dq_all), ("ds_all", ds_all), ("dctx_all", dctx_all), ("dx", dx), ("dh", dh), ("attn_ws", sv["attn_ws"]), ("gemm_ws", sv["gemm_ws"]),
-                    ("clip_order", sv.get("active") and sv["active"]["order"]), ("clip_rank", sv.get("active") and sv["active"]["rank"]),
-                    ("row_until", sv.get("active") and sv["active"]["until"])):
+                    ("dq_all", dq_all), ("ds_all", ds_all), ("dctx_all", dctx_all), ("dx", dx), ("dh", dh), ("attn_ws", sv["attn_ws"]), ("gemm_ws", sv["gemm_ws"])):
         setattr(a, name, t.data_ptr() if t is not None else None)
     a.gemm_ws_bytes = sv["gemm_ws"].numel() * 4 if sv["gemm_ws"] is not None else 0
     if sv.get("step_ws") is not None:
         a.step_ws, a.step_ws_floats = sv["step_ws"].data_ptr(), sv["step_ws"].numel()
-    a.n_active = C.cast(sv["active"]["n_active"], C.c_void_p).value if sv.get("active") else None
-    a.n_clips = sv["active"]["n_clips"] if sv.get("active") else 0
-    a.m_active = C.cast(m_active, C.c_void_p).value if m_active is not None else None
-    if sv.get("active") and sv["active"].get("row_list") is not None:
-        a.row_list, a.n_rows_active = sv["active"]["row_list"].data_ptr(), C.cast(sv["active"]["n_rows_active"], C.c_void_p).value
-    else:
-        a.row_list, a.n_rows_active = None, None
+    hip.set_row_plan(a, sv.get("active"))
     a.R, a.T, a.H, a.E, a.steps = B, T, H, E, n
     # the forward ran this call as one persistent launch (at most 8 clips): so does the reverse loop (csrc/a2s_dec_persist.hip)
     a.persist_ws, a.persist_ws_bytes, a.w_ih_full = None, 0, None

@@ -16,6 +16,19 @@ NoteDecArgs, NoteDecBwdArgs, BeamArgs, AlignArgs = (STRUCTS[n] for n in ("a2s_no
 _lib = None
 
 
+def set_row_plan(a, active):
+    """The row plan of a decoder call (the eight fields a2s_note_dec_args and a2s_note_dec_bwd_args share) from `active` = dict(until, order, rank:
+    device int32 tensors; n_active: C int array per step; n_clips; optional m_active: C int array, row_list: device int32 + n_rows_active: C int
+    array), or from None: plain rows, nothing fused, nothing skipped."""
+    active = active or {}
+    for field, key in (("clip_order", "order"), ("clip_rank", "rank"), ("row_until", "until"), ("row_list", "row_list")):
+        setattr(a, field, active[key].data_ptr() if active.get(key) is not None else None)
+    for field, key in (("n_active", "n_active"), ("m_active", "m_active"), ("n_rows_active", "n_rows_active")):
+        host = active.get(key) if (key != "n_rows_active" or active.get("row_list") is not None) else None
+        setattr(a, field, C.cast(host, C.c_void_p).value if host is not None else None)
+    a.n_clips = active.get("n_clips", 0)
+
+
 def lib():
     global _lib
     if _lib is None:

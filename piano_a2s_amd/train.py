@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine, engine_bwd, hip
+from .decode_plan import plan_clip_groups, plan_step_groups, split_long_group      # (plan_clip_groups: looked up here per step -- tests and tools wrap the name)
 from .spec import PAD, VOCAB_SIZE
 
 
@@ -196,120 +197,6 @@ def reserve_pools(device, batch, frames=1201, scale=1.0):
     return total
 
 
-def plan_clip_groups(until_up, until_lo, max_tail_frac=0.5, min_gain=0.08, step_cost=150.0, jump=1.3, max_candidates=8):
-    """Cut a minibatch into [ordinary clips | long clips] for Engine.forward's clip groups.
-
-    until_up / until_lo: (B, bars) int arrays, decode steps each (clip, bar) row needs (last real target + 1).  Cost model of a group
-    of clips, in units of one clip's attention pass (~0.7 us on MI355X): a decode step costs max(step_cost, rows still active) --
-    bandwidth-bound while many rows are active, a latency floor (~100 us of dependent small kernels) once only a few long rows
-    remain -- summed over the steps of the longer staff of every bar.  Two groups run CONCURRENTLY but share the HBM, so a cut costs
-    max(cost of either group, attention work of both).  Candidate cuts: the places where the clips' longest rows, sorted, jump by
-    `jump`x.  The best cut is taken if it beats the uncut minibatch by min_gain.  Returns (order, n_main): `order` = clip permutation
-    (ordinary clips first, sorted by their longest row, longest first; the long clips in their original order), n_main = size of the
-    first group (== B: do not split)."""
-    import numpy as np
-    up, lo = np.asarray(until_up, dtype=np.int64), np.asarray(until_lo, dtype=np.int64)
-    B = up.shape[0]
-    ident = np.arange(B)
-    if B < 4:
-        return ident, B
-
-    def cost(sel):
-        total, work = 0.0, 0.0
-        for bar in range(up.shape[1]):
-            u, l = up[sel, bar], lo[sel, bar]
-            n = int(max(u.max(), l.max()))
-            act = np.zeros(n, dtype=np.float64)
-            for v in (u, l):
-                act += len(v) - np.cumsum(np.bincount(v, minlength=n + 1))[:n]         # rows with until > t
-            total += np.maximum(act, step_cost).sum()
-            work += act.sum()
-        return total, work
-
-    longest = np.maximum(up.max(1), lo.max(1))
-    by_len = np.argsort(-longest, kind="stable")                 # longest clips first
-    srt = longest[by_len].astype(np.float64)
-    kmax = max(1, int(B * max_tail_frac))
-    ratio = srt[:kmax] / np.maximum(srt[1:kmax + 1], 1.0)        # jump between the k-th longest clip and the next
-    cands = [int(k) + 1 for k in np.argsort(-ratio, kind="stable")[:max_candidates] if ratio[k] >= jump]
-    if not cands:
-        return ident, B
-    whole, _ = cost(ident)
-    best_k, best = None, (1.0 - min_gain) * whole
-    for k in cands:
-        ct, wt = cost(by_len[:k])
-        cm, wm = cost(by_len[k:])
-        c = max(ct, cm, wt + wm)
-        if c < best:
-            best_k, best = k, c
-    if best_k is None:
-        return ident, B
-    # inside the ordinary group the clips with the longest rows come first (by_len is a stable descending sort): late in a decoder call
-    # only a prefix of the clips is still running (engine.active_rows: m_active); the long clips keep their original order
-    return np.concatenate([by_len[best_k:], np.sort(by_len[:best_k])]), B - best_k
-
-
-def split_long_group(long_ids, until_up, until_lo, segments, min_gain=0.1):
-    """Round 5.  The long-clip group's decode chain is, per bar SEGMENT of the step, as long as the longest row ANY of its clips has there -- typically a
-    full-length (398-step) upper bar in every segment, although each clip holds only one such bar.  Cut it by where the clips' longest bars lie:
-    sub-group A = clips whose longest upper bar is in segments 0..k, sub-group B = the rest; each then runs 398 steps only in "its" segments.  The two
-    sub-groups get one stream each (engine.group_stream) and decode their staves one after the other, so a sub-group's chain is the SUM of its
-    staves' steps per segment, against the MAXIMUM for the single group (staves side by side).  Returns (A, B) -- lists of clip ids -- for the
-    best k when max(chain A, chain B) < (1 - min_gain) x the single group's chain, else None.  Loss, gradients and update do not depend on the
-    grouping (clip groups are independent: Engine.forward)."""
-    import numpy as np
-    long_ids = list(long_ids)
-    if len(long_ids) < 2 or len(segments) < 2:
-        return None
-    up, lo = np.asarray(until_up), np.asarray(until_lo)
-
-    def chain(ids, sequential):
-        total = 0
-        for seg in segments:
-            u, l = int(up[np.ix_(ids, seg)].max()), int(lo[np.ix_(ids, seg)].max())
-            total += (u + l) if sequential else max(u, l)
-        return total
-    seg_of_bar = {bar: si for si, seg in enumerate(segments) for bar in seg}
-    where = [seg_of_bar[int(up[c].argmax())] for c in long_ids]
-    single = chain(long_ids, False)
-    best = None
-    for k in range(len(segments) - 1):
-        a = [c for c, w in zip(long_ids, where) if w <= k]
-        b = [c for c, w in zip(long_ids, where) if w > k]
-        if not a or not b:
-            continue
-        m = max(chain(a, True), chain(b, True))
-        if best is None or m < best[0]:
-            best = (m, a, b)
-    if best is not None and best[0] < (1.0 - min_gain) * single:
-        return best[1], best[2]
-    return None
-
-
-def plan_step_groups(gt_host, bars, max_length, rng, teacher_forcing_ratio, group_plan=None, long_subgroups=True):
-    """The host's clip-group plan of one step, from the targets alone: gt_host = (upper, lower, ...) host tensors (B, bars, len).  Returns (order,
-    group_cuts, host_plan): the clip permutation, the contiguous clip ranges of the groups in that order -- [ordinary | long] or, when the long
-    clips' longest bars lie in different bar segments of THIS step's coins, [ordinary | long A | long B] (split_long_group) -- and the coins if
-    they had to be drawn for that (engine.draw_plan: the reference's draw order; Engine.forward then takes them as host_plan), else None.
-    TrainStep._step calls it; tests/golden/make_golden.py uses it to choose fixtures that exercise the three-group path."""
-    import numpy as _np
-    up, lo = gt_host[0], gt_host[1]
-    idx_u = torch.arange(1, up.shape[-1] + 1)
-    idx_l = torch.arange(1, lo.shape[-1] + 1)
-    until_u, until_l = ((up != PAD).long() * idx_u).amax(-1).numpy(), ((lo != PAD).long() * idx_l).amax(-1).numpy()
-    order, n_main = plan_clip_groups(until_u, until_l, **(group_plan or {}))
-    B = up.shape[0]
-    group_cuts, host_plan = [(0, n_main), (n_main, B)], None
-    if n_main < B and long_subgroups:
-        # the coins of the step are drawn HERE, in the reference's order: the cut looks at the bar segments
-        host_plan = engine.draw_plan(gt_host, bars, max_length, rng, teacher_forcing_ratio)
-        sub = split_long_group(order[n_main:].tolist(), until_u, until_l, engine.plan_segments(host_plan, bars, True))
-        if sub is not None:
-            order = _np.concatenate([order[:n_main], _np.asarray(sub[0], dtype=order.dtype), _np.asarray(sub[1], dtype=order.dtype)])
-            group_cuts = [(0, n_main), (n_main, n_main + len(sub[0])), (n_main + len(sub[0]), B)]
-    return order, group_cuts, host_plan
-
-
 class TrainStep:
     """model: models.ScoreTranscription on a GPU.  One call = one optimizer step on one minibatch."""
 
@@ -434,7 +321,7 @@ class TrainStep:
                 gt_host = [up_t.cpu(), lo_t.cpu(), up_len.cpu(), lo_len.cpu()]       # the one host sync of the step (Engine.forward reuses it)
             cfg_ = self.model.cfg
             order, group_cuts, host_plan = plan_step_groups(gt_host, cfg_["max_bars"], cfg_["max_length"], rng, teacher_forcing_ratio, self.group_plan,
-                                                            self.long_subgroups)
+                                                            self.long_subgroups, cut=plan_clip_groups)
             B = up_t.shape[0]
             n_main = group_cuts[0][1]
             if n_main < B:
