@@ -11,15 +11,13 @@ does not depend on the recurrence is deferred and batched over all steps of a (b
 import ctypes as C
 import os
 import threading
+from collections import namedtuple
 
 import torch
 
 from . import hip
+from .conv_bwd_plan import CHANS, ConvBwdFlags, plan_convstack_bwd
 from .spec import SOS, VOCAB_SIZE
-
-
-def _os_env(name, default):
-    return os.environ.get(name, default)
 
 
 def _ptr(t, off=0):
@@ -600,7 +598,6 @@ def backward(eng, S, grad_outputs, grad_ready=None, loss_total=None):
     return ctx.finish(grad_ready)
 
 
-_WG_STREAMS = {}
 _DEFERRED_STREAMS = {}
 
 
@@ -716,211 +713,91 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
     return dout                                              # (B, T, conv_feature_size)
 
 
-# How the ConvStack's backward is laid out.  Module constants (tests set them directly); the one environment switch is the documented fallback
-# A2S_FUSE_BN_ROWS=0: the BatchNorm-backward apply as a tensor pass of its own instead of inside the row-streaming weight gradient.
-# _FUSE_BN_APPLY: the round-2 form of that fusion (inside the tiled weight gradient a2s_conv3x3_wgrad_bn) -- parity-tested, slower (the extra operand
-# pushes conv3x3_wgrad<40> from 202 to 281 registers); kept for conv1 only (_FUSE_BN_APPLY_L1), whose weight gradient is its own kernel.
+# How the ConvStack's backward is laid out: conv_bwd_plan.ConvBwdFlags describes each switch.  Module attributes (tests and tools assign them; _convstack_bwd
+# reads them once per call); the one environment switch is the documented fallback A2S_FUSE_BN_ROWS=0.
 _FUSE_BN_APPLY = False
 _FUSE_BN_APPLY_L1 = True
-_DGRAD_BNSTATS = True           # BatchNorm-backward statistics in the data-gradient conv's epilogue
-# synchronised BatchNorm keeps the fused backward paths (statistics from the producers' partials, ONE small all-reduce per layer, the input gradient
-# formed inside the weight-gradient kernel): round 5; False = round 4's separate statistics + apply passes
+_DGRAD_BNSTATS = True
 _SYNC_FUSED = True
-# Where the 19200 -> 256 Linear's weight gradient runs (see _convstack_bwd).  Round 6 A/Bs (profiles/r06_ab_switches.txt, r06_ab_lin_wgrad_placement.txt): in
-# front of the data gradient on the main stream 454.6 ms per step, beside it on the weight-gradient stream (round 5) 454.5, beside conv4's / conv3's /
-# conv2's weight gradient 456.9 / 456.3 / 463.3 -- no placement of this 11 ms launch moves the step; the simplest is the default.
 _LIN_WGRAD_AT = "before"
-_FUSE_BN_ROWS = os.environ.get("A2S_FUSE_BN_ROWS", "1") != "0"        # BatchNorm-backward apply inside the row-streaming weight gradient's staging
+_FUSE_BN_ROWS = os.environ.get("A2S_FUSE_BN_ROWS", "1") != "0"
+# the gradient entering a layer with what the kernel that wrote it reduced on the way: statistics partials (tensor, blocks), max |g| (scalar or per channel)
+GradIn = namedtuple("GradIn", "g partial amax", defaults=(None, None))
 
 
-def _linear_dgrad_generic(L, dev, rows, F, Cf, dz, Wout, da, y4, bn4, dz_amax, w_amax):
-    """Data gradient of the 19200 -> Cf Linear + layer-4 BatchNorm-backward statistics on the generic two-term GEMM tiles (shapes the kernel of
-    csrc/a2s_linear.hip does not take, or hip.LINEAR_KERNELS off).  Returns (partials, blocks)."""
-    nblk = L.a2s_gemm_bnstats_blocks(rows, F)
-    part = torch.empty((nblk, 40, 2), dtype=torch.float32, device=dev)
-    if L.a2s_debug_get(b"gemm_bf16x3") > 0:
-        # a k-contiguous copy of the weight (19.7 MB) puts this product on the split-operand path of the GEMM (both operands k-contiguous)
-        Wt = Wout.t().contiguous()
-        wb, s_bk, s_bn = Wt, 1, Cf
-    else:
-        wb, s_bk, s_bn = Wout, 40 * F, 1
-    hip.check(L.a2s_gemm_f32_bnstats_scaled(hip.stream(), rows, 40 * F, Cf, hip._p(dz), Cf, 1, hip._p(wb), s_bk, s_bn, hip._p(da), 40 * F, hip._p(y4), hip._p(bn4[0]),
-                                            hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F, hip._p(part), hip._p(dz_amax), hip._p(w_amax)),
-              "a2s_gemm_f32_bnstats_scaled")
-    return part, nblk
+def _bn_bwd(source, eng, G, name, gin, x, bn, dims, mask=None, dx=None, amax=None):
+    """BatchNorm backward of gin.g, statistics from `source` (conv_bwd_plan.stats_source); dx None: statistics only.  Returns c12, the per-channel means."""
+    dgamma, dbeta = G[name + ".weight"], G[name + ".bias"]
+    if source in ("own", "partial"):
+        return hip.bn_bwd(gin.g, x, bn, mask, dgamma, dbeta, dx, dims, amax, gin.partial if source == "partial" else None)
+    import torch.distributed as dist          # statistics of the global minibatch (see Engine.__init__)
+    return hip.bn_bwd_sync(gin.g, x, bn, mask, dgamma, dbeta, dims, eng.bn_counts[name], dist.all_reduce, gin.partial if source == "sync_partial" else None)
 
 
 def _convstack_bwd(eng, S, G, cs, d_out, B, T, F):
-    L = hip.lib()
-    dev = d_out.device
-    Cf = eng.cfg["conv_feature_size"]
-    rows = B * T
-
-    def bn_bwd(g, x, bn, name, mask, n_rows, C_, F_, stats_only=False, partial=None, amax=None):
-        """stats_only: dgamma / dbeta and the two per-channel means (returned) only -- the input gradient is then formed inside the
-        weight-gradient kernel (a2s_conv3x3_wgrad_bn).  partial = (tensor, nblocks): the statistics partials were already produced by
-        the data-gradient convolution that wrote g (a2s_conv3x3_dgrad_bnstats): no statistics pass."""
-        mean, invstd, scale, shift = bn
-        if partial is not None and eng.sync_bn and stats_only:
-            # synchronised statistics on the fused path (round 5): the producer's partials -> this rank's sums -> ONE small all-reduce ->
-            # c12 from the global sums; dgamma / dbeta from the local ones (torch.nn.SyncBatchNorm's rule).  No pass over (g, x).
-            import torch.distributed as dist
-            local = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_sums_from_partial(hip.stream(), hip._p(partial[0]), partial[1], C_, hip._p(local)), "a2s_bn_bwd_sums_from_partial")
-            glob = local.clone()
-            dist.all_reduce(glob)
-            c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_c12_from_sums(hip.stream(), hip._p(local), hip._p(glob), eng.bn_counts[name], hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]),
-                                                 hip._p(c12), C_), "a2s_bn_bwd_c12_from_sums")
-            return c12
-        if partial is not None and not eng.sync_bn:
-            c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_from_partial_amax(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift),
-                                                     hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), None if stats_only else hip._p(g), hip._p(partial[0]),
-                                                     partial[1], hip._p(c12), n_rows, C_, F_, hip._p(amax)), "a2s_bn_bwd_from_partial")
-            return c12 if stats_only else g
-        part = torch.empty(L.a2s_bn_bwd_partial_floats(n_rows, C_, F_), dtype=torch.float32, device=dev)
-        c12 = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-        if eng.sync_bn:                                       # statistics of the global minibatch (see Engine.__init__)
-            import torch.distributed as dist
-            local = torch.empty(2 * C_, dtype=torch.float32, device=dev)
-            hip.check(L.a2s_bn_bwd_stats(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
-                                         hip._p(part), hip._p(local), n_rows, C_, F_), "a2s_bn_bwd_stats")
-            glob = local.clone()
-            dist.all_reduce(glob)
-            hip.check(L.a2s_bn_bwd_apply(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
-                                         hip._p(local), hip._p(glob), eng.bn_counts[name], hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), hip._p(g),
-                                         hip._p(c12), n_rows, C_, F_), "a2s_bn_bwd_apply")
-            return g
-        hip.check(L.a2s_bn_bwd_amax(hip.stream(), hip._p(g), hip._p(x), hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip._p(mask), 1.0 / 0.8,
-                                    hip._p(G[name + ".weight"]), hip._p(G[name + ".bias"]), None if stats_only else hip._p(g), hip._p(part), hip._p(c12), n_rows, C_, F_,
-                                    hip._p(amax)), "a2s_bn_bwd")
-        return c12 if stats_only else g                       # in place: g now holds dx
-
-    # dropout + ReLU + BatchNorm1d over the (B*T, Cf) Linear output
-    g = d_out.reshape(rows, Cf).contiguous()
-    dz_amax = torch.zeros(1, dtype=torch.float32, device=dev)
-    dz = bn_bwd(g, cs["z"], cs["out_bn"], "convstack.out_bn", cs["drop"], rows, Cf, 1, amax=dz_amax)
-    if eng.sync_bn:
+    """Walks conv_bwd_plan.plan_convstack_bwd: every decision is the plan's, this function allocates and launches."""
+    if cs["a4"] is not None:
+        raise ValueError("the Linear's input is re-formed from y4 on the fly: a materialised a4 has no backward path")
+    L, dev, Cf, rows = hip.lib(), d_out.device, eng.cfg["conv_feature_size"], B * T
+    flags = ConvBwdFlags(_FUSE_BN_ROWS, _DGRAD_BNSTATS, _SYNC_FUSED, _FUSE_BN_APPLY, _FUSE_BN_APPLY_L1, _LIN_WGRAD_AT)
+    lin, layers = plan_convstack_bwd(flags, eng.sync_bn, rows, F, hip.LINEAR_KERNELS, bool(L.a2s_linear_dgrad_eligible(rows, 40 * F, Cf, F)),
+                                     {c: bool(L.a2s_conv3x3_wgrad_bn_ranged_eligible(F, *c)) for c in CHANS[1:]})
+    scalar = lambda: torch.zeros(1, dtype=torch.float32, device=dev)
+    # dropout + ReLU + BatchNorm1d over the (B*T, Cf) Linear output, in place
+    dz, dz_amax = d_out.reshape(rows, Cf).contiguous(), scalar()
+    _bn_bwd(lin.stats, eng, G, "convstack.out_bn", GradIn(dz), cs["z"], cs["out_bn"], (rows, Cf, 1), cs["drop"], dz, dz_amax)
+    if lin.absmax_after:
         hip.absmax(dz, dz_amax)
-    w_amax = cs.get("w_out_amax")
-    # Linear 19200 -> Cf, no bias:  dW += dz^T a4 ; da4 = dz W
-    a4 = cs["a4"]
-    g_partial = None                     # BatchNorm-backward statistics partials of g, when the kernel that produced g also reduced them
-    g_amax = None                        # max |g| (device scalar), when the kernel that produced g also reduced it
-    Wout = S["convstack.out.weight"]
-    if a4 is None:                         # the Linear read relu(bn4(y4)) on the fly: so does its weight gradient
-        y4 = cs["y"][3].view(rows, 40 * F)
-        da = torch.empty_like(y4)
-        bn4 = cs["bn"][3]
-        def lin_wgrad():
-            if not hip.linear_wgrad(dz, y4, (bn4[2], bn4[3], F), dz_amax, cs["abound"][3], G["convstack.out.weight"]):       # round 4: csrc/a2s_linear.hip
-                _linear_bwd(y4, Wout, dz, G, "convstack.out.weight", None, x_affine=(bn4[2], bn4[3], F), dy_amax=dz_amax, x_bound=cs["abound"][3])
-        # Where the Linear's weight gradient (reads y4 once, 10-11 ms alone; nothing but the optimizer waits for it) runs -- _LIN_WGRAD_AT:
-        #   "before"  on the main stream in front of the data gradient (on the backward's critical chain);
-        #   "beside"  round 5: on the weight-gradient stream beside the data gradient;
-        #   4 / 3 / 2 on the weight-gradient stream from the moment layer i's weight gradient is enqueued on the main stream (beside the later, smaller
-        #             launches of the chain); the main stream joins that stream at the end of the ConvStack backward.
-        lin_at = _LIN_WGRAD_AT
-        lin_overlap = lin_at != "before"
+    # Linear 19200 -> Cf, no bias, which read relu(bn4(y4)) on the fly (so does its weight gradient):  dW += dz^T a4 ; da4 = dz W
+    Wout, y4, bn4 = S["convstack.out.weight"], cs["y"][3].view(rows, 40 * F), cs["bn"][3]
+    da = torch.empty_like(y4)
 
-        def lin_wgrad_side():
-            wg_stream = _weight_grad_stream(dev)
-            ev = torch.cuda.Event()
-            ev.record()
-            wg_stream.wait_event(ev)
-            with torch.cuda.stream(wg_stream):
-                lin_wgrad()
-        if lin_at == "beside":
-            lin_wgrad_side()
-        elif lin_at == "before":
+    def lin_wgrad():
+        if not hip.linear_wgrad(dz, y4, (bn4[2], bn4[3], F), dz_amax, cs["abound"][3], G["convstack.out.weight"]):       # csrc/a2s_linear.hip
+            _linear_bwd(y4, Wout, dz, G, "convstack.out.weight", None, x_affine=(bn4[2], bn4[3], F), dy_amax=dz_amax, x_bound=cs["abound"][3])
+    def lin_wgrad_beside():          # on the weight-gradient stream, after everything the main stream holds so far
+        wg_stream, ev = _weight_grad_stream(dev), torch.cuda.Event()
+        ev.record()
+        wg_stream.wait_event(ev)
+        with torch.cuda.stream(wg_stream):
             lin_wgrad()
-        if _DGRAD_BNSTATS and (not eng.sync_bn or _SYNC_FUSED) and F >= 128 and F % 4 == 0 and rows > 64:      # (the epilogue lives in the 128-row GEMM tile)
-            # data gradient of the Linear with the layer-4 BatchNorm-backward statistics accumulated in the GEMM's epilogue
-            if w_amax is None:
-                w_amax = hip.absmax(Wout)
-            if hip.LINEAR_KERNELS and L.a2s_linear_dgrad_eligible(rows, 40 * F, Cf, F):
-                # round 4: the kernel of its own (csrc/a2s_linear.hip): the weight pre-split once per launch, a workgroup's rows of dz resident in LDS
-                # for all column tiles, no barrier in the sweep
-                nblk = L.a2s_linear_dgrad_blocks(rows)
-                part = torch.empty((nblk, 40, 2), dtype=torch.float32, device=dev)
-                Wt = Wout.t().contiguous()
-                nb = L.a2s_linear_dgrad_ws_bytes(40 * F, Cf)
-                lws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-                g_amax = torch.zeros(1, dtype=torch.float32, device=dev)          # max |da|: the range of the BatchNorm backward fused into conv4's weight gradient
-                hip.check(L.a2s_linear_dgrad_bnstats(hip.stream(), rows, 40 * F, Cf, hip._p(dz), Cf, hip._p(Wt), hip._p(da), 40 * F, hip._p(y4), hip._p(bn4[0]),
-                                                     hip._p(bn4[1]), hip._p(bn4[2]), hip._p(bn4[3]), F, hip._p(part), hip._p(dz_amax), hip._p(w_amax), hip._p(lws), nb,
-                                                     hip._p(g_amax)), "a2s_linear_dgrad_bnstats")
-                g_partial = (part, nblk)
-            else:
-                g_partial = _linear_dgrad_generic(L, dev, rows, F, Cf, dz, Wout, da, y4, bn4, dz_amax, w_amax)
-        else:
-            hip.gemm(dz, Cf, 1, Wout, 40 * F, 1, da, 40 * F, rows, 40 * F, Cf)
+    if lin.wgrad_at in ("before", "beside"):
+        (lin_wgrad if lin.wgrad_at == "before" else lin_wgrad_beside)()
+    gin = GradIn(da.view(B, T, 40, F))
+    if lin.dgrad == "gemm":
+        hip.gemm(dz, Cf, 1, Wout, 40 * F, 1, da, 40 * F, rows, 40 * F, Cf)
     else:
-        da = torch.empty_like(a4)
-        _linear_bwd(a4, Wout, dz, G, "convstack.out.weight", None, dx=da)
-    chans = [(1, 20), (20, 20), (20, 40), (40, 40)]
-    g = da.view(B, T, 40, F)
-    for i in (4, 3, 2, 1):
-        ci, co = chans[i - 1]
-        y = cs["y"][i - 1]                                    # pre-BN conv output of this layer
-        x_in = cs["y"][i - 2] if i > 1 else cs["x0"]
-        in_bn = cs["bn"][i - 2] if i > 1 else None
-        nb = L.a2s_conv3x3_wgrad_workspace_bytes(ci, co)
-        ws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-        # the first layer has no data-gradient consumer: its BatchNorm input gradient is only read by the (streaming, HBM-bound)
-        # weight-gradient kernel, which forms it on the fly -- one pass over (g, y) instead of apply (read 2, write 1) + read 1
-        fuse_here = _FUSE_BN_APPLY or (i == 1 and _FUSE_BN_APPLY_L1)
-        # max |dy| of this layer's output gradient, reduced by the kernel that writes dy: the two-term fp16 data-gradient convolution
-        # below scales its operand by the matching power of two (gradients would otherwise sit in fp16's subnormal range)
-        dy_amax = torch.zeros(1, dtype=torch.float32, device=dev) if (i > 1 and (not eng.sync_bn or _SYNC_FUSED)) else None
-        fuse_rows = (_FUSE_BN_ROWS and (not eng.sync_bn or _SYNC_FUSED) and i > 1 and g_amax is not None and g_partial is not None and in_bn is not None
-                     and L.a2s_conv3x3_wgrad_bn_ranged_eligible(F, ci, co))
-        if a4 is None and lin_at == i:
-            lin_wgrad_side()
-        if fuse_rows:
-            # round 4: BatchNorm backward as statistics only; dy is formed by the STAGING waves of the row-streaming weight-gradient kernel (they
-            # wait 40-57 % of their time for the multiply waves), written once for the data-gradient convolution: one pass over (g, y) less
-            bn_i = cs["bn"][i - 1]
-            c12 = bn_bwd(g, y, bn_i, f"convstack.bn{i}", None, rows, co, F, stats_only=True, partial=g_partial)
-            dy = g                                                 # in place: every element is read and written once, by the same thread
-            hip.check(L.a2s_conv3x3_wgrad_bn_ranged(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]), hip._p(c12),
-                                                    hip._p(g_amax), g_amax.numel(), hip._p(cs["yabs"][i - 1]), hip._p(dy), hip._p(dy_amax), hip._p(x_in),
-                                                    hip._p(in_bn[2]), hip._p(in_bn[3]), hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), nb, B, T, F, ci, co,
-                                                    hip._p(cs["abound"][i - 2])), "a2s_conv3x3_wgrad_bn_ranged")
-        elif eng.sync_bn or not fuse_here:
-            dy = bn_bwd(g, y, cs["bn"][i - 1], f"convstack.bn{i}", None, rows, co, F, partial=g_partial, amax=dy_amax)
-            if eng.sync_bn and dy_amax is not None:            # (the synchronised apply pass does not reduce the range of what it writes)
-                hip.absmax(dy, dy_amax)
-            hip.conv3x3_wgrad(dy, x_in.view(B, T, ci, F), in_bn[2] if in_bn else None, in_bn[3] if in_bn else None, G[f"convstack.conv{i}.weight"], ws,
-                              dy_amax, cs["abound"][i - 2] if in_bn else None)
+        w_amax = cs["w_out_amax"] if cs.get("w_out_amax") is not None else hip.absmax(Wout)
+        gin = GradIn(gin.g, *hip.linear_dgrad_bnstats(dz, Wout, da, y4, bn4, F, dz_amax, w_amax, lin.dgrad == "own"))
+    for lp in layers:
+        i, ci, co, g = lp.i, lp.ci, lp.co, gin.g
+        y, bn_i, dW = cs["y"][i - 1], cs["bn"][i - 1], G[f"convstack.conv{i}.weight"]          # pre-BN conv output of this layer, ...
+        x_in, in_bn, in_bound = (cs["y"][i - 2], cs["bn"][i - 2], cs["abound"][i - 2]) if i > 1 else (cs["x0"], None, None)
+        ws = torch.empty(L.a2s_conv3x3_wgrad_workspace_bytes(ci, co) // 4, dtype=torch.float32, device=dev)
+        dy_amax = scalar() if lp.dy_range else None          # max |dy|: the two-term fp16 kernels scale their operand by the matching power of two
+        if lp.lin_wgrad:
+            lin_wgrad_beside()
+        bn_args = (lp.stats, eng, G, f"convstack.bn{i}", gin, y, bn_i, (rows, co, F))
+        dy = g                                                 # in place, but for "tiled"
+        if lp.form == "rows":
+            hip.conv3x3_wgrad_bn(g, y, bn_i, _bn_bwd(*bn_args), None, x_in, in_bn, dW, ws, ranged=(gin.amax, cs["yabs"][i - 1], dy_amax, in_bound))
+        elif lp.form == "apply":
+            _bn_bwd(*bn_args, dx=g, amax=dy_amax)
+            if lp.absmax_after:            # (the synchronised apply pass does not reduce the range of what it writes)
+                hip.absmax(g, dy_amax)
+            hip.conv3x3_wgrad(g, x_in.view(B, T, ci, F), in_bn[2] if in_bn else None, in_bn[3] if in_bn else None, dW, ws, dy_amax, in_bound)
         else:
-            # BatchNorm backward: statistics pass only; dy = scale (g' - c1 - xhat c2) is formed by the weight-gradient kernel while
-            # it stages its dy operand (MFMA-bound, HBM to spare) and written out for the data-gradient convolution below
-            bn_i = cs["bn"][i - 1]
-            c12 = bn_bwd(g, y, bn_i, f"convstack.bn{i}", None, rows, co, F, stats_only=True, partial=g_partial)
             dy = torch.empty_like(g) if i > 1 else None
-            hip.check(L.a2s_conv3x3_wgrad_bn(hip.stream(), hip._p(g), hip._p(y), hip._p(bn_i[0]), hip._p(bn_i[1]), hip._p(bn_i[2]), hip._p(bn_i[3]), hip._p(c12),
-                                             hip._p(dy), hip._p(x_in), hip._p(in_bn[2]) if in_bn else None, hip._p(in_bn[3]) if in_bn else None,
-                                             hip._p(G[f"convstack.conv{i}.weight"]), hip._p(ws), nb, B, T, F, ci, co), "a2s_conv3x3_wgrad_bn")
-        if i > 1:
-            gprev = torch.empty((B, T, ci, F), dtype=torch.float32, device=dev)
-            cws = hip.conv_workspace(co, dev)
-            if _DGRAD_BNSTATS and (not eng.sync_bn or _SYNC_FUSED):
-                # the data-gradient convolution also accumulates the BatchNorm-backward statistics of the layer below in its epilogue
-                bn_l = cs["bn"][i - 2]
-                nblk = L.a2s_conv3x3_stat_blocks(B, T, F, co)
-                part = torch.empty((nblk, ci, 2), dtype=torch.float32, device=dev)
-                g_amax_next = torch.empty(ci, dtype=torch.float32, device=dev) if (_FUSE_BN_ROWS and i > 2) else None      # max |g| per channel (zeroed by the launch)
-                hip.check(L.a2s_conv3x3_dgrad_bnstats_ranged(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev), hip._p(cs["y"][i - 2]),
-                                                             hip._p(bn_l[0]), hip._p(bn_l[1]), hip._p(bn_l[2]), hip._p(bn_l[3]), hip._p(part), B, T, F, co, ci,
-                                                             hip._p(cws), hip._p(dy_amax) if not fuse_here else None, hip._p(g_amax_next)), "a2s_conv3x3_dgrad_bnstats")
-                g_partial = (part, nblk)
-            else:
-                hip.check(L.a2s_conv3x3(hip.stream(), hip._p(dy), hip._p(S[f"convstack.conv{i}.weight"]), hip._p(gprev), None, None, None, B, T, F, co, ci, 1,
-                                        hip._p(cws)), "a2s_conv3x3 dgrad")
-                g_partial = None
-            g = gprev
-            g_amax = g_amax_next if (_DGRAD_BNSTATS and (not eng.sync_bn or _SYNC_FUSED)) else None
-    if a4 is None and lin_overlap:
-        torch.cuda.current_stream().wait_stream(_weight_grad_stream(dev))      # the Linear's weight gradient (issued beside the data gradient above)
+            hip.conv3x3_wgrad_bn(g, y, bn_i, _bn_bwd(*bn_args), dy, x_in, in_bn, dW, ws)
+        if lp.dgrad == "none":
+            break
+        gprev, cws = torch.empty((B, T, ci, F), dtype=torch.float32, device=dev), hip.conv_workspace(co, dev)
+        below = nblk = out_amax = None
+        if lp.dgrad == "bnstats":                              # statistics partials of the layer below, and its per-channel range, from the epilogue
+            nblk = L.a2s_conv3x3_stat_blocks(B, T, F, co)
+            below = (x_in, in_bn, torch.empty((nblk, ci, 2), dtype=torch.float32, device=dev))
+            out_amax = torch.empty(ci, dtype=torch.float32, device=dev) if lp.out_range else None      # max |g| per channel (zeroed by the launch)
+        hip.conv3x3_dgrad(dy, S[f"convstack.conv{i}.weight"], gprev, cws, below, dy_amax if lp.dgrad_range else None, out_amax)
+        gin = GradIn(gprev, (below[2], nblk) if below else None, out_amax)
+    if lin.join_side:
+        torch.cuda.current_stream().wait_stream(_weight_grad_stream(dev))      # the Linear's weight gradient, issued beside the chain above

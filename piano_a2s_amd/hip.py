@@ -712,17 +712,11 @@ def conv3x3_forward(x, w, y, scale, shift, partial, cws, in_absmax=None, out_abs
 def conv3x3_dgrad_for_test(dy, w, yl):
     """Data gradient of a (Cin -> Cout) layer as engine_bwd issues it: dy (B, T, Cout, F) -> dx (B, T, Cin, F), operand scaled by the
     power of two derived from max|dy|, BatchNorm-backward statistics epilogue against `yl` (identity BatchNorm parameters here)."""
-    L = lib()
-    B, T, Cout, F = dy.shape
-    Cin = w.shape[1]
-    dev = dy.device
+    (B, T, Cout, F), Cin, dev = dy.shape, w.shape[1], dy.device
     dx = torch.full((B, T, Cin, F), float("nan"), device=dev)
-    amax = absmax(dy)
-    part = torch.zeros(L.a2s_conv3x3_stat_blocks(B, T, F, Cout), Cin, 2, device=dev)
-    cws = conv_workspace(Cout, dev)
+    part = torch.zeros(lib().a2s_conv3x3_stat_blocks(B, T, F, Cout), Cin, 2, device=dev)
     zeros, ones = torch.zeros(Cin, device=dev), torch.ones(Cin, device=dev)
-    check(L.a2s_conv3x3_dgrad_bnstats_scaled(stream(), _p(dy), _p(w), _p(dx), _p(yl), _p(zeros), _p(ones), _p(ones), _p(zeros), _p(part),
-                                             B, T, F, Cout, Cin, _p(cws), _p(amax)), "a2s_conv3x3_dgrad_bnstats_scaled")
+    conv3x3_dgrad(dy, w, dx, conv_workspace(Cout, dev), (yl, (zeros, ones, ones, zeros), part), absmax(dy))
     torch.cuda.synchronize()
     return dx
 
@@ -791,6 +785,85 @@ def linear_wgrad(dz, x2d, x_affine, dz_absmax, x_bound, G):
     check(L.a2s_linear_wgrad(stream(), M, N, K, _p(dz), N, _p(x2d), K, _p(G), K, _p(x_affine[0]), _p(x_affine[1]), x_affine[2], _p(dz_absmax), _p(x_bound), _p(ws), nb),
           "a2s_linear_wgrad")
     return True
+
+
+# ---- the ConvStack backward's launches as engine_bwd._convstack_bwd issues them (conv_bwd_plan.py says when).  bn = (mean, invstd, scale, shift); dims = (rows,
+# channels, F); dgamma / dbeta accumulate; every BatchNorm backward returns c12, its two per-channel means; mask: dropout (kept elements scaled by 1 / 0.8)
+def _f32(like, *shape):
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+def bn_bwd(g, x, bn, mask, dgamma, dbeta, dx, dims, amax, partial=None):
+    """dx (None: statistics only; g: in place) and max |dx| into amax; statistics by a pass of its own, or from partial = (tensor, blocks) of g's producer."""
+    c12 = _f32(g, 2 * dims[1])
+    if partial is None:
+        part = _f32(g, lib().a2s_bn_bwd_partial_floats(*dims))
+        check(lib().a2s_bn_bwd_amax(stream(), _p(g), _p(x), *map(_p, bn), _p(mask), 1.0 / 0.8, _p(dgamma), _p(dbeta), _p(dx), _p(part), _p(c12), *dims, _p(amax)),
+              "a2s_bn_bwd")
+    else:
+        check(lib().a2s_bn_bwd_from_partial_amax(stream(), _p(g), _p(x), *map(_p, bn), _p(dgamma), _p(dbeta), _p(dx), _p(partial[0]), partial[1], _p(c12), *dims,
+                                                 _p(amax)), "a2s_bn_bwd_from_partial")
+    return c12
+
+
+def bn_bwd_sync(g, x, bn, mask, dgamma, dbeta, dims, count, all_reduce, partial=None):
+    """Synchronised: this rank's sums (partial None: by a pass, and dx over g in place; else from the partials, statistics only) and ONE small all-reduce."""
+    L, local, c12 = lib(), _f32(g, 2 * dims[1]), _f32(g, 2 * dims[1])
+    if partial is None:
+        part = _f32(g, L.a2s_bn_bwd_partial_floats(*dims))
+        check(L.a2s_bn_bwd_stats(stream(), _p(g), _p(x), *map(_p, bn), _p(mask), 1.0 / 0.8, _p(part), _p(local), *dims), "a2s_bn_bwd_stats")
+    else:
+        check(L.a2s_bn_bwd_sums_from_partial(stream(), _p(partial[0]), partial[1], dims[1], _p(local)), "a2s_bn_bwd_sums_from_partial")
+    glob = local.clone()
+    all_reduce(glob)
+    if partial is None:
+        check(L.a2s_bn_bwd_apply(stream(), _p(g), _p(x), *map(_p, bn), _p(mask), 1.0 / 0.8, _p(local), _p(glob), count, _p(dgamma), _p(dbeta), _p(g), _p(c12), *dims),
+              "a2s_bn_bwd_apply")
+    else:
+        check(L.a2s_bn_bwd_c12_from_sums(stream(), _p(local), _p(glob), count, _p(dgamma), _p(dbeta), _p(c12), dims[1]), "a2s_bn_bwd_c12_from_sums")
+    return c12
+
+
+def conv3x3_wgrad_bn(g, y, bn, c12, dy, x, in_bn, dW, ws, ranged=None):
+    """dW (Cout, Cin, 3, 3) += weight gradient by a kernel that forms dy from (g, y, c12) itself; in_bn: of the layer below (None: x as it is).  ranged None:
+    tiled, dy (None: not needed) written out; (g_absmax, y_absmax, dy_absmax out, act_absmax): row-streaming, dy over g IN PLACE (LayerPlan.form)."""
+    B, T, _, F = g.shape
+    sc, sh = in_bn[2:] if in_bn else (None, None)
+    tail = _p(x), _p(sc), _p(sh), _p(dW), _p(ws), ws.numel() * 4, B, T, F, dW.shape[1], dW.shape[0]
+    if ranged is None:
+        return check(lib().a2s_conv3x3_wgrad_bn(stream(), _p(g), _p(y), *map(_p, bn), _p(c12), _p(dy), *tail), "a2s_conv3x3_wgrad_bn")
+    g_absmax, y_absmax, dy_absmax, act_absmax = ranged
+    check(lib().a2s_conv3x3_wgrad_bn_ranged(stream(), _p(g), _p(y), *map(_p, bn), _p(c12), _p(g_absmax), g_absmax.numel(), _p(y_absmax), _p(g), _p(dy_absmax), *tail,
+                                            _p(act_absmax)), "a2s_conv3x3_wgrad_bn_ranged")
+
+
+def conv3x3_dgrad(dy, w, dx, cws, below=None, dy_absmax=None, out_absmax=None):
+    """dx (B, T, Cin, F) = data gradient for weight w (Cout, Cin, 3, 3): plain, or with below = (y, bn, partial out) of the layer below its statistics
+    partials in the epilogue, operand scaled by max |dy| (dy_absmax; None: unscaled), per-channel max |dx| into out_absmax if given (LayerPlan.dgrad)."""
+    B, T, _, F = dy.shape
+    if below is None:
+        return check(lib().a2s_conv3x3(stream(), _p(dy), _p(w), _p(dx), None, None, None, B, T, F, w.shape[0], w.shape[1], 1, _p(cws)), "a2s_conv3x3 dgrad")
+    check(lib().a2s_conv3x3_dgrad_bnstats_ranged(stream(), _p(dy), _p(w), _p(dx), _p(below[0]), *map(_p, below[1]), _p(below[2]), B, T, F, w.shape[0], w.shape[1],
+                                                 _p(cws), _p(dy_absmax), _p(out_absmax)), "a2s_conv3x3_dgrad_bnstats")
+
+
+def linear_dgrad_bnstats(dz, W, da, y, bn, F, dz_absmax, w_absmax, own):
+    """da (rows, K) = dz W of the ConvStack's Linear, layer 4's BatchNorm-backward statistics (y, bn; column k is channel k // F) in the epilogue; own:
+    the kernel of csrc/a2s_linear.hip, else the generic GEMM tiles (LinearPlan.dgrad).  Returns ((partials, blocks), max |da| or None)."""
+    L, (rows, Cf), K = lib(), dz.shape, W.shape[1]
+    nblk = L.a2s_linear_dgrad_blocks(rows) if own else L.a2s_gemm_bnstats_blocks(rows, F)
+    part = _f32(dz, nblk, K // F, 2)
+    if own:
+        nb = L.a2s_linear_dgrad_ws_bytes(K, Cf)
+        Wt, ws, amax = W.t().contiguous(), _f32(dz, nb // 4), torch.zeros(1, dtype=torch.float32, device=dz.device)
+        check(L.a2s_linear_dgrad_bnstats(stream(), rows, K, Cf, _p(dz), Cf, _p(Wt), _p(da), K, _p(y), *map(_p, bn), F, _p(part), _p(dz_absmax), _p(w_absmax), _p(ws), nb,
+                                         _p(amax)), "a2s_linear_dgrad_bnstats")
+        return (part, nblk), amax
+    # a k-contiguous copy of the weight (19.7 MB) puts this product on the split-operand path of the GEMM (both operands k-contiguous)
+    wb, s_bk, s_bn = (W.t().contiguous(), 1, Cf) if L.a2s_debug_get(b"gemm_bf16x3") > 0 else (W, K, 1)
+    check(L.a2s_gemm_f32_bnstats_scaled(stream(), rows, K, Cf, _p(dz), Cf, 1, _p(wb), s_bk, s_bn, _p(da), K, _p(y), *map(_p, bn), F, _p(part), _p(dz_absmax), _p(w_absmax)),
+          "a2s_gemm_f32_bnstats_scaled")
+    return (part, nblk), None
 
 
 _TALLK_WS = {}

@@ -681,3 +681,38 @@ def test_convstack_range_chain_with_every_layer_at_another_magnitude(dev, paths)
         if e > 2e-4:
             failures.append((k, e))
     assert not failures, (paths, failures)
+
+
+HOST_VARIANTS = {"_FUSE_BN_ROWS": False, "_DGRAD_BNSTATS": False, "_FUSE_BN_APPLY": True, "_FUSE_BN_APPLY_L1": False}
+
+
+@gpu
+@pytest.mark.parametrize("attr", list(HOST_VARIANTS))
+def test_convstack_range_chain_on_the_host_variants(dev, attr):
+    """The same chain, same float64 reference and same 2e-4 bar with one switch of engine_bwd (conv_bwd_plan.ConvBwdFlags) off its default: the
+    BatchNorm-backward apply as a pass of its own, the plain data gradients with statistics passes of their own, the apply inside the tiled
+    weight gradient of every layer, and of none.  At 69 rows the Linear's statistics epilogue and the row kernels are eligible, so each variant
+    changes the launches."""
+    from piano_a2s_amd import engine, engine_bwd
+    cfg, st, x, d_out, out64, grads64, _ = _chain_ref64()
+    B, T, F = CHAIN_SHAPE
+    prev = getattr(engine_bwd, attr)
+    try:
+        setattr(engine_bwd, attr, HOST_VARIANTS[attr])
+        S = {k: v.clone().to(dev) for k, v in st.items() if k.startswith("convstack.")}
+        eng = engine.Engine(cfg)
+        out, cs = eng.convstack(S, x.to(dev), training=True)
+        G = {k: torch.zeros_like(S[k]) for k in CONV_PARAMS}
+        engine_bwd._convstack_bwd(eng, S, G, cs, d_out.to(dev).clone(), B, T, F)
+        torch.cuda.synchronize()
+    finally:
+        setattr(engine_bwd, attr, prev)
+    failures = []
+    for k, (got, ref) in {"out": (out, out64), **{k: (G[k], grads64[k]) for k in CONV_PARAMS}}.items():
+        assert torch.isfinite(got).all(), (attr, k)
+        e = _rel_max(got.cpu(), ref)
+        _report(f"chain {attr} = {HOST_VARIANTS[attr]}: {k}", e)
+        print(f"chain {attr} = {HOST_VARIANTS[attr]}: {k}: {e:.3e}")
+        if e > 2e-4:
+            failures.append((k, e))
+    assert not failures, (attr, failures)
