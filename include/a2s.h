@@ -225,6 +225,9 @@ size_t a2s_attn_workspace_floats(int B, int T, int H);
 /* the same for a fused-bars decoder call (a2s_note_dec_args.n_clips): `groups` bars of n_clips clips in one call */
 size_t a2s_attn_workspace_floats_fused(int n_clips, int T, int H, int groups);
 
+/* y[r, :V] = log_softmax(x[r, :V]) over R rows with row strides ldx / ldy; argmax_out (R ints, may be NULL) = the lowest index among the
+ * row's maxima.  The index written is always in [0, V): a row without an ordered value (all NaN, all -inf) gives 0 -- its
+ * log-probabilities are NaN all the same. */
 int a2s_log_softmax_rows(void* stream, const float* x, long ldx, float* y, long ldy, int* argmax_out, int R, int V);
 int a2s_embed_rows(void* stream, const float* table, const long long* ids64, const int* ids32, long id_stride,
                    int const_id, float* out, long ldo, int col0, int R, int E, const uint8_t* keep_mask, float inv_keep);
@@ -275,6 +278,9 @@ typedef struct a2s_note_dec_args {
     const int* tf_flags_dev;          /* device, `steps` ints: the same bits as tf_flags (NULL with tf_flags NULL) */
     float* persist_ws; size_t persist_ws_bytes;   /* a2s_note_decoder_persist_ws_bytes(n_clips, R, steps) bytes, 256-byte aligned, or NULL */
 } a2s_note_dec_args;
+/* The id a step chooses -- written to argmax_out, compared with eos_id, and the row of `emb` the next step's input is gathered from when the
+ * step is not teacher-forced -- is always in [0, V), on every path (launch per step, few-row, persistent): a row of logits without an ordered
+ * value (all NaN, all -inf) chooses 0.  Its log-probabilities stay NaN, so the loss stays non-finite and the update is skipped. */
 int a2s_note_decoder_fwd(void* stream, const a2s_note_dec_args* args, int* steps_done);
 /* ---- grammar-constrained greedy decoding (csrc/a2s_grammar.hip).  A token grammar is a finite automaton given as a
  * device table next_state[s * V + v] (n_states x V signed bytes, 1 <= n_states <= 127, V <= 256): the state after token v in state s, negative

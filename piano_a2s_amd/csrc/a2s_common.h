@@ -170,6 +170,11 @@ __device__ __forceinline__ GruCellGrad gru_cell_bwd(float dh, float rg, float zg
     o.dhz = dh * zg;
     return o;
 }
+// Arg-maximum of a row of logits: every lane starts from "no candidate yet" and takes an index only where a value compares greater than
+// -inf, so a row without an ordered value (all NaN, all -inf) leaves the sentinel behind after the wave reduction.  The id a kernel stores,
+// compares with <eos> or gathers an embedding row by must lie in the row: such a row chooses index 0 (its log-probabilities stay NaN).
+#define A2S_ARGMAX_NONE 0x7fffffff
+__device__ __forceinline__ int argmax_in_row(int mi) { return mi != A2S_ARGMAX_NONE ? mi : 0; }
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -542,7 +542,7 @@ __global__ __launch_bounds__(NTH, 2) void dec_persist_fwd(DecPersistFwd a) {
                     if (__all(ok)) break;
                     if (!spin.again()) break;
                 }
-                float m = -INFINITY; int mi = 0x7fffffff;
+                float m = -INFINITY; int mi = A2S_ARGMAX_NONE;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) if (v[k] > m) { m = v[k]; mi = lane + 64 * k; }
 #pragma unroll
@@ -550,6 +550,7 @@ __global__ __launch_bounds__(NTH, 2) void dec_persist_fwd(DecPersistFwd a) {
                     const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
                     if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
                 }
+                mi = argmax_in_row(mi);
                 float sacc = 0.f;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) if (lane + 64 * k < VV) sacc += expf(v[k] - m);

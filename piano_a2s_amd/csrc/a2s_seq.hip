@@ -389,13 +389,14 @@ __global__ __launch_bounds__(256) void note_step_finalize(StepFinArgs a) {
     if (t >= a.max_t) return;                                   // a replayed chunk may overshoot the step budget
     const float* lg = a.logits + (long)row * a.ldl;
     const bool finished = a.row_until && t >= a.row_until[row];    // its bar's loop has ended in the reference (outputs stay zero) or only <pad> targets remain
-    float m = -INFINITY; int mi = 0x7fffffff;
+    float m = -INFINITY; int mi = A2S_ARGMAX_NONE;
     for (int j = lane; j < a.V; j += 64) { const float x = lg[j]; if (x > m) { m = x; mi = j; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
         if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
     }
+    mi = argmax_in_row(mi);
     if (!finished) {
         float s = 0.f;
         for (int j = lane; j < a.V; j += 64) s += expf(lg[j] - m);
@@ -435,13 +436,14 @@ __global__ __launch_bounds__(256) void log_softmax_rows(const float* __restrict_
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= R) return;
     const float* lg = x + (long)row * ldx;
-    float m = -INFINITY; int mi = 0x7fffffff;
+    float m = -INFINITY; int mi = A2S_ARGMAX_NONE;
     for (int j = lane; j < V; j += 64) { const float v = lg[j]; if (v > m) { m = v; mi = j; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
         if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
     }
+    mi = argmax_in_row(mi);
     float s = 0.f;
     for (int j = lane; j < V; j += 64) s += expf(lg[j] - m);
     s = wave_sum(s);

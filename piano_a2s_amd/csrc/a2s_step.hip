@@ -509,7 +509,7 @@ __device__ __forceinline__ void dec_row_epilogue(const DecOutArgs& a, int vrow, 
     const int row = dec_row(a.rowmap, vrow);
     const bool finished = a.row_until && t >= a.row_until[row];    // its bar's loop has ended in the reference or only <pad> targets remain
     float v[3];
-    float m = -INFINITY; int mi = 0x7fffffff;
+    float m = -INFINITY; int mi = A2S_ARGMAX_NONE;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int j = lane + 64 * k;
@@ -521,6 +521,7 @@ __device__ __forceinline__ void dec_row_epilogue(const DecOutArgs& a, int vrow, 
         const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
         if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
     }
+    mi = argmax_in_row(mi);
     if (!finished) {
         float s = 0.f;
 #pragma unroll

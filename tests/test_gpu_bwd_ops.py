@@ -1,5 +1,8 @@
 """Per-kernel parity of the backward kernels on the MI355X against torch.autograd (CPU, fp32) of the oracle's
-primitives.  NB raw pointers do not keep tensors alive: every device operand is bound to a local name."""
+primitives.  NB raw pointers do not keep tensors alive: every device operand is bound to a local name.
+Tested in test_gpu_row_ops.py instead: a2s_ew_act_bwd, the 32-bit-id and const_id forms of a2s_embed_scatter_add, and the two halves of the
+synchronised BatchNorm backward (a2s_bn_bwd_stats + a2s_bn_bwd_apply, a2s_bn_bwd_sums_from_partial + a2s_bn_bwd_c12_from_sums) with two
+emulated ranks."""
 import ctypes as C
 
 import pytest

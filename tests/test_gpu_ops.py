@@ -1,6 +1,9 @@
-"""Per-kernel parity on the MI355X: every C-ABI entry point of liba2s_hip.so against the same operation in
-plain fp32 PyTorch on the CPU (oracle primitives where they exist).  Tolerances are fp32 round-off scaled by
-the reduction length; each is stated at the assertion."""
+"""Per-kernel parity on the MI355X: the GEMM, convolution, BatchNorm-statistics, GRU-sequence, attention-step and staff-embedding entry
+points of liba2s_hip.so against the same operation in plain fp32 PyTorch on the CPU (oracle primitives where they exist).
+Tolerances are fp32 round-off scaled by the reduction length; each is stated at the assertion.
+The remaining entry points are tested elsewhere: the backward kernels in test_gpu_bwd_ops.py; the row, loss and optimizer kernels
+(a2s_log_softmax_rows, a2s_embed_rows, a2s_nll_loss / a2s_nll_grad, a2s_clip_adadelta, a2s_bn_relu_apply, a2s_bn1d_relu_dropout) against
+float64 in test_gpu_row_ops.py."""
 import ctypes as C
 
 import numpy as np
