@@ -496,6 +496,42 @@ int a2s_resample_rows(void* stream, const float* x, long x_bstride, const int* n
                       float* y, long y_bstride, int n_out_max, int B);
 int a2s_resample_tile_samples(void);
 int a2s_resample_launches(void);
+
+/* ---- beat and downbeat tracking on the model's own features (csrc/a2s_beat.hip): the three device stages between the VQT and
+ * the host's decision stages (piano_a2s_amd/beats.py).  Every entry point takes borrowed device pointers and a stream; it allocates nothing, does not
+ * synchronise and reads nothing back.  One launch per call each; a2s_beat_launches: launches of the three so far.
+ * a2s_onset_strength: x = B clips of `rows` rows of F float32 (dB / 80 + 1), row t of clip b at x + b * x_bstride + t * x_rstride; n_rows (B,) int32,
+ * clamped to [0, rows] on the device.  env_full, env_low: row b at + b * env_bstride, `rows` floats each:
+ *     env_full[b][t] = sum_{f < F} max(0, x[b][t][f] - x[b][t - lag][f])   for lag <= t < n_rows[b],   0 elsewhere in [0, rows);
+ *     env_low[b][t]  = the same sum over f < f_split.
+ * Plain fp32 sums, no division: inputs on a grid of 1/8 give exact results.  Nothing at or behind row n_rows[b] is read (it may hold NaN).  A clip's
+ * bits depend on (F, lag, f_split, the alignment class below) and its own rows alone, not on B, on its place in the batch or on n_rows.  16-byte
+ * loads where F % 4 == 0, x is 16-byte aligned and both strides are multiples of 4, 4-byte loads otherwise; 16-byte stores where env_full and env_low
+ * are 16-byte aligned and env_bstride is a multiple of 4.  Every element is loaded once, but for the `lag` rows in front of each run of 64 rows, which
+ * the workgroup of that run loads again.  Null pointers, B < 0 or > 65535, rows < 1, F < 1, lag < 1, lag * F above 12288, f_split outside 0 .. F,
+ * x_rstride < F, x_bstride < (rows - 1) * x_rstride + F, env_bstride < rows: A2S_ERR_ARG, nothing is launched; B = 0 returns 0 and launches nothing.
+ * a2s_tempogram: env = R recordings, recording r at env + r * stride, n (R,) int32 frames each (clamped to [0, stride]); out (R, J, lag_max - lag_min + 1).
+ * Block j is centred at frame j * hop_b: its window holds the frames g = j * hop_b - win / 2 + u, u in [0, win);
+ *     d[u] = env[g] - (mean of env over the window's frames inside [0, n[r])) for g inside [0, n[r]), 0 outside;
+ *     out[r][j][l - lag_min] = sum_{u = 0}^{win - 1 - l} d[u] d[u + l] / sum_u d[u]^2,   0 where the denominator is 0.
+ * fp32 FMAs.  Null pointers, R < 0 or > 65535, stride < 1, J < 1, win < 1 or > 8192, hop_b < 1, lag_min < 0, lag_min > lag_max, more than 4096 lags:
+ * A2S_ERR_ARG, nothing is launched; R = 0 returns 0 and launches nothing.
+ * a2s_beat_dp: ls = R rows of `stride` floats (the envelope over its standard deviation), n (R,) int32 (clamped to [0, stride]), period (R, J) int32,
+ * pen = (lag_max - lag_min + 1) rows of 2 * lag_max + 1 floats, pen[tau - lag_min][d] the price of a beat interval of d frames at the period tau.
+ * For t = 0 .. n - 1, tau = clamp(period[r][min(t / hop_b, J - 1)], lag_min, lag_max), over the candidates p in [max(0, t - 2 tau), t - ceil(tau / 2)]:
+ *     c(p) = S[p] - pen[tau - lag_min][t - p];   S[t] = ls[t] + max(0, max_p c(p));   back[t] = the arg max, the one nearest to t among equals, -1
+ *     where no candidate is above 0.
+ * One fp32 subtraction and one fp32 addition per value, no multiply: a float32 restatement gives the same bits.  The last beat is the first arg max
+ * of S over the last tau(n - 1) frames; beats[r * max_beats + k] receives the beats, ascending, as many as fit, count[r] their true number (0 for
+ * n = 0); entries of beats at and behind count[r] are not written.  S, back: R rows of `stride`, written at [0, n).  Null pointers, R < 0 or > 65535,
+ * stride < 1, J < 1, hop_b < 1, lag_min < 1, lag_min > lag_max, lag_max > 4096, max_beats < 1: A2S_ERR_ARG, nothing is launched; R = 0 returns 0 and
+ * launches nothing. */
+int a2s_onset_strength(void* stream, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F, int lag, int f_split,
+                       float* env_full, float* env_low, long env_bstride);
+int a2s_tempogram(void* stream, const float* env, long stride, const int* n, int R, int J, int win, int hop_b, int lag_min, int lag_max, float* out);
+int a2s_beat_dp(void* stream, const float* ls, long stride, const int* period, int J, int hop_b, const float* pen, int lag_min, int lag_max, const int* n,
+                int R, float* S, int* back, int* beats, int max_beats, int* count);
+int a2s_beat_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -297,6 +297,19 @@ int a2s_resample_rows(void* stream, const float* x, long x_bstride, const int* n
 }
 int a2s_resample_tile_samples(void) { return a2s_resample_tile_samples_impl(); }
 int a2s_resample_launches(void) { return a2s_resample_launches_impl(); }
+
+int a2s_onset_strength(void* stream, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F, int lag, int f_split,
+                       float* env_full, float* env_low, long env_bstride) {
+    return a2s_onset_strength_impl(ST, x, x_bstride, x_rstride, n_rows, B, rows, F, lag, f_split, env_full, env_low, env_bstride);
+}
+int a2s_tempogram(void* stream, const float* env, long stride, const int* n, int R, int J, int win, int hop_b, int lag_min, int lag_max, float* out) {
+    return a2s_tempogram_impl(ST, env, stride, n, R, J, win, hop_b, lag_min, lag_max, out);
+}
+int a2s_beat_dp(void* stream, const float* ls, long stride, const int* period, int J, int hop_b, const float* pen, int lag_min, int lag_max, const int* n,
+                int R, float* S, int* back, int* beats, int max_beats, int* count) {
+    return a2s_beat_dp_impl(ST, ls, stride, period, J, hop_b, pen, lag_min, lag_max, n, R, S, back, beats, max_beats, count);
+}
+int a2s_beat_launches(void) { return a2s_beat_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

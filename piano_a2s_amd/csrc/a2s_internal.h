@@ -319,6 +319,14 @@ int a2s_resample_rows_impl(hipStream_t st, const float* x, long x_bstride, const
 int a2s_resample_tile_samples_impl(void);
 int a2s_resample_launches_impl(void);
 
+// ---- a2s_beat.hip
+int a2s_onset_strength_impl(hipStream_t st, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F, int lag, int f_split,
+                            float* env_full, float* env_low, long env_bstride);
+int a2s_tempogram_impl(hipStream_t st, const float* env, long stride, const int* n, int R, int J, int win, int hop_b, int lag_min, int lag_max, float* out);
+int a2s_beat_dp_impl(hipStream_t st, const float* ls, long stride, const int* period, int J, int hop_b, const float* pen, int lag_min, int lag_max,
+                     const int* n, int R, float* S, int* back, int* beats, int max_beats, int* count);
+int a2s_beat_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

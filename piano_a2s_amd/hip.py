@@ -591,6 +591,128 @@ def resample_launches():
     return int(lib().a2s_resample_launches())
 
 
+def _whole(fn, **values):
+    """The named arguments as Python ints; a value that is no whole number is an error that names it."""
+    out = []
+    for name, v in values.items():
+        try:
+            i = int(v)
+        except (TypeError, ValueError):
+            i = None
+        _need(i is not None and i == v, fn, name, f"must be a whole number (got {v!r})")
+        out.append(i)
+    return out
+
+
+def _int_rows(fn, name, t, shape, device):
+    _need(torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == device, fn, name,
+          f"must be a contiguous int32 tensor of shape {tuple(shape)} on the device of the first argument")
+
+
+def onset_strength(x, n_rows, lag=1, f_split=180, env_full=None, env_low=None):
+    """a2s_onset_strength: x (B, rows, F) or (B, 1, rows, F) float32 on the device, unit stride along F (the rows and the clips may be strided), n_rows
+    (B,) int32 -> (env_full, env_low), (B, rows) float32 each (fresh tensors when not given; given ones are 2-D with unit column stride):
+    env_full[b][t] = sum_f max(0, x[b][t][f] - x[b][t - lag][f]) for lag <= t < n_rows[b], 0 elsewhere; env_low the same over f < f_split."""
+    fn = "onset_strength"
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and (x.dim() == 3 or (x.dim() == 4 and x.shape[1] == 1)), fn, "x",
+          "must be a float32 tensor (B, rows, F) or (B, 1, rows, F) on the device")
+    if x.dim() == 4:
+        x = x[:, 0]
+    B, rows, F = x.shape
+    lag, f_split = _whole(fn, lag=lag, f_split=f_split)
+    _need(lag >= 1, fn, "lag", f"must be >= 1 (got {lag})")
+    _need(0 <= f_split <= F, fn, "f_split", f"must be in 0 .. F = {F} (got {f_split})")
+    _int_rows(fn, "n_rows", n_rows, (B,), x.device)
+    outs = []
+    for name, t in (("env_full", env_full), ("env_low", env_low)):
+        if t is None:
+            t = torch.empty((B, rows), dtype=torch.float32, device=x.device)
+        outs.append(t)
+    if B == 0 or rows == 0 or F == 0:
+        _need(B == 0 or F > 0 or rows == 0, fn, "x", "has rows but no columns")
+        return tuple(outs)
+    _need(x.stride(2) == 1 or F == 1, fn, "x", "must have unit stride along F")
+    xr = x.stride(1) if rows > 1 else max(x.stride(1), F)
+    xb = x.stride(0) if B > 1 else max(x.stride(0), (rows - 1) * xr + F)
+    _need(xr >= F and xb >= (rows - 1) * xr + F, fn, "x", f"has overlapping rows or clips (strides {tuple(x.stride())})")
+    es = _rows(fn, "env_full", outs[0], B, rows, x.device)
+    _need(_rows(fn, "env_low", outs[1], B, rows, x.device) == es, fn, "env_low", "must have env_full's row stride")
+    _need(lag * (-(-F // 4) * 4) <= 12288, fn, "lag", f"times F = {F} exceeds the 12288 floats a workgroup keeps (got {lag})")
+    check(lib().a2s_onset_strength(stream(), _p(x), xb, xr, _p(n_rows), B, rows, F, lag, f_split, _p(outs[0]), _p(outs[1]), es), "a2s_onset_strength")
+    return tuple(outs)
+
+
+def tempogram(env, n, win=800, hop_b=100, lag_min=20, lag_max=200, J=None, out=None):
+    """a2s_tempogram: env (R, stride) float32 on the device (unit column stride), n (R,) int32 frames per recording -> out (R, J, lag_max - lag_min + 1)
+    float32, contiguous (a fresh tensor when not given): the normalised autocorrelation of the mean-free window of `win` frames centred at frame
+    j * hop_b, at the lags lag_min .. lag_max.  J defaults to max(1, ceil(stride / hop_b))."""
+    fn = "tempogram"
+    _need(torch.is_tensor(env) and env.dtype == torch.float32 and env.dim() == 2 and env.is_cuda, fn, "env", "must be a 2-D float32 tensor on the device")
+    R, width = env.shape
+    win, hop_b, lag_min, lag_max = _whole(fn, win=win, hop_b=hop_b, lag_min=lag_min, lag_max=lag_max)
+    _need(1 <= win <= 8192, fn, "win", f"must be in 1 .. 8192 (got {win})")
+    _need(hop_b >= 1, fn, "hop_b", f"must be >= 1 (got {hop_b})")
+    _need(0 <= lag_min <= lag_max and lag_max - lag_min < 4096, fn, "lag_min", f"and lag_max must satisfy 0 <= lag_min <= lag_max, at most 4096 lags (got {lag_min}, {lag_max})")
+    J = max(1, -(-width // hop_b)) if J is None else _whole(fn, J=J)[0]
+    _need(J >= 1, fn, "J", f"must be >= 1 (got {J})")
+    _int_rows(fn, "n", n, (R,), env.device)
+    nl = lag_max - lag_min + 1
+    if out is None:
+        out = torch.empty((R, J, nl), dtype=torch.float32, device=env.device)
+    _need(torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (R, J, nl) and out.is_contiguous() and out.device == env.device, fn, "out",
+          f"must be a contiguous float32 tensor of shape {(R, J, nl)} on env's device")
+    if R == 0:
+        return out
+    _need(width >= 1, fn, "env", "has no columns")
+    stride = _rows(fn, "env", env, R, width, env.device)
+    check(lib().a2s_tempogram(stream(), _p(env), stride, _p(n), R, J, win, hop_b, lag_min, lag_max, _p(out)), "a2s_tempogram")
+    return out
+
+
+def beat_dp(ls, period, pen, n, hop_b=100, lag_min=20, max_beats=None, S=None, back=None, beats=None, count=None):
+    """a2s_beat_dp: ls (R, stride) float32 (the envelope over its standard deviation), period (R, J) int32, pen (lag_max - lag_min + 1, 2 lag_max + 1)
+    float32 (beats.penalty_table), n (R,) int32, all on the device -> (S (R, stride) float32, back (R, stride) int32, beats (R, max_beats) int32,
+    count (R,) int32), fresh tensors where not given (S and back zero-filled, beats filled with -1: the kernel writes [0, n) and the first
+    min(count, max_beats) beats only).  count is the true number of beats also where it exceeds max_beats (default stride // ceil(lag_min / 2) + 1,
+    which it cannot exceed)."""
+    fn = "beat_dp"
+    _need(torch.is_tensor(ls) and ls.dtype == torch.float32 and ls.dim() == 2 and ls.is_contiguous() and ls.is_cuda, fn, "ls",
+          "must be a contiguous 2-D float32 tensor on the device")
+    R, stride = ls.shape
+    hop_b, lag_min = _whole(fn, hop_b=hop_b, lag_min=lag_min)
+    _need(hop_b >= 1, fn, "hop_b", f"must be >= 1 (got {hop_b})")
+    _need(torch.is_tensor(pen) and pen.dtype == torch.float32 and pen.dim() == 2 and pen.is_contiguous() and pen.device == ls.device, fn, "pen",
+          "must be a contiguous 2-D float32 tensor on ls's device")
+    lag_max = (pen.shape[1] - 1) // 2
+    _need(lag_min >= 1 and pen.shape[1] == 2 * lag_max + 1 and pen.shape[0] == lag_max - lag_min + 1 and lag_max <= 4096, fn, "pen",
+          f"must have lag_max - lag_min + 1 rows of 2 lag_max + 1 columns, 1 <= lag_min <= lag_max <= 4096 (got {tuple(pen.shape)} for lag_min = {lag_min})")
+    _need(torch.is_tensor(period) and period.dim() == 2 and period.shape[1] >= 1, fn, "period", "must be a 2-D int32 tensor (R, J), J >= 1")
+    _int_rows(fn, "period", period, (R, period.shape[1]), ls.device)
+    _int_rows(fn, "n", n, (R,), ls.device)
+    max_beats = stride // ((lag_min + 1) // 2) + 1 if max_beats is None else _whole(fn, max_beats=max_beats)[0]
+    _need(max_beats >= 1, fn, "max_beats", f"must be >= 1 (got {max_beats})")
+    S = torch.zeros((R, stride), dtype=torch.float32, device=ls.device) if S is None else S
+    back = torch.zeros((R, stride), dtype=torch.int32, device=ls.device) if back is None else back
+    beats = torch.full((R, max_beats), -1, dtype=torch.int32, device=ls.device) if beats is None else beats
+    count = torch.zeros((R,), dtype=torch.int32, device=ls.device) if count is None else count
+    _need(torch.is_tensor(S) and S.dtype == torch.float32 and tuple(S.shape) == (R, stride) and S.is_contiguous() and S.device == ls.device, fn, "S",
+          f"must be a contiguous float32 tensor of shape {(R, stride)} on ls's device")
+    _int_rows(fn, "back", back, (R, stride), ls.device)
+    _int_rows(fn, "beats", beats, (R, max_beats), ls.device)
+    _int_rows(fn, "count", count, (R,), ls.device)
+    if R == 0:
+        return S, back, beats, count
+    _need(stride >= 1, fn, "ls", "has no columns")
+    check(lib().a2s_beat_dp(stream(), _p(ls), stride, _p(period), period.shape[1], hop_b, _p(pen), lag_min, lag_max, _p(n), R, _p(S), _p(back), _p(beats),
+                            max_beats, _p(count)), "a2s_beat_dp")
+    return S, back, beats, count
+
+
+def beat_launches():
+    """Launches of the three beat-tracking kernels in this process (a2s_beat_launches)."""
+    return int(lib().a2s_beat_launches())
+
+
 def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):
     """a2s_note_match: the note counts of n_pairs pairs of bar rows, one launch on the current stream.  ref / hyp (int32 ids) and ref_off / hyp_off
     (int64, n_pairs + 1 each) are device tensors or device addresses (ints: parts of one packed buffer, metrics.device_note_counts); dur_ticks, midi, cls

@@ -52,15 +52,29 @@ def to_16k(x, sr, device, hparams):
     return y[0], rate
 
 
-def transcribe_waveform(model, x, sr, *, downbeats=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams):
+def check_downbeats(downbeats, beats_per_bar):
+    """What transcribe_waveform takes as `downbeats`: None, times in seconds, or the word "track"; beats_per_bar (2, 3 or 4) only with "track"."""
+    if isinstance(downbeats, str) and downbeats != "track":
+        raise ValueError(f'transcribe: downbeats must be None, a list of times in seconds or "track" (got {downbeats!r})')
+    tracking = isinstance(downbeats, str)
+    if beats_per_bar is not None and not tracking:
+        raise ValueError('transcribe: beats_per_bar belongs to downbeats="track"')
+    if beats_per_bar is not None and beats_per_bar not in (2, 3, 4):
+        raise ValueError(f"transcribe: beats_per_bar must be 2, 3 or 4 (got {beats_per_bar!r})")
+
+
+def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
     Windows: audio.plan_windows -- with `downbeats` (seconds) groups of max_bars bars as in the reference's test protocol, without them fixed windows
-    every hop_seconds (the model was trained on bar-aligned clips: expect less of the second).
+    every hop_seconds (the model was trained on bar-aligned clips: expect less of the second).  downbeats="track": the downbeats are tracked on the
+    recording's own features (piano_a2s_amd.beats; beats_per_bar 2, 3 or 4 fixes the meter) and then used as if they had been
+    given; the result gains "tracking": {"beats_s", "downbeats_s", "beats_per_bar", "period_frames"}.
     -> {"sample_rate_in", "sample_rate", "frames_per_second", "windows": [{"start_s", "stop_s", "n_bars", "flags", "time_signature", "key",
         "bars": [{"upper", "lower", "upper_ids", "lower_ids"}], ["alignment"]}]};  time_signature and key hold one entry per kept bar (key as in the
         recipe's result files: class - 6), bars the first n_bars decoded bars."""
+    check_downbeats(downbeats, beats_per_bar)
     core = getattr(model, "module", model)
     device = next(core.parameters()).device
     hop = int(_hp(hparams, "hop_length", 160))
@@ -68,8 +82,15 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, window_seconds=12.0, ho
     length = (int(_hp(hparams, "max_frame_num", 1201)) - 1) * hop
     wave, rate = to_16k(x, sr, device, hparams)
     fps = rate / hop
+    tracking = None
+    if isinstance(downbeats, str):
+        from . import beats
+        tracking = beats.track_recording(wave, hparams, beats_per_bar=beats_per_bar)
+        downbeats = tracking["downbeats_s"]
     plan = audio._plan(wave.shape[0], rate, downbeats, window_seconds, hop_seconds, max_bars, length)
     result = {"sample_rate_in": int(sr), "sample_rate": rate, "frames_per_second": fps, "windows": []}
+    if tracking is not None:
+        result["tracking"] = tracking
     if not plan:
         return result
     feats = _vqt(device, hparams)(audio.cut_windows(wave, plan, length))
@@ -150,8 +171,9 @@ def load_model(hparams_file, checkpoint, device, overrides=None):
 
 HELP = """Transcribe WAV recordings (any sample rate, any number of channels) into kern bars, one JSON file per recording.
 
-With --downbeats the recording is cut into groups of max_bars bars, the reference's test protocol.  Without it the tool works on fixed windows, but the
-model was trained on bar-aligned clips: expect less.  The output holds the decoded bars of every window per staff; a joined two-staff Humdrum file is out
+With --downbeats the recording is cut into groups of max_bars bars, the reference's test protocol.  With --track_downbeats the tool finds the downbeats
+itself, on the recording's own features (metres of 2, 3 and 4 beats; --beats_per_bar fixes the metre), and cuts at them in the same way.  With neither the
+tool works on fixed windows, but the model was trained on bar-aligned clips: expect less.  The output holds the decoded bars of every window per staff; a joined two-staff Humdrum file is out
 of scope (it needs spine-split bookkeeping across bars, which the reference leaves to humextra)."""
 
 
@@ -161,7 +183,10 @@ def main(argv):
     ap.add_argument("hparams", help="hparams yaml (hparams/finetune.yaml): the model is its `transcription` key")
     ap.add_argument("audio", nargs="+", help="WAV files: PCM 8/16/24/32 bits, IEEE float 32/64 bits, extensible headers")
     ap.add_argument("--checkpoint", required=True, help="a state_dict file, or a checkpoint directory holding transcription.ckpt")
-    ap.add_argument("--downbeats", help="one downbeat time (s) per line, first column; with a third column only lines whose third column starts with `db`")
+    where = ap.add_mutually_exclusive_group()
+    where.add_argument("--downbeats", help="one downbeat time (s) per line, first column; with a third column only lines whose third column starts with `db`")
+    where.add_argument("--track_downbeats", action="store_true", help="track beats and downbeats on the recording itself and cut at the tracked downbeats")
+    ap.add_argument("--beats_per_bar", type=int, choices=(2, 3, 4), default=None, help="with --track_downbeats: the metre, instead of the tracker's choice")
     ap.add_argument("--out", default=".", help="output folder: DIR/NAME.json per recording")
     ap.add_argument("--window_seconds", type=float, default=12.0)
     ap.add_argument("--hop_seconds", type=float, default=None)
@@ -182,15 +207,17 @@ def main(argv):
         ap.error(f"--beam_size must be in 1 .. 4 (got {a.beam_size})")
     if len(a.audio) > 1 and a.downbeats:
         ap.error("--downbeats belongs to one recording")
+    if a.beats_per_bar is not None and not a.track_downbeats:
+        ap.error("--beats_per_bar belongs to --track_downbeats")
     model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
     model.constrained_decoding, model.alignment = bool(a.constrained_decoding), bool(a.alignment)
     model.beam_size, model.beam_length_penalty = a.beam_size, a.beam_length_penalty
-    downbeats = read_downbeats(a.downbeats) if a.downbeats else None
+    downbeats = read_downbeats(a.downbeats) if a.downbeats else ("track" if a.track_downbeats else None)
     os.makedirs(a.out, exist_ok=True)
     for path in a.audio:
         x, sr = audio.read_wav(path)
-        result = transcribe_waveform(model, x, sr, downbeats=downbeats, window_seconds=a.window_seconds, hop_seconds=a.hop_seconds,
-                                     batch_size=a.batch_size, hparams=hp)
+        result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
+                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
         with open(out, "w") as f:
