@@ -206,7 +206,15 @@ int a2s_gru_seq_fwd(void* stream, const float* gi_all, long gi_bstride, long gi_
  * score_t = v . tanh(K[b,t,:] + q[b,:]); a = softmax_t; ctx = sum_t a_t enc[b,t,:].
  * `keys` of every attention entry point is the KEY IMAGE exp(2 K) (a2s_gemm_f32 with act 3 on K = enc W_e^T; |K| clamped to 43), not K:
  * tanh(k + q) = 1 - 2 / (1 + exp(2k) exp(2q)) then costs one transcendental per (frame, unit).  q is passed as is; the gradient
- * a2s_attn_dk_accum returns is the one with respect to K. */
+ * a2s_attn_dk_accum returns is the one with respect to K.
+ * DOMAIN.  The image clamps k to +-43 and every kernel clamps q to +-43, each without looking at the other, so the energies are those of
+ * tanh(k + q) -- to within 3.05e-8 = 1 - tanh(9) -- only on
+ *     D = (|k| <= 43 and |q| <= 43)  or  min(|k|, |q|) <= 34.
+ * Outside D the result is finite, looks like any other and is wrong by up to 1.0 (k = 50, q = -45 gives 0 where tanh(5) = 0.9999); the
+ * gradients likewise.  No entry point checks this: a caller whose attention Linear is unconstrained (a trained checkpoint) must.  The host
+ * side does, for every pass that decodes in eval mode: piano_a2s_amd/attn_range.py reads max |k| back from the image (0.5 max |ln image|,
+ * which saturates at 43: "43 or more"), bounds |q| by max_j (sum |W_h[j, :]| + |b_j|) (the states are GRU states in (-1, 1)) and raises
+ * A2SError outside D.  Inside D an image entry is within 2^-23 + |k| 2^-22 relative of exp(2k). */
 int a2s_attn_step_fwd(void* stream, const float* keys, const float* enc, const float* q, long ldq, const float* v,
                       float* ctx, long ldctx, float* ctx2, long ldctx2, float* attw, int B, int T, int H,
                       const int* n_done, int n_rows_total, float* workspace);

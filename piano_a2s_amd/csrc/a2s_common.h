@@ -216,6 +216,13 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // act 3) and E_q = exp(2 q) (once per row and step):  tanh(k + q) = 1 - 2 / (1 + E_K E_q)  is 3 instructions with ONE transcendental
 // per (frame, unit) instead of 8 with two -- the attention kernels that serve several rows per clip are bound by exactly this.
 // The clamp keeps both factors finite and normal (|x| <= 43: e^86 < FLT_MAX); a product that overflows gives rcp(inf) = 0 -> tanh = 1.
+// Each factor is clamped WITHOUT looking at the other one, so what these three functions evaluate is tanh(k~ + q~) of the clamped values.  That is
+// tanh(k + q) to within 1 - tanh(9) = 3.05e-8 on the domain
+//     D = (|k| <= 43 and |q| <= 43)  or  min(|k|, |q|) <= 34        (34 = 43 - 9: a clamped side still leaves |k~ + q~| >= 9 with the sign of k + q)
+// and SILENTLY WRONG outside it, by up to 1.0: k = 50, q = -45 gives tanh(43 - 43) = 0 where tanh(5) = 0.9999.  The same split holds for sech2_ek.
+// The kernels do not check this; the host does for every pass that decodes in eval mode (piano_a2s_amd/attn_range.py, Engine._attn_range_check).
+// Accuracy inside D (tests/attn_range_oracle.py, measured by tests/test_gpu_attn_range.py): the image entry's relative error is at most
+// 2^-23 + |x| 2^-22 (1.0e-5 at |x| = 43), so an unsaturated energy formed from two large opposite-signed arguments is off by up to 1.0e-5.
 __device__ __forceinline__ float exp2x_clamped(float x) { return __expf(2.f * fminf(fmaxf(x, -43.f), 43.f)); }
 __device__ __forceinline__ float tanh_ek(float ek, float eq) { return fmaf(-2.f, __builtin_amdgcn_rcpf(fmaf(ek, eq, 1.f)), 1.f); }
 __device__ __forceinline__ float sech2_ek(float ek, float eq) {      // 1 - tanh^2(k + q) = 4 r (1 - r), r = 1 / (1 + E_K E_q)

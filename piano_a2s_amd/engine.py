@@ -12,7 +12,7 @@ import threading
 
 import torch
 
-from . import decode_plan, hip
+from . import attn_range, decode_plan, hip
 from .decode_plan import draw_plan, plan_note_steps, plan_segments
 from .spec import EOS, PAD, SOS, VOCAB_SIZE
 
@@ -314,6 +314,10 @@ class Engine:
         # shape (B, bars) for "bar" and (B, bars, max_length) for the staves; where no step ran: peak -1, weight 0, centroid -1
         self.alignment = False
         self.alignment_out = None
+        # the pending range readings of an eval forward (attn_range.py): (layer names, device tensor [max |k| per layer | bound on |q| per layer]), read by
+        # the first decoder call that synchronises; after the forward `attn_ranges` = {layer: (max |k|, bound on |q|)} of the last eval pass
+        self._attn_range_pending = None
+        self.attn_ranges = None
         # Synchronised BatchNorm (what SpeechBrain's DDP wrapping gives the reference): batch statistics over the
         # GLOBAL minibatch -- per-channel (sum, sum of squares, count) are all-reduced between the ranks.  Off by default:
         # per-rank statistics (plain DDP semantics).  Needs an initialised process group.
@@ -471,6 +475,25 @@ class Engine:
                  two_term=(hip.one(enc2d.device), hip.absmax(W)) if _ENC_TWO_TERM else None)
         return K
 
+    _ATTN_LAYERS = ("decoder.attn", "decoder.upper_decoder.attn", "decoder.lower_decoder.attn")
+
+    def _attn_range_enqueue(self, S, keys, H):
+        """Eval passes only: the largest |k| each key image holds and the bound on |q| of each attention Linear, enqueued behind _keys as one small device
+        tensor.  Nothing is read here: _attn_range_check does that where the decoder synchronises anyway."""
+        ks = [attn_range.key_range(keys[p[:-len(".attn")]]) for p in self._ATTN_LAYERS]          # (forward keeps the images under the decoders' names)
+        qs = [attn_range.query_bound(S[p + ".attn.weight"], S[p + ".attn.bias"], H) for p in self._ATTN_LAYERS]
+        self._attn_range_pending = torch.stack(ks + qs)
+
+    def _attn_range_check(self):
+        """Called right after a read-back the decoder makes anyway (steps_exec.item(): the stream is drained, the readings are there): outside the
+        domain of the key-image attention the forward must not return numbers (attn_range.on_violation: raise, or warn once)."""
+        pending, self._attn_range_pending = self._attn_range_pending, None
+        if pending is None:
+            return
+        r, n = pending.tolist(), len(self._ATTN_LAYERS)
+        self.attn_ranges = {p: (r[i], r[n + i]) for i, p in enumerate(self._ATTN_LAYERS)}
+        attn_range.report(attn_range.violations(self._ATTN_LAYERS, r[:n], r[n:]), hip.A2SError)
+
     def _staff_token(self, S, ids, lengths, len_stride, out, col0, maxlen, id_bstride, ids_are_i64, record=None):
         """record: list that receives what the backward pass needs to replay this call (training only)."""
         L = hip.lib()
@@ -583,6 +606,8 @@ class Engine:
             # steps the reference would have executed: known from the plan with ground truth; read back from the device
             # in greedy mode (launched steps can overshoot the early break by < poll; those were no-ops)
             executed = n if gt_bar is not None else int(steps_exec.item())
+            if gt_bar is None:
+                self._attn_range_check()
             if gt_bar is None and a.persist_ws:
                 hip.check_persist_abort(dev, raise_error=True)       # (the host has just synchronised: a persistent launch that gave up returns unusable ids)
             saved = dict(h=h, x=x, q=q, o=o, gates=gates, attw=attw, drop=drop, steps=executed, launched=launched, ids=ids, flags=list(flags),
@@ -659,6 +684,7 @@ class Engine:
         done = C.c_int(0)
         hip.check(L.a2s_note_decoder_fwd_beam(hip.stream(), C.byref(a), C.byref(g), C.byref(done)), "a2s_note_decoder_fwd_beam")
         executed = int(steps_exec.item())
+        self._attn_range_check()
         saved = dict(h=h, x=x, q=q, o=o, gates=None, attw=None, drop=None, steps=executed, launched=done.value, ids=bt["ids_out"], gt_bar=None, prefix=prefix,
                      max_steps=max_steps, attn_ws=attn_ws, gemm_ws=gemm_ws, step_ws=step_ws, logits=logits, gh=gh, gi=gi, n_done=n_done, beam=bt, beam_size=K,
                      row_state=bt["row_state"])
@@ -807,6 +833,9 @@ class Engine:
         enc2d = enc.view(B * T, 2 * H)
         keys = {p: self._keys(S, p + ".attn", enc2d, H) for p in ("decoder", "decoder.upper_decoder", "decoder.lower_decoder")}
         enc_hidden = hidden
+        self._attn_range_pending = None
+        if not training:
+            self._attn_range_enqueue(S, keys, H)
 
         def decode_group(gidx, b0, b1, gen):
             """The decoder (reference HierarchicalDecoder.decode_bars, models.py:191-316) over the clips [b0, b1).  Runs on the calling
@@ -1063,6 +1092,8 @@ class Engine:
                 gens.append(g_)
             _trace("generators made")
             group_saved = run_clip_groups(dev, [lambda gi=gi, r=r: decode_group(gi, r[0], r[1], gens[gi]) for gi, r in enumerate(clip_groups)])
+        # (an eval pass whose decoder calls were all teacher-forced has read nothing back: its readings are taken here, the pass's one read)
+        self._attn_range_check()
         self.decoded = None
         if constrained:
             # the EMITTED ids and the lengths of every bar (the log-probabilities stay the unconstrained ones: their argmax is not what was decoded)
