@@ -714,14 +714,17 @@ int a2s_clip_adadelta(void* stream, float* params, float* grads, float* square_a
 
 /* ---- VQT front-end epilogue (utilities.get_VQT, utilities.py:240-254): C (B, rows, 2*bins) = [re | im] of the framed complex GEMM
  * (run with a2s_gemm_f32, A row stride = hop) -> out (B, rows, bins) = dB relative to the clip maximum, floor 1e-5, top_db, /80 + 1.
- * partial: B*64 floats of scratch. */
+ * partial: B*64 floats of scratch.  Null pointers, B < 1, rows < 1 or bins < 1: A2S_ERR_ARG, nothing is launched. */
 int a2s_vqt_logmag(void* stream, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db);
 /* the same over a response laid out octave by octave: C (B, rows, n_oct * 2 * bins_per_octave), octave o (HIGHEST first) = [re | im] of its
- * bins_per_octave bins -- what one framed GEMM per octave against the (n_fft, 2 * bins_per_octave) bank writes */
+ * bins_per_octave bins -- what one framed GEMM per octave against the (n_fft, 2 * bins_per_octave) bank writes.  Null pointers, B < 1, rows < 1,
+ * bins < 1, bins_per_octave < 1 or bins no multiple of bins_per_octave: A2S_ERR_ARG, nothing is launched. */
 int a2s_vqt_logmag_octaves(void* stream, const float* C, float* out, float* partial, int B, long rows, int bins, int bins_per_octave, float top_db);
 /* decimation by 2 between the octaves of librosa.vqt's recursion (librosa.resample(y, orig_sr=2, target_sr=1, scale=True); the filter is this
- * build's stand-in for libsoxr, see piano_a2s_amd/vqt.py): out[b][m] = sum_j ypad[b][2 m + j] taps[j], ntaps even; ypad (B, padded_len) with
- * padded_len >= 2 n_out + ntaps (reads beyond are taken as zero), out (B, n_out). */
+ * build's stand-in for libsoxr, see piano_a2s_amd/vqt.py): out[b][m] = sum_j ypad[b][2 m + j] taps[j], ntaps even and <= 4096; ypad (B, padded_len),
+ * rows padded_len floats apart, with any padded_len >= 1: ypad[b][s] is taken as zero for every s >= padded_len (never read, so a short row does not
+ * reach into the next clip's), out (B, n_out).  Null pointers, B < 1, n_out < 1, padded_len < 1, ntaps < 2, odd or > 4096: A2S_ERR_ARG, nothing is
+ * launched. */
 int a2s_vqt_decimate(void* stream, const float* ypad, long padded_len, const float* taps, int ntaps, float* out, long n_out, int B);
 
 /* ---- scoring of the VALID / TEST stages (pretrain.py:216-249: jiwer.wer per clip on the host): unit-cost Levenshtein distance of n_pairs

@@ -42,6 +42,7 @@ __global__ void vqt_logmag(const float* __restrict__ C, const float* __restrict_
 
 int a2s_vqt_logmag_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, float top_db) {
     A2S_REQUIRE(C && out && partial, "vqt_logmag: null tensor");
+    A2S_REQUIRE(B >= 1 && rows >= 1 && bins >= 1, "vqt_logmag: B (%d), rows (%ld) and bins (%d) must be >= 1", B, rows, bins);
     const int bpc = 64;
     hipLaunchKernelGGL(vqt_mag_max, dim3(B * bpc), dim3(256), 0, st, C, partial, rows, bins, bpc);
     A2S_CHECK_LAUNCH("vqt_mag_max");
@@ -81,7 +82,8 @@ __global__ __launch_bounds__(256) void vqt_decimate(const float* __restrict__ yp
     for (int u = 0; u < 4; ++u) { const long m = m0 + threadIdx.x + 256 * u; if (m < n_out) out[(long)b * n_out + m] = acc[u]; }
 }
 int a2s_vqt_decimate_impl(hipStream_t st, const float* ypad, long plen, const float* taps, int ntaps, float* out, long n_out, int B) {
-    A2S_REQUIRE(ypad && taps && out && B > 0 && n_out > 0, "vqt_decimate: null tensor");
+    A2S_REQUIRE(ypad && taps && out, "vqt_decimate: null tensor");
+    A2S_REQUIRE(B > 0 && n_out > 0 && plen > 0, "vqt_decimate: B (%d), n_out (%ld) and padded_len (%ld) must be >= 1", B, n_out, plen);
     A2S_REQUIRE(ntaps > 0 && ntaps % 2 == 0 && ntaps <= 4096, "vqt_decimate: the tap count must be even (pad with a zero) and <= 4096, got %d", ntaps);
     const size_t shm = sizeof(float) * (2 * DEC_OUT_PER_WG + ntaps + 2);
     hipLaunchKernelGGL(vqt_decimate, dim3((unsigned)a2s_cdiv(n_out, DEC_OUT_PER_WG), B), dim3(256), shm, st, ypad, plen, taps, ntaps, out, n_out);
@@ -133,6 +135,7 @@ __global__ __launch_bounds__(256) void vqt_logmag_oct(const float* __restrict__ 
 }
 int a2s_vqt_logmag_octaves_impl(hipStream_t st, const float* C, float* out, float* partial, int B, long rows, int bins, int bpo, float top_db) {
     A2S_REQUIRE(C && out && partial, "vqt_logmag_octaves: null tensor");
+    A2S_REQUIRE(B >= 1 && rows >= 1 && bins >= 1, "vqt_logmag_octaves: B (%d), rows (%ld) and bins (%d) must be >= 1", B, rows, bins);
     A2S_REQUIRE(bpo > 0 && bins % bpo == 0, "vqt_logmag_octaves: bins (%d) must be a multiple of the bins per octave (%d)", bins, bpo);
     const int bpc = 64;
     hipLaunchKernelGGL(vqt_mag_max_oct, dim3(B * bpc), dim3(256), 0, st, C, partial, rows, bins, bpo, bpc);

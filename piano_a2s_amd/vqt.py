@@ -14,7 +14,7 @@ call on the GPU, as framed GEMMs on the matrix cores:
     row's magnitude, scaled by sqrt(sr/sr_o) and 1/sqrt(length at the full rate) -- and then transformed BACK to the time domain
     (response = sum_f basis[f] FFT(frame)[f] = frame . g with g[m] = sum_f basis[f] e^{-2 pi i f m / n_fft}), so that the sparsified
     basis, the dropped negative frequencies and the rectangular-window STFT of librosa are all inside one dense real x complex product;
-  * the decimator is a framed GEMM as well (row stride 2, one output column): a linear-phase Kaiser-windowed sinc with soxr-HQ's
+  * the decimator is a kernel of its own (a2s_vqt_decimate, csrc/a2s_vqt.hip): a linear-phase Kaiser-windowed sinc with soxr-HQ's
     documented band edges.  librosa decimates with libsoxr (res_type='soxr_hq'), a compiled resampler whose coefficients are not
     published: this is the one step that cannot follow librosa exactly, and why the front-end's parity stays **unpinned**;
   * log-magnitude epilogue (csrc/a2s_vqt.hip): dB relative to the clip maximum, floor 1e-5, top_db 80, /80 + 1.
@@ -57,6 +57,23 @@ def decimation_filter(passband=0.913, atten_db=120.0):
     n = np.arange(-half, half + 1)
     h = 2.0 * cutoff * np.sinc(2.0 * cutoff * n) * np.kaiser(2 * half + 1, 0.1102 * (atten_db - 8.7))
     return h / h.sum() * math.sqrt(2.0), half
+
+
+def decimator_taps(h):
+    """The taps a2s_vqt_decimate takes for the filter h[-half..half] (float64): reversed, since out[m] = sum_j ypad[2m + j] taps[j] is a correlation
+    and y_out[m] = sum_j ypad[2m + j] h[half - j], and zero-padded to a multiple of 4."""
+    n = len(h)
+    taps = np.zeros(n + (-n) % 4)
+    taps[:n] = h[::-1]
+    return taps
+
+
+def decimate_layout(N, half, ntaps):
+    """Host layout of one decimation of N samples -> (offset, padded_len, n_out): the signal sits at ypad[offset : offset + N] of a zeroed row of
+    padded_len floats (a multiple of 4 beyond the last tap of the last output), n_out = ceil(N / 2) as librosa.resample counts."""
+    n_out = (N + 1) // 2
+    plen = 2 * n_out + ntaps + 4
+    return half, plen + (-plen) % 4, n_out
 
 
 def octave_banks(sr=16000, hop=160, n_bins=480, bins_per_octave=60, gamma=20.0, fmin=A0_HZ, sparsity=0.01):
@@ -108,10 +125,8 @@ class VQT:
         for o in self.octaves:
             o["bank_dev"] = torch.from_numpy(o["bank"]).to(device)
         h, self.half = decimation_filter()
-        taps = 2 * self.half + 1
-        self.dec_taps = taps + (-taps) % 4
-        hb = np.zeros((self.dec_taps, 1), dtype=np.float32)
-        hb[:taps, 0] = h[::-1]                                                # y_out[m] = sum_j ypad[2m + j] h[half - j]  (h is symmetric)
+        hb = decimator_taps(h).astype(np.float32)[:, None]
+        self.dec_taps = len(hb)
         self.dec_bank = torch.from_numpy(hb).to(device)
         self.hop, self.n_bins, self.device = hop, n_bins, device
         self.bpo = min(bins_per_octave, n_bins)
@@ -120,11 +135,9 @@ class VQT:
 
     def _decimate(self, y):
         B, N = y.shape
-        n_out = (N + 1) // 2
-        plen = 2 * n_out + self.dec_taps + 4
-        plen += (-plen) % 4
+        off, plen, n_out = decimate_layout(N, self.half, self.dec_taps)
         yp = torch.zeros((B, plen), dtype=torch.float32, device=y.device)
-        yp[:, self.half:self.half + N] = y
+        yp[:, off:off + N] = y
         out = torch.empty((B, n_out), dtype=torch.float32, device=y.device)
         hip.check(hip.lib().a2s_vqt_decimate(hip.stream(), hip._p(yp), plen, hip._p(self.dec_bank), self.dec_taps, hip._p(out), n_out, B), "a2s_vqt_decimate")
         return out
