@@ -17,6 +17,7 @@ import torch
 
 from . import hip
 from .conv_bwd_plan import CHANS, ConvBwdFlags, plan_convstack_bwd
+from .dec_bwd_plan import dim, plan_note_decoder_bwd, plan_staff_issue
 from .spec import SOS, VOCAB_SIZE
 
 
@@ -56,17 +57,6 @@ def _linear_bwd(x, W, dy, G, wname, bname, dx=None, dx_beta=0.0, x_affine=None, 
     return dx
 
 
-_ONES = {}
-
-
-def _one(dev):
-    """Device scalar 1.0: the range of an operand bounded by 1 (softmax weights, GRU states) for the two-term fp16 products."""
-    key = torch.device(dev).index
-    if key not in _ONES:
-        _ONES[key] = torch.ones(1, dtype=torch.float32, device=dev)
-    return _ONES[key]
-
-
 def _staff_token_bwd(eng, S, G, rec, dtok):
     """Backward of one _staff_token call; dtok: (R, >= col0+2S) gradient buffer holding the token gradient."""
     L = hip.lib()
@@ -97,7 +87,7 @@ def _attn_deferred(eng, S, G, prefix, keys, enc, q_all, ds_all, attw_all, dctx_a
                   "a2s_attn_denc_accum")
     else:
         hip.gemm(attw_all, 1, B * T, dctx_all, B * 2 * H, 1, dEnc, 2 * H, T, 2 * H, steps * groups, beta=1.0, batch=B, bsA=T, bsB=2 * H, bsC=T * 2 * H,
-                 two_term=(_one(enc.device), hip.absmax(dctx_all)) if dctx_all.is_contiguous() else None)
+                 two_term=(hip.one(enc.device), hip.absmax(dctx_all)) if dctx_all.is_contiguous() else None)
     nblk = L.a2s_attn_dk_blocks(B, T)
     dvp = torch.empty((nblk, H), dtype=torch.float32, device=enc.device)
     hip.check(L.a2s_attn_dk_accum(hip.stream(), hip._p(keys), hip._p(q_all), hip._p(ds_all), hip._p(S[prefix + ".v.weight"]), hip._p(dK),
@@ -105,48 +95,70 @@ def _attn_deferred(eng, S, G, prefix, keys, enc, q_all, ds_all, attw_all, dctx_a
     _colsum(dvp, H, G[prefix + ".v.weight"], nblk, H)
 
 
-def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc, n_clips, T, deferred=None, enc_amax=None, late=None, defer_launch=False):
-    """Reverse of Engine._decode_staff.  Returns the gradient wrt the initial hidden (rows, 2H); rows = groups * n_clips.
-    late: optional list.  The call's WEIGHT gradients (output projection, GRU, attention query half, embedding rows: everything only the
-    optimizer waits for) are then not computed here: a (closure, event, tensors) entry is appended and Backward.finish runs the closures on the
-    weight-gradient stream beside the encoder's back-propagation -- on the staff's own stream they sit in series with the next segment's decode
-    steps (8-12 ms of GEMMs per call of the bulk clip group, profiles/r05_queue_timeline.txt).  The key / encoder-output gradients stay here.
-    deferred: optional HIP stream for everything that does not gate the recurrence (weight gradients, the deferred key / encoder-
-    output gradients, embedding scatter): a staff's stream executes in order, so leaving them on it would put ~20 % of MFMA-bound GEMM
-    time in series with the HBM-bound attention steps of the next segment; returns (dh0, event after the deferred work or None)."""
-    L = hip.lib()
-    groups = sv.get("groups", 1)
-    B = groups * n_clips
-    cfg = eng.cfg
-    H, E, V = cfg["hidden_size"], cfg["note_emb_size"], VOCAB_SIZE
-    H2, ldx = 2 * H, E + 2 * H
-    n, prefix, dev = sv["steps"], sv["prefix"], enc.device
-    R = n * B
-    # (a) dlogits for all executed steps, step-major (n, B, V)
-    dlog = torch.empty((n, B, V), dtype=torch.float32, device=dev)
-    hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), hip._p(dprobs_bar), hip._p(probs_bar), probs_bar.stride(0), n, hip._p(dlog), R, V, B, 1),
-              "a2s_log_softmax_bwd_rows")
-    # (b) output projection, all steps at once: do_all = dlog W_out ; dW_out += dlog^T o ; db_out += colsum
-    o2d, dlog2d = sv["o"].view(R, 2 * H2), dlog.view(R, V)
-    do_all = torch.empty((n, B, 2 * H2), dtype=torch.float32, device=dev)
-    Wo = S[prefix + ".out.weight"]
-    dlog_amax = hip.absmax(dlog) if enc_amax is not None else None
-    hip.gemm(dlog2d, V, 1, Wo, 2 * H2, 1, do_all.view(R, 2 * H2), 2 * H2, R, 2 * H2, V,          # do_all = dlog W_out  (gates the recurrence)
-             two_term=(dlog_amax, hip.absmax(Wo)) if enc_amax is not None else None)
-    # (c) reverse recurrence
-    dgi_all = torch.empty((n, B, 3 * H2), dtype=torch.float32, device=dev)
-    dgh_all = torch.empty((n, B, 3 * H2), dtype=torch.float32, device=dev)
-    dq_all = torch.empty((n, B, H), dtype=torch.float32, device=dev)
-    ds_all = torch.empty((n, B, T), dtype=torch.float32, device=dev)
-    dctx_all = torch.empty((n, B, H2), dtype=torch.float32, device=dev)
-    # (with m_active the per-step products skip the rows of finished clips: their dx rows are never written and must read as zero)
-    dx = torch.empty((n, B, ldx), dtype=torch.float32, device=dev)          # (zero-filled by a2s_note_decoder_bwd when rows are skipped)
-    dh = torch.empty((2, B, H2), dtype=torch.float32, device=dev)
+def _consumed_tokens(sv, n, B, n_clips, dev):
+    """(n, B) int32, the token each executed step consumed: <sos> at step 0, then the ground truth (where the row's group was teacher-forced) or the
+    argmax of the previous step."""
+    tok = torch.full((n, B), SOS, dtype=torch.int32, device=dev)
+    if n > 1:
+        prev = sv["ids"][:, :n - 1].t()
+        if sv["gt_bar"] is not None:
+            bits = sv.get("flags_dev")                                                                            # bit g: group g teacher-forced
+            if bits is None:
+                bits = torch.tensor(sv["flags"][:n - 1], dtype=torch.int32, device=dev)
+            bits = bits[:n - 1].unsqueeze(1)
+            grp = (torch.arange(B, dtype=torch.int32, device=dev) // n_clips).unsqueeze(0)
+            prev = torch.where(((bits >> grp) & 1).bool(), sv["gt_bar"][:, :n - 1].t().to(torch.int32), prev)
+        tok[1:] = prev
+    return tok
+
+
+def _dec_weight_side(plan, t, S, G, prefix, n, H, E):
+    """The "weights" side of dec_bwd_plan: the products of plan.products over plan.rw rows, each with its bias sum.  t: the call's tensors by the plan's names."""
+    L, dev, R = hip.lib(), t["dlog"].device, n * t["dlog"].shape[1]
+    # operand ranges (two-term fp16 split, DESIGN.md section 5): the bounds of the inputs as Product.x_bound states them, the gradients' max magnitudes measured
+    one = hip.one(dev)
+    bound = {"max(emb, enc)": torch.maximum(hip.absmax(S[prefix + ".embedding.weight"]), t["enc_amax"]), "max(one, enc)": torch.maximum(one, t["enc_amax"]), "one": one}
+    if plan.empty:
+        return
+    rows = {k: (t[k] if t[k].shape[0] == n else t[k][:n]).view(R, t[k].shape[-1]) for k in plan.operands}          # (x, h: one row more than the executed steps)
+    if plan.gather:          # the pairs that ran, as dense operands: the products, bias sums and measured ranges run over those only
+        rows = {k: v.index_select(0, t["live_idx"]) for k, v in rows.items()}
+    for p in plan.products:
+        x, dy = rows[p.x], rows[p.dy]
+        N, K = dy.shape[1], dim(p.cols, H, E)
+        dy_amax = hip.absmax(dy) if p.dy_range == "measure" else t[p.dy_range]
+        sk = L.a2s_gemm_pick_splitk(N, K, plan.rw, 1)
+        hip.gemm(dy, 1, N, x, K, 1, G[prefix + p.weight], dim(p.ld, H, E), N, K, plan.rw, beta=1.0, splitk=sk, c_off=p.col0, two_term=(dy_amax, bound[p.x_bound]))
+        _colsum(dy, N, G[prefix + p.bias], plan.rw, N)
+
+
+def _dec_scatter(plan, t, sv, G, prefix, n, n_clips, E):
+    """The "scatter" side: the embedding rows of the tokens consumed at each step (at the pairs that ran: their tokens, dx columns and dropout masks)."""
+    dx, drop = t["dx"], t["drop"]
+    B, ldx = dx.shape[1], dx.shape[2]
+    tok, dx_w, ld_w = _consumed_tokens(sv, n, B, n_clips, dx.device), dx, ldx
+    if plan.gather:
+        tok = tok.view(-1).index_select(0, t["live_idx"])
+        dx_w, ld_w = dx.view(n * B, ldx)[:, :E].index_select(0, t["live_idx"]), E
+        if drop is not None:
+            drop = drop.reshape(-1, E)[:n * B].index_select(0, t["live_idx"])
+    hip.check(hip.lib().a2s_embed_scatter_add(hip.stream(), hip._p(G[prefix + ".embedding.weight"]), None, hip._p(tok), 1, 0, hip._p(dx_w), ld_w, 0, plan.rw, E, hip._p(drop),
+                                              1.0 / (1.0 - sv["drop_p"]) if drop is not None else 1.0), "a2s_embed_scatter_add")
+
+
+def _note_dec_bwd_args(S, sv, keys, enc, do_all, n_clips, T, H, E):
+    """The argument block of a2s_note_decoder_bwd for one call, what the reverse loop writes allocated.  Returns (block, the tensors it writes by the
+    names of dec_bwd_plan, the persistent launch's workspace or None: alive until the launch is enqueued)."""
+    n, B, _ = do_all.shape
+    H2, prefix, dev = 2 * H, sv["prefix"], enc.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    # (with m_active the per-step products skip the rows of finished clips: their dx rows are never written and must read as zero: zero-filled by the call)
+    w = dict(dgi=new(n, B, 3 * H2), dgh=new(n, B, 3 * H2), dq=new(n, B, H), ds=new(n, B, T), dctx=new(n, B, H2), dx=new(n, B, E + H2), dh=new(2, B, H2))
     a = hip.NoteDecBwdArgs()
     for name, t in (("attn_w", S[prefix + ".attn.attn.weight"]), ("attn_v", S[prefix + ".attn.v.weight"]), ("w_ih", S[prefix + ".gru.weight_ih_l0"]),
                     ("w_hh", S[prefix + ".gru.weight_hh_l0"]), ("keys", keys), ("enc", enc), ("h", sv["h"]), ("x", sv["x"]), ("q", sv["q"]),
-                    ("gates", sv["gates"]), ("attw", sv["attw"]), ("do_all", do_all), ("dgi_all", dgi_all), ("dgh_all", dgh_all),
-                    ("dq_all", dq_all), ("ds_all", ds_all), ("dctx_all", dctx_all), ("dx", dx), ("dh", dh), ("attn_ws", sv["attn_ws"]), ("gemm_ws", sv["gemm_ws"])):
+                    ("gates", sv["gates"]), ("attw", sv["attw"]), ("do_all", do_all), ("dgi_all", w["dgi"]), ("dgh_all", w["dgh"]),
+                    ("dq_all", w["dq"]), ("ds_all", w["ds"]), ("dctx_all", w["dctx"]), ("dx", w["dx"]), ("dh", w["dh"]), ("attn_ws", sv["attn_ws"]), ("gemm_ws", sv["gemm_ws"])):
         setattr(a, name, t.data_ptr() if t is not None else None)
     a.gemm_ws_bytes = sv["gemm_ws"].numel() * 4 if sv["gemm_ws"] is not None else 0
     if sv.get("step_ws") is not None:
@@ -157,100 +169,64 @@ def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc,
     a.persist_ws, a.persist_ws_bytes, a.w_ih_full = None, 0, None
     persist_ws = None
     if sv.get("persist_ws") is not None:
-        nb_ws = L.a2s_note_decoder_bwd_persist_ws_bytes(n_clips)
+        nb_ws = hip.lib().a2s_note_decoder_bwd_persist_ws_bytes(n_clips)
         if nb_ws:
             persist_ws = torch.empty(nb_ws, dtype=torch.uint8, device=dev)
             a.persist_ws, a.persist_ws_bytes = persist_ws.data_ptr(), nb_ws
+    return a, w, persist_ws
+
+
+def _note_decoder_bwd(eng, S, G, sv, keys, enc, dprobs_bar, probs_bar, dK, dEnc, n_clips, T, enc_amax, late=None, defer_launch=False):
+    """Reverse of Engine._decode_staff.  Returns the gradient wrt the initial hidden (rows, 2H); rows = groups * n_clips.  enc_amax: device scalar max |enc|.
+    What follows the reverse loop is dec_bwd_plan.plan_note_decoder_bwd's: this function allocates, launches and walks it.
+    late: optional list.  The call's WEIGHT gradients (output projection, GRU, attention query half, embedding rows: everything only the
+    optimizer waits for) are then not computed here: a (closure, event, tensors) entry is appended and Backward.finish runs the closures on the
+    weight-gradient stream beside the encoder's back-propagation -- on the staff's own stream they sit in series with the next segment's decode
+    steps (8-12 ms of GEMMs per call of the bulk clip group, profiles/r05_queue_timeline.txt).  The key / encoder-output gradients stay here.
+    defer_launch (_note_decoder_bwd_pair): nothing is launched; returns (argument block, the rest of this function, what the launch needs alive)."""
+    L = hip.lib()
+    groups = sv.get("groups", 1)
+    B = groups * n_clips
+    H, E, V = eng.cfg["hidden_size"], eng.cfg["note_emb_size"], VOCAB_SIZE
+    H2 = 2 * H
+    n, prefix, dev = sv["steps"], sv["prefix"], enc.device
+    R = n * B
+    act = sv.get("active") or {}
+    live = act.get("live_idx")
+    plan = plan_note_decoder_bwd(n, B, act.get("live_steps"), live.numel() if live is not None else None, late is not None)
+    # (a) dlogits for all executed steps, step-major (n, B, V)
+    dlog = torch.empty((n, B, V), dtype=torch.float32, device=dev)
+    hip.check(L.a2s_log_softmax_bwd_rows(hip.stream(), hip._p(dprobs_bar), hip._p(probs_bar), probs_bar.stride(0), n, hip._p(dlog), R, V, B, 1),
+              "a2s_log_softmax_bwd_rows")
+    # (b) the half of the output projection that gates the recurrence, all steps at once: do_all = dlog W_out
+    do_all = torch.empty((n, B, 2 * H2), dtype=torch.float32, device=dev)
+    Wo = S[prefix + ".out.weight"]
+    dlog_amax = hip.absmax(dlog)
+    hip.gemm(dlog.view(R, V), V, 1, Wo, 2 * H2, 1, do_all.view(R, 2 * H2), 2 * H2, R, 2 * H2, V, two_term=(dlog_amax, hip.absmax(Wo)))
+    # (c) reverse recurrence
+    a, w, persist_ws = _note_dec_bwd_args(S, sv, keys, enc, do_all, n_clips, T, H, E)
     if not defer_launch:
         hip.check(L.a2s_note_decoder_bwd(hip.stream(), C.byref(a)), "a2s_note_decoder_bwd")
     # (d) everything nobody in the recurrence waits for
-    def deferred_work(part="all"):
-        if part == "attn":          # the key / encoder-output gradients only (the weight gradients follow in Backward.finish)
-            _attn_deferred(eng, S, G, prefix + ".attn", keys, enc, sv["q"], ds_all, sv["attw"], dctx_all, dK, dEnc, n_clips, T, H, n, sv.get("active"), groups)
-            return
-        # Operand ranges of the weight-gradient products (two-term fp16 split): the GRU state lies in (-1, 1), the
-        # context is a convex combination of encoder rows, the token half of x an embedding row; the gradients' max magnitudes are measured.
-        one = _one(dev)
-        xb = torch.maximum(hip.absmax(S[prefix + ".embedding.weight"]), enc_amax) if enc_amax is not None else None
-        ob = torch.maximum(one, enc_amax) if enc_amax is not None else None
-        am = (lambda t: hip.absmax(t)) if enc_amax is not None else (lambda t: None)
-        x2d, h2d = sv["x"][:n].view(R, ldx), sv["h"][:n].view(R, H2)
-        # Every product below contracts over the (step, row) pairs of the call.  Rows whose targets had run out were skipped by the forward pass and
-        # carry EXACT zero gradients from then on (dlog, dgi, dgh, dq: zeros): with the bench's lengths that is three quarters of the pairs.  The
-        # pairs that ran (active["live_idx"], planned on the host with everything else) are gathered into dense operands first -- 22 KB per pair,
-        # read once -- and the products, bias sums and operand ranges run over those only.
-        live = sv["active"].get("live_idx") if (sv.get("active") and sv["active"].get("live_steps") == n) else None
-        dlog_w, o_w, dgi_w, dgh_w, dq_w, Rw = dlog2d, o2d, dgi_all.view(R, 3 * H2), dgh_all.view(R, 3 * H2), dq_all.view(R, H), R
-        if live is not None and live.numel() < 0.8 * R:
-            Rw = live.numel()
-            if Rw == 0:
-                return                                    # nothing ran: every gradient of this call is zero
-            sel = lambda t2d: t2d.index_select(0, live)
-            dlog_w, o_w, dgi_w, dgh_w, dq_w, x2d, h2d = sel(dlog_w), sel(o_w), sel(dgi_w), sel(dgh_w), sel(dq_w), sel(x2d), sel(h2d)
-        else:
-            live = None
-        _linear_bwd(o_w, Wo, dlog_w, G, prefix + ".out.weight", prefix + ".out.bias", dy_amax=dlog_amax, x_bound=ob)       # dW_out += dlog^T o ; db_out += colsum
-        _linear_bwd(x2d, S[prefix + ".gru.weight_ih_l0"], dgi_w, G, prefix + ".gru.weight_ih_l0", prefix + ".gru.bias_ih_l0",
-                    dy_amax=am(dgi_w), x_bound=xb)
-        _linear_bwd(h2d, S[prefix + ".gru.weight_hh_l0"], dgh_w, G, prefix + ".gru.weight_hh_l0", prefix + ".gru.bias_hh_l0",
-                    dy_amax=am(dgh_w), x_bound=one)
-        # attention query half: dW[:, :2H] += dq^T h ; db += colsum(dq)
-        Gw = G[prefix + ".attn.attn.weight"]
-        sk = L.a2s_gemm_pick_splitk(H, H2, Rw, 1)
-        hip.gemm(dq_w, 1, H, h2d, H2, 1, Gw, 4 * H, H, H2, Rw, beta=1.0, splitk=sk, two_term=(hip.absmax(dq_w), one) if enc_amax is not None else None)
-        _colsum(dq_w, H, G[prefix + ".attn.attn.bias"], Rw, H)
-        if part == "all":
-            _attn_deferred(eng, S, G, prefix + ".attn", keys, enc, sv["q"], ds_all, sv["attw"], dctx_all, dK, dEnc, n_clips, T, H, n, sv.get("active"), groups)
-        # embedding rows of the tokens consumed at each step: <sos> at step 0, then gt or argmax of the previous step
-        tok = torch.full((n, B), SOS, dtype=torch.int32, device=dev)
-        if n > 1:
-            prev = sv["ids"][:, :n - 1].t()
-            if sv["gt_bar"] is not None:
-                bits = sv.get("flags_dev")                                                                            # bit g: group g teacher-forced
-                if bits is None:
-                    bits = torch.tensor(sv["flags"][:n - 1], dtype=torch.int32, device=dev)
-                bits = bits[:n - 1].unsqueeze(1)
-                grp = (torch.arange(B, dtype=torch.int32, device=dev) // n_clips).unsqueeze(0)
-                flags = ((bits >> grp) & 1).bool()
-                prev = torch.where(flags, sv["gt_bar"][:, :n - 1].t().to(torch.int32), prev)
-            tok[1:] = prev
-        drop = sv["drop"]
-        dx_w, ld_w = dx, ldx
-        if live is not None:        # (the token-embedding columns of dx at the pairs that ran; their tokens; their dropout masks)
-            tok = tok.view(-1).index_select(0, live)
-            dx_w, ld_w = dx.view(R, ldx)[:, :E].index_select(0, live), E
-            if drop is not None:
-                drop = drop.reshape(-1, E)[:R].index_select(0, live)
-        hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(G[prefix + ".embedding.weight"]), None, hip._p(tok), 1, 0, hip._p(dx_w), ld_w, 0, Rw, E, hip._p(drop),
-                                          1.0 / (1.0 - sv["drop_p"]) if drop is not None else 1.0), "a2s_embed_scatter_add")
+    t = dict(w, dlog=dlog, do_all=do_all, dlog_amax=dlog_amax, enc_amax=enc_amax, live_idx=live, flags_dev=sv.get("flags_dev"),
+             **{k: sv[k] for k in ("o", "x", "h", "ids", "drop", "gt_bar")})
+    sides = {"weights": lambda: _dec_weight_side(plan, t, S, G, prefix, n, H, E),
+             "keys": lambda: _attn_deferred(eng, S, G, prefix + ".attn", keys, enc, sv["q"], w["ds"], sv["attw"], w["dctx"], dK, dEnc, n_clips, T, H, n, sv.get("active"), groups),
+             "scatter": lambda: _dec_scatter(plan, t, sv, G, prefix, n, n_clips, E)}
 
-    def after_launch():
-        if late is not None:
-            deferred_work("attn")
+    def walk():
+        for side in plan.on_stream:
+            sides[side]()
+        if plan.in_closure:
             ev = torch.cuda.Event()
             ev.record()
-            # everything the closure reads that was allocated on this (staff / group) stream: the weight-gradient stream records them all
-            act = sv.get("active") or {}
-            late.append((lambda: deferred_work("weights"), ev, (dlog, do_all, dgi_all, dgh_all, dq_all, dx, sv["x"], sv["h"], sv["o"], sv["ids"], sv["drop"], sv["gt_bar"],
-                                                                sv.get("flags_dev"), act.get("live_idx"), dlog_amax, enc_amax)))
-            return dh[0], None
-        if deferred is None:
-            deferred_work()
-            return dh[0], None
-        ev = torch.cuda.Event()
-        ev.record()
-        deferred.wait_event(ev)
-        for t in (dlog, do_all, dgi_all, dgh_all, dq_all, ds_all, dctx_all, dx):
-            t.record_stream(deferred)                       # keep the allocator from handing them back to the staff stream too early
-        with torch.cuda.stream(deferred):
-            deferred_work()
-            done = torch.cuda.Event()
-            done.record()
-        return dh[0], done
+            # the entry holds everything the closure reads that was allocated on this (staff / group) stream: the weight-gradient stream records them all
+            late.append((lambda: [sides[side]() for side in plan.in_closure], ev, tuple(t[k] for k in plan.keep_alive)))
+        return w["dh"][0]
 
-    if defer_launch:                  # _note_decoder_bwd_pair: the arguments are ready (kept alive by the closure), the caller launches both staves with one call
-        return a, after_launch, (persist_ws,)
-    return after_launch()
+    if defer_launch:                  # the arguments are ready (kept alive by the closure), the caller launches both staves with one call
+        return a, walk, (persist_ws,)
+    return walk()
 
 
 def _note_decoder_bwd_pair(calls, streams, pair):
@@ -268,6 +244,7 @@ def _note_decoder_bwd_pair(calls, streams, pair):
         with torch.cuda.stream(st):
             res.append(after())
     return res
+
 
 class Backward:
     """The backward pass in three phases, so that the decoder part of each clip group can be started by whoever has that group's loss
@@ -307,18 +284,12 @@ class Backward:
         self.concurrent = bool(concurrent)
         self.dEnc_staff = [torch.zeros_like(self.dEnc), torch.zeros_like(self.dEnc)] if self.concurrent else [self.dEnc, self.dEnc]
         self.bar_major = bool(bar_major)
-        # weight gradients etc. of each staff off its recurrence stream: measured +0.7 % in round 1, but two more streams than the four
-        # hardware queues the runtime has (engine.group_stream) -- off since the clip groups need a queue
-        self.use_deferred = False
         # round 5: the note decoders' weight gradients run in finish(), on the weight-gradient stream beside the encoder's back-propagation
         # (eng.late_wgrads = False: where they were, behind each call's reverse loop on the staff's stream)
         lw = getattr(eng, "late_wgrads", None)
         self.late_wgrads = True if lw is None else bool(lw)
         self.late = []                                     # (closure, event on the issuing stream, tensors it reads): appended by any group's host thread
         self.clip_groups = list(clip_groups) if clip_groups else [(0, B)]
-        # the deferred products of the decoder backward (weight gradients, key / encoder-output gradients) with measured operand ranges on
-        # the two-term fp16 split instead of three bf16 terms (round 2's)
-        self.two_term = True
         self.d_hidden = torch.empty((B, H2), dtype=torch.float32, device=dev)       # gradient wrt the encoder's bridge output (initial bar-level hidden)
         self.group_flat = [self.flat] + [torch.zeros_like(self.flat) for _ in self.clip_groups[1:]]
         self.group_ptrs = [self.G["__staff_emb_ptrs__"]]
@@ -330,11 +301,11 @@ class Backward:
     def decoder_group(self, gidx, gs, dts_g, dkey_g, dup_g, dlo_g):
         """Decoder backward of clip group gidx (gs: what Engine.forward saved for it) on the calling thread's current stream (+ the two
         side streams for group 0).  d*_g: gradients wrt the group's four output views (gs["outs"])."""
-        from .engine import fork_on_streams, staff_streams
+        from .engine import fork_on_streams, staff_streams, staves_concurrent
         eng, S, G, dev, T = self.eng, self.S, self.G, self.dev, self.T
         names, offs, group_flat, group_ptrs = self.names, self.offs, self.group_flat, self.group_ptrs
         dEnc, dK, dEnc_staff, d_hidden = self.dEnc, self.dK, self.dEnc_staff, self.d_hidden
-        concurrent, bar_major, use_deferred = self.concurrent, self.bar_major, self.use_deferred
+        concurrent, bar_major = self.concurrent, self.bar_major
         L = hip.lib()
         cfg = eng.cfg
         H, Sz = cfg["hidden_size"], cfg["staff_emb_size"]
@@ -346,7 +317,9 @@ class Backward:
         Gg = G if gidx == 0 else {k: group_flat[gidx][off:off + S[k].numel()].view(S[k].shape) for k, off in zip(names, offs)}
         Gg["__staff_emb_ptrs__"] = group_ptrs[gidx]
         enc_g, keys_g = gs["enc"], gs["keys"]
-        enc_amax_g = hip.absmax(enc_g) if (self.two_term and enc_g.is_contiguous()) else None      # max |enc| of the group's clips
+        if not enc_g.is_contiguous():
+            raise ValueError("the group's slice of the encoder output is not contiguous: its range cannot be measured, and the decoder's products have no other arithmetic")
+        enc_amax_g = hip.absmax(enc_g)      # max |enc| of the group's clips: the operand range of the decoder's deferred products (two-term fp16 split)
         dEnc_g = dEnc[b0:b1]
         dK_g = {p: t[b0:b1] for p, t in dK.items()}
         dEnc_staff_g = [t[b0:b1] for t in dEnc_staff]
@@ -354,12 +327,7 @@ class Backward:
         # as in Engine.forward (engine.staff_streams); a group whose calls ran as persistent launches back-propagates its staves one after
         # the other (two persistent launches must never be in flight together)
         persist_g = any(seg["staff"][k][2].get("persist_ws") is not None for seg in gs["segments"] for k in ("up", "lo"))
-        from .engine import staves_concurrent
-        concurrent_g = concurrent and staves_concurrent(gidx, len(self.clip_groups)) and not persist_g
-        streams = staff_streams(dev, gidx) if concurrent_g else None
-        use_deferred_g = use_deferred and gidx == 0
-        deferred_streams = _deferred_streams(dev, gidx) if use_deferred_g else None
-        deferred_done = []
+        staves_g = staves_concurrent(gidx, len(self.clip_groups))
         seg_dh0 = {}                # segment index -> [dh0 of the upper call, dh0 of the lower call], rows = (bar in segment, clip)
 
         def segment_decoders_bwd(si_seg):
@@ -374,18 +342,17 @@ class Backward:
                 else:
                     dpr, pr = dout[:, bar0], out_t[:, bar0]
                 calls.append((eng, S, Gg, seg["staff"][name][2], keys_g[prefix], enc_g, dpr, pr, dK_g[prefix], dEnc_staff_g[si], Bg, T,
-                              deferred_streams[si] if use_deferred_g else None, enc_amax_g, self.late if self.late_wgrads else None))
-            if concurrent_g and seg.get("pair") is not None and L.a2s_debug_get(b"attn_pair"):
+                              enc_amax_g, self.late if self.late_wgrads else None))
+            issue = plan_staff_issue(concurrent, staves_g, persist_g, seg.get("pair") is not None, bool(L.a2s_debug_get(b"attn_pair")))
+            if issue == "pair":
                 # both staves' reverse loops from one host thread, their sweeps as one launch per step (as the forward ran them)
+                streams = staff_streams(dev, gidx)
                 (res,), events = fork_on_streams(dev, [streams[1]], [lambda: _note_decoder_bwd_pair(calls, streams, seg["pair"])])(wait=False)
-                seg_dh0[si_seg] = ([r[0] for r in res], events)
-                deferred_done.extend(r[1] for r in res if r[1] is not None)
-            elif concurrent_g:    # one host thread per staff (engine.fork_on_streams); the current stream waits when the result is consumed
-                res, events = fork_on_streams(dev, streams, [lambda args=args: _note_decoder_bwd(*args) for args in calls])(wait=False)
-                seg_dh0[si_seg] = ([r[0] for r in res], events)
-                deferred_done.extend(r[1] for r in res if r[1] is not None)
+                seg_dh0[si_seg] = (res, events)
+            elif issue == "fork":    # one host thread per staff (engine.fork_on_streams); the current stream waits when the result is consumed
+                seg_dh0[si_seg] = fork_on_streams(dev, staff_streams(dev, gidx), [lambda args=args: _note_decoder_bwd(*args) for args in calls])(wait=False)
             else:
-                seg_dh0[si_seg] = ([_note_decoder_bwd(*args)[0] for args in calls], [])
+                seg_dh0[si_seg] = ([_note_decoder_bwd(*args) for args in calls], [])
 
         # The note decoders' backward passes only need the loss gradients: all segments are enqueued up front (last segment first, as the
         # bar chain below consumes them), so the two staff streams run through every segment back to back instead of draining at each
@@ -477,8 +444,6 @@ class Backward:
             hip.check(L.a2s_embed_scatter_add(hip.stream(), hip._p(Gg[table]), None, None, 0, cid, hip._p(d_token_next), tokw, col, Bg, width, None, 1.0),
                       "scatter sos ts/key")
         d_hidden[b0:b1].copy_(d_hid_carry)
-        for ev in deferred_done:                      # the staves' weight / key / encoder-output gradients are complete past this point
-            torch.cuda.current_stream().wait_event(ev)
         return None
 
 
@@ -522,17 +487,15 @@ class Backward:
             dEnc.add_(self.dEnc_staff[0]).add_(self.dEnc_staff[1])
         # ---- attention keys: K = enc W_e^T  ->  dW_e += dK^T enc ; dEnc += dK W_e
         enc2d = enc.view(B * T, H2)
-        enc_amax = hip.absmax(enc) if self.two_term else None
+        enc_amax = hip.absmax(enc)
         for p, dKp in dK.items():
             Wn = p + ".attn.attn.weight"
-            dk_amax = hip.absmax(dKp) if self.two_term else None
+            dk_amax = hip.absmax(dKp)
             # (tall-K kernel: dK packed, enc streamed once, the result into columns 2H.. of the 4H-wide matrix; csrc/a2s_linear.hip)
             if not hip.tallk_wgrad(dKp, 0, H, enc2d, 0, H2, G[Wn], H2, 4 * H, B * T, H, H2, dk_amax, enc_amax):
                 sk = L.a2s_gemm_pick_splitk(H, H2, B * T, 1)
-                hip.gemm(dKp, 1, H, enc2d, H2, 1, G[Wn], 4 * H, H, H2, B * T, beta=1.0, splitk=sk, c_off=H2,
-                         two_term=(dk_amax, enc_amax) if self.two_term else None)
-            hip.gemm(dKp, H, 1, S[Wn], 4 * H, 1, dEnc, H2, B * T, H2, H, beta=1.0, b_off=H2,
-                     two_term=(dk_amax, hip.absmax(S[Wn])) if self.two_term else None)
+                hip.gemm(dKp, 1, H, enc2d, H2, 1, G[Wn], 4 * H, H, H2, B * T, beta=1.0, splitk=sk, c_off=H2, two_term=(dk_amax, enc_amax))
+            hip.gemm(dKp, H, 1, S[Wn], 4 * H, 1, dEnc, H2, B * T, H2, H, beta=1.0, b_off=H2, two_term=(dk_amax, hip.absmax(S[Wn])))
         if late_join is not None:
             wg = _weight_grad_stream(dev)
             wg.wait_stream(torch.cuda.current_stream())            # (the key products above)
@@ -546,20 +509,15 @@ class Backward:
         # them) overlap with the START of the ConvStack backward: the caller's stream does not wait for them here.  The decoder + encoder slice
         # is announced from that stream (a collective issued there is ordered behind its work, which itself waited for everything the main
         # stream had enqueued when those GEMMs were launched), and the main stream joins it after the ConvStack backward.
-        defer = True
-        d_conv = _encoder_bwd(eng, S, G, sv["enc"], dEnc, d_hid_carry, B, T, wait_weight_grads=not defer)
+        d_conv = _encoder_bwd(eng, S, G, sv["enc"], dEnc, d_hid_carry, B, T)
         n_conv = next(off for k, off in zip(names, offs) if not k.startswith("convstack."))      # state_dict order: convstack first
         if grad_ready is not None:
-            if defer:
-                with torch.cuda.stream(_weight_grad_stream(dev)):
-                    grad_ready(self.flat_full, n_conv, total + 1)
-            else:
+            with torch.cuda.stream(_weight_grad_stream(dev)):
                 grad_ready(self.flat_full, n_conv, total + 1)           # (+ the loss word)
         if getattr(eng, "conv_unperm", None) is not None:       # the ConvStack ran before the clips were permuted into their groups (train.TrainStep)
             d_conv = d_conv.reshape(B, T, -1).index_select(0, eng.conv_unperm)
         _convstack_bwd(eng, S, G, sv["conv"], d_conv, B, T, F)
-        if defer:
-            torch.cuda.current_stream().wait_stream(_weight_grad_stream(dev))
+        torch.cuda.current_stream().wait_stream(_weight_grad_stream(dev))
         if grad_ready is not None:
             grad_ready(flat, 0, n_conv)
         G[None] = flat
@@ -598,27 +556,15 @@ def backward(eng, S, grad_outputs, grad_ready=None, loss_total=None):
     return ctx.finish(grad_ready)
 
 
-_DEFERRED_STREAMS = {}
-
-
-def _deferred_streams(dev, group=0):
-    idx = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
-    key = (idx, group)
-    if key not in _DEFERRED_STREAMS:
-        _DEFERRED_STREAMS[key] = (torch.cuda.Stream(device=idx), torch.cuda.Stream(device=idx))
-    return _DEFERRED_STREAMS[key]
-
-
-
 def _weight_grad_stream(dev):
     from .engine import group_stream
     return group_stream(dev, 1)             # the fourth stream of the budget: idle while the encoder back-propagates
 
 
-def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
-    """wait_weight_grads=False: the caller's stream is NOT made to wait for the weight gradients on _weight_grad_stream(dev) (layer 0's run
-    after its recurrence, with nothing left to hide them under): the caller waits for that stream before anything reads the encoder's
-    gradient slice (Backward.finish announces the slice FROM that stream and joins it after the ConvStack backward)."""
+def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T):
+    """The caller's stream is NOT made to wait for the weight gradients on _weight_grad_stream(dev) (layer 0's run after its recurrence, with
+    nothing left to hide them under): the caller waits for that stream before anything reads the encoder's gradient slice (Backward.finish
+    announces the slice FROM that stream and joins it after the ConvStack backward)."""
     L = hip.lib()
     H = eng.cfg["hidden_size"]
     dev = dEnc.device
@@ -635,8 +581,7 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
             dhn.append(d)
         _colsum(dpre, 2 * H, G["encoder.fc.bias"], B, H, x_off=l * H)
     gws = [hip.gemm_workspace(B, dev), hip.gemm_workspace(B, dev)]
-    two_term = True
-    in_amax = hip.absmax(es["layers"][0]["in"]) if two_term else None        # max of the ConvStack features (layer 0's input)
+    in_amax = hip.absmax(es["layers"][0]["in"])        # max of the ConvStack features (layer 0's input)
     dout = dEnc                                              # gradient wrt layer-1 outputs (B,T,2H)
     for layer in (1, 0):
         ls = es["layers"][layer]
@@ -654,7 +599,7 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
             # max |dgi|, max |dghs| (the operand ranges of dX and of the deferred weight gradients) come out of the persistent BPTT launch, which
             # holds every element in a register; the launch-per-step kernels do not produce them (valid = 0): the tensors are measured then
             ranges, valid = torch.empty(2, device=dev), C.c_int(0)
-            if two_term and L.a2s_debug_get(b"tallk_wgrad") > 0:
+            if L.a2s_debug_get(b"tallk_wgrad") > 0:
                 hip.check(L.a2s_gru_seq_bwd_ranged(hip.stream(), _ptr(dout, d * H), T * 2 * H, 2 * H, _ptr(out, d * H), T * 2 * H, 2 * H, hip._p(ls["dirs"][d]["gates"]),
                                                    hip._p(S[f"encoder.gru.weight_hh_{sfx}"]), hip._p(dhn[2 * layer + d]), hip._p(dgi), hip._p(dghs), hip._p(dgh_first),
                                                    hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(gws[d]), gws[d].numel() * 4, hip._p(ranges), C.byref(valid)),
@@ -672,8 +617,8 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
             dgi2 = res[d][0].view(B * T, 3 * H)
             Wih = S[f"encoder.gru.weight_ih_{sfx}"]
             ranges = res[d][5]
-            tt = (ranges[0:1] if ranges is not None else hip.absmax(dgi2), hip.absmax(Wih)) if two_term else None        # ranges: the two-term fp16 split
-            dgi_amax.append(tt[0] if tt else None)
+            tt = (ranges[0:1] if ranges is not None else hip.absmax(dgi2), hip.absmax(Wih))        # ranges: the two-term fp16 split
+            dgi_amax.append(tt[0])
             if L.a2s_debug_get(b"gemm_bf16x3") > 0:      # k-contiguous weight copy (<= 1.5 MB): both operands on the GEMM's split-operand path
                 hip.gemm(dgi2, 3 * H, 1, Wih.t().contiguous(), 1, 3 * H, dX, I, B * T, I, 3 * H, beta=0.0 if d == 0 else 1.0, two_term=tt)
             else:
@@ -694,22 +639,20 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T, wait_weight_grads=True):
                 dgi2, dghs2 = dgi.view(B * T, 3 * H), dghs.view(B * T, 3 * H)
                 # Tall-K kernel (csrc/a2s_linear.hip): the GRADIENT is the streamed operand -- read once, its column sums (the bias gradient) taken
                 # on the way -- the layer's input / output is packed, and the result lands transposed, in the parameter's (3H, I) layout.
-                x_bound = ((in_amax if layer == 0 else hip.one(dev)) if two_term else None)
+                x_bound = in_amax if layer == 0 else hip.one(dev)
                 if not hip.tallk_wgrad(inp, 0, I, dgi2, 0, 3 * H, G[f"encoder.gru.weight_ih_{sfx}"], 0, I, B * T, I, 3 * H, x_bound, dgi_amax[d],
                                        transposed=True, bias=G[f"encoder.gru.bias_ih_{sfx}"]):
                     _linear_bwd(inp, S[f"encoder.gru.weight_ih_{sfx}"], dgi2, G, f"encoder.gru.weight_ih_{sfx}", f"encoder.gru.bias_ih_{sfx}",
                                 dy_amax=dgi_amax[d], x_bound=x_bound)
-                dghs_amax = (ranges[1:2] if ranges is not None else hip.absmax(dghs2)) if two_term else None
+                dghs_amax = ranges[1:2] if ranges is not None else hip.absmax(dghs2)
                 if not hip.tallk_wgrad(out, d * H, 2 * H, dghs2, 0, 3 * H, G[f"encoder.gru.weight_hh_{sfx}"], 0, H, B * T, H, 3 * H,
-                                       hip.one(dev) if two_term else None, dghs_amax, transposed=True, bias=G[f"encoder.gru.bias_hh_{sfx}"]):
+                                       hip.one(dev), dghs_amax, transposed=True, bias=G[f"encoder.gru.bias_hh_{sfx}"]):
                     sk = L.a2s_gemm_pick_splitk(3 * H, H, B * T, 1)
                     hip.gemm(dghs2, 1, 3 * H, out, 2 * H, 1, G[f"encoder.gru.weight_hh_{sfx}"], H, 3 * H, H, B * T, beta=1.0, splitk=sk, b_off=d * H,
-                             two_term=(dghs_amax, hip.one(dev)) if two_term else None)
+                             two_term=(dghs_amax, hip.one(dev)))
                     _colsum(dghs2, 3 * H, G[f"encoder.gru.bias_hh_{sfx}"], B * T, 3 * H)
                 _colsum(dgh_first, 3 * H, G[f"encoder.gru.bias_hh_{sfx}"], B, 3 * H)
         dout = dX.view(B, T, I)
-    if wait_weight_grads:
-        torch.cuda.current_stream().wait_stream(_weight_grad_stream(dev))     # the encoder gradients are complete past this point
     return dout                                              # (B, T, conv_feature_size)
 
 
