@@ -3,7 +3,7 @@
 
 As the reference's finetune.py (:230-294): starts from the pre-training checkpoints by copying ``<pretrain>/save`` into the new
 output folder and resetting their recorded WER so that the first fine-tuned epoch is kept; fixed teacher-forcing ratio; the test
-split doubles as validation split.  ``--constrained_decoding=true``, ``--beam_size=K [--beam_length_penalty=A]``, ``--note_metrics=true``, ``--synthetic_scores=rendered`` and
+split doubles as validation split.  ``--constrained_decoding=true``, ``--metrical_decoding=true``, ``--beam_size=K [--beam_length_penalty=A]``, ``--note_metrics=true``, ``--synthetic_scores=rendered`` and
 ``--transpose_augment=K [--detune_bins=D]`` as in pretrain.py;
 ``--tempo_augment=R`` likewise: the one variation a fine-tuning corpus of recordings otherwise lacks, each clip being heard at exactly one tempo;
 ``--eq_augment_db=E --noise_augment_db="(lo, hi)" --mask_time=Wt --mask_freq=Wf [--mask_count=m]`` likewise: microphone and instrument response, noise floor and missing stretches

@@ -304,6 +304,45 @@ int a2s_grammar_argmax_rows(void* stream, const float* x, long ldx, float* y, lo
                             int* choice_out, int R, int V);
 int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state, int* steps_done);
 int a2s_grammar_launches(void);
+/* ---- metre-aware constrained decoding (csrc/a2s_grammar.hip): the grammar above plus the metre of the bar.  A token the
+ * table allows must also pass the row's metre: a note starts in a spine only where its previous note ends, a `.` stands only where one still
+ * sounds, a duration neither overfills the bar nor leaves a remainder no sum of duration symbols fills, chord members share one duration, later
+ * lines have the first line's field count, a line break needs the earliest spine end m below the bar length L and <eos> needs m == L (the empty
+ * bar stays legal).  row_metre holds A2S_METRE_INTS ints per row, read and updated in place:
+ *     [0] L: bar length in ticks of 1/147840 whole note; L <= 0: the row is unmetred and obeys the table alone (its ints are never written)
+ *     [1] t: onset of the current line   [2] first_line (1 / 0)   [3] n_fields (fixed by the first line break)   [4] field: current spine, 0 .. 7
+ *     [5] in_chord (1 behind a chord separator, until the field ends)   [6] field_dur: ticks of the field's first note   [7] reserved, 0
+ *     [8 .. 15] end[0 .. 7]: where each spine's last note ends
+ * A fresh row is {L, 0, 1, 0, 0, 0, 0, 0, 0 x 8}.  The metre reference (the library's a2s_metre_ref; like the grammar's table it is passed member by
+ * member, all device memory): dur_ticks: V ints, ticks of a duration symbol; cls: V bytes of A2S_METRE_CLS_* (0: a class the metre does not look
+ * at); fillable: n_fillable bytes (max L + 1), fillable[r] != 0 where r ticks are a sum of duration symbols (an index outside the table reads as
+ * not fillable); row_metre: R x A2S_METRE_INTS ints.  Values read from row_metre are clamped before they index anything.
+ * a2s_metre_argmax_rows / a2s_note_decoder_fwd_metre: a2s_grammar_argmax_rows / a2s_note_decoder_fwd_grammar with that predicate -- the same
+ * argument rules, the same loop (launch per step, or replayed as a graph), the same log-probabilities; a NULL member of the metre reference or
+ * n_fillable < 1: A2S_ERR_ARG, nothing is launched.  With every L <= 0 they compute what the grammar entry points compute, bit for bit.
+ * a2s_metre_launches: metre step epilogues launched so far (proof of the path). */
+#define A2S_METRE_INTS 16
+#define A2S_METRE_FIELDS 8
+#define A2S_METRE_L 0
+#define A2S_METRE_T 1
+#define A2S_METRE_FIRST 2
+#define A2S_METRE_NFIELDS 3
+#define A2S_METRE_FIELD 4
+#define A2S_METRE_CHORD 5
+#define A2S_METRE_FDUR 6
+#define A2S_METRE_END 8
+#define A2S_METRE_CLS_DUR 1
+#define A2S_METRE_CLS_NULL 2
+#define A2S_METRE_CLS_OPEN 3
+#define A2S_METRE_CLS_TAB 4
+#define A2S_METRE_CLS_NL 5
+#define A2S_METRE_CLS_SP 6
+#define A2S_METRE_CLS_EOS 7
+int a2s_metre_argmax_rows(void* stream, const float* x, long ldx, float* y, long ldy, const signed char* next_state, int n_states, int* row_state,
+                          const int* dur_ticks, const uint8_t* cls, const uint8_t* fillable, int n_fillable, int* row_metre, int* choice_out, int R, int V);
+int a2s_note_decoder_fwd_metre(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state,
+                               const int* dur_ticks, const uint8_t* cls, const uint8_t* fillable, int n_fillable, int* row_metre, int* steps_done);
+int a2s_metre_launches(void);
 /* ---- beam-search decoding of one (bar, staff) call (csrc/a2s_beam.hip).  The call runs over B clips with K beam slots
  * each, 1 <= K <= A2S_BEAM_MAX: args->R = K * B, args->n_clips = B, row = slot * B + clip (the fused-bars layout, so the attention kernels read a
  * clip's key image and encoder rows once for its K rows); every row of args->h / args->x starts from the same state and the <sos> embedding.

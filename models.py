@@ -75,8 +75,10 @@ class _Transcribe(torch.autograd.Function):
         S = dict(zip(names, params))
         S.update(module._buffer_dict())
         eng = engine.Engine(module.cfg)
-        if module.constrained_decoding and inference:
+        if (module.constrained_decoding or module.metrical_decoding) and inference:
             eng.kern_grammar = module._kern_grammar()
+        if module.metrical_decoding and inference:
+            eng.kern_metre = module._kern_metre()
         if inference:
             eng.beam_size, eng.beam_length_penalty = module.beam_size, module.beam_length_penalty
         eng.alignment = bool(module.alignment) and not module.training
@@ -108,6 +110,10 @@ class ScoreTranscription(nn.Module):
     # log-probability tensors stay the unconstrained ones.  False (default): the reference's greedy decoder, `last_decoded` is None.
     constrained_decoding = False
     last_decoded = None
+    # True (implies constrained_decoding): inference also keeps every decoded bar inside the metre of the time signature the model predicts for it
+    # (piano_a2s_amd.kern_grammar.KernMetre): a bar that reaches <eos> fills its time signature exactly.  Greedy decoding only:
+    # with beam_size >= 2 or alignment the forward raises.
+    metrical_decoding = False
     # beam search over the note sequences of every (bar, staff) in inference (csrc/a2s_beam.hip): beam_size hypotheses per
     # clip, 1 .. 4, 1 = greedy; each clip keeps the one with the largest score / len^beam_length_penalty.  With >= 2 the emitted ids are in
     # `last_decoded` (they are not argmax of the returned log-probabilities) and the kept hypotheses' scores in `last_beam_scores`
@@ -129,6 +135,12 @@ class ScoreTranscription(nn.Module):
             from piano_a2s_amd.kern_grammar import KernGrammar
             self._grammar = KernGrammar(labels.labels)
         return self._grammar
+
+    def _kern_metre(self):
+        if getattr(self, "_metre", None) is None:
+            from piano_a2s_amd.kern_grammar import KernMetre
+            self._metre = KernMetre(self._kern_grammar())
+        return self._metre
 
     def __init__(self, in_channels=1, freq_bins=480, conv_feature_size=256,
                  hidden_size=256, max_bars=5, num_time_sig=7, num_keys=14,

@@ -222,6 +222,19 @@ int a2s_note_decoder_fwd_grammar(void* stream, const a2s_note_dec_args* args, co
     return a2s_note_decoder_fwd_grammar_impl(ST, *args, g, steps_done);
 }
 int a2s_grammar_launches(void) { return a2s_grammar_launches_impl(); }
+int a2s_metre_argmax_rows(void* stream, const float* x, long ldx, float* y, long ldy, const signed char* next_state, int n_states, int* row_state,
+                          const int* dur_ticks, const uint8_t* cls, const uint8_t* fillable, int n_fillable, int* row_metre, int* choice_out, int R, int V) {
+    const a2s_metre_ref m = {dur_ticks, cls, fillable, n_fillable, row_metre};
+    return a2s_metre_argmax_rows_impl(ST, x, ldx, y, ldy, next_state, n_states, row_state, &m, choice_out, R, V);
+}
+int a2s_note_decoder_fwd_metre(void* stream, const a2s_note_dec_args* args, const signed char* next_state, int n_states, int* row_state,
+                               const int* dur_ticks, const uint8_t* cls, const uint8_t* fillable, int n_fillable, int* row_metre, int* steps_done) {
+    if (!args) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_metre: null args"); return A2S_ERR_ARG; }
+    const a2s_grammar_ref g = {next_state, n_states, row_state};
+    const a2s_metre_ref m = {dur_ticks, cls, fillable, n_fillable, row_metre};
+    return a2s_note_decoder_fwd_metre_impl(ST, *args, g, &m, steps_done);
+}
+int a2s_metre_launches(void) { return a2s_metre_launches_impl(); }
 int a2s_note_decoder_fwd_beam(void* stream, const a2s_note_dec_args* args, const a2s_beam_args* beam, int* steps_done) {
     if (!args || !beam) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_beam: null args"); return A2S_ERR_ARG; }
     return a2s_note_decoder_fwd_beam_impl(ST, *args, *beam, steps_done);

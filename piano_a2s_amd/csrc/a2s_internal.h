@@ -128,6 +128,8 @@ struct StepFinArgs {
 };
 // a token grammar for the greedy decoder: next[s * V + v] = state after token v in state s, negative where v is illegal; one state per row
 struct a2s_grammar_ref { const signed char* next; int n_states; int* row_state; };
+// the metre on top of it (members as include/a2s.h documents them): tables per token id, and 16 ints per row
+struct a2s_metre_ref { const int* dur_ticks; const uint8_t* cls; const uint8_t* fillable; int n_fillable; int* row_metre; };
 int a2s_gru_gates_fwd_impl(hipStream_t st, const float* gi, long ldgi, const float* gh, long ldgh, const float* hprev,
     long ldhp, float* hout, long ldho, float* hout2, long ldho2, float* save, int R, int H);
 int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t, const float* dhz_in, const float* dout, long ld_dout,
@@ -145,6 +147,7 @@ int a2s_embed_rows_impl(hipStream_t st, const float* table, const long long* ids
     int const_id, float* out, long ldo, int col0, int R, int E, const uint8_t* drop, float inv_keep);
 int a2s_note_decoder_fwd_impl(hipStream_t st, const a2s_note_dec_args& a, int* steps_done);
 int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_grammar_ref& g, int* steps_done);
+int a2s_note_decoder_fwd_metre_impl(hipStream_t st, const a2s_note_dec_args& a, const a2s_grammar_ref& g, const a2s_metre_ref* mt, int* steps_done);
 int a2s_note_decoder_fwd_pair_impl(hipStream_t su, hipStream_t sl, const a2s_note_dec_args& au, const a2s_note_dec_args& al, const int* pair_order,
     const int* pair_rank, const int* pair_n_active, int* done_u, int* done_l);
 int a2s_staff_emb_fwd_impl(hipStream_t st, const float* note_emb, const float* const* w /* 8 GRU tensors f then r */,
@@ -220,6 +223,11 @@ int a2s_grammar_argmax_rows_impl(hipStream_t st, const float* x, long ldx, float
     int* choice_out, int R, int V);
 int a2s_grammar_step_finalize_impl(hipStream_t st, const StepFinArgs& a, const a2s_grammar_ref& g);
 int a2s_grammar_launches_impl(void);
+bool a2s_metre_ref_ok(const a2s_metre_ref& m);
+int a2s_metre_argmax_rows_impl(hipStream_t st, const float* x, long ldx, float* y, long ldy, const signed char* next, int n_states, int* row_state,
+    const a2s_metre_ref* mt, int* choice_out, int R, int V);
+int a2s_metre_step_finalize_impl(hipStream_t st, const StepFinArgs& a, const a2s_grammar_ref& g, const a2s_metre_ref& mt);
+int a2s_metre_launches_impl(void);
 
 // ---- a2s_align.hip
 // n_done / n_rows_total (the decode loop's greedy calls, else null / 0): the launch is a no-op once every row has shown <eos>, as the step's attention

@@ -515,6 +515,7 @@ static int enqueue_query(hipStream_t st, const NoteDecArgs& a, int si, int sv) {
 // feature gets a field here, not another positional argument or another loop.
 struct NoteStepMode {
     const a2s_grammar_ref* grammar = nullptr;    // the epilogue: the constrained choice (a2s_grammar.hip) ...
+    const a2s_metre_ref* metre = nullptr;        // ... with the metre of the bar on top of it (grammar set too) ...
     const a2s_beam_args* beam = nullptr;         // ... the beam step (a2s_beam.hip), else the argmax epilogue
     const a2s_align_args* align = nullptr;       // the step's attention weights reduced into column t of the alignment arrays (a2s_align.hip)
     const int* t_base = nullptr;                 // graph replay: step index = t + *t_base
@@ -618,6 +619,7 @@ static int enqueue_note_step(hipStream_t st, const NoteDecArgs& a, const NoteSte
     f.t_base = m.t_base;
     f.row_until = a.n_active ? a.row_until : nullptr; f.n_clips = a.n_clips > 0 ? a.n_clips : a.R;
     f.R = a.R; f.V = a.V; f.E = a.E; f.t = t; f.teacher_force = k.tf; f.eos_id = a.eos_id; f.max_t = a.steps;
+    if (m.grammar && m.metre) return a2s_metre_step_finalize_impl(st, f, *m.grammar, *m.metre);
     if (m.grammar) return a2s_grammar_step_finalize_impl(st, f, *m.grammar);       // the constrained choice in the place of the argmax (a2s_grammar.hip)
     return a2s_note_step_finalize_impl(st, f);
 }
@@ -708,13 +710,13 @@ static int note_decoder_run(hipStream_t st, const NoteDecArgs& a, const NoteStep
 
 // The plain and the grammar entry: the two shortcuts around the loop, else the loop.  grammar: the constrained greedy decoder
 // (a2s_note_decoder_fwd_grammar_impl) -- never the persistent launch or the few-row kernels, every step's epilogue the grammar kernel.
-static int note_decoder_fwd(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar) {
+static int note_decoder_fwd(hipStream_t st, const NoteDecArgs& a, int* steps_done, const a2s_grammar_ref* grammar, const a2s_metre_ref* metre = nullptr) {
     // few clips: one persistent launch for the whole call (a2s_dec_persist.hip)
     if (!grammar && a2s_note_decoder_fwd_persist_ok(a)) return a2s_note_decoder_fwd_persist(st, a, steps_done);
     // stream capture is not allowed on the legacy default stream: callers that want the graph path run on a created stream
     if (!a.gt && a.use_graph && a.t_base && !a.gates && !a.attw && !a.drop && st != nullptr)
-        return note_decoder_greedy_graph(st, a, {.grammar = grammar, .t_base = a.t_base, .few_row = !grammar}, steps_done);
-    return note_decoder_run(st, a, {.grammar = grammar, .few_row = !grammar}, steps_done);
+        return note_decoder_greedy_graph(st, a, {.grammar = grammar, .metre = metre, .t_base = a.t_base, .few_row = !grammar}, steps_done);
+    return note_decoder_run(st, a, {.grammar = grammar, .metre = metre, .few_row = !grammar}, steps_done);
 }
 
 int a2s_note_decoder_fwd_impl(hipStream_t st, const NoteDecArgs& a, int* steps_done) { return note_decoder_fwd(st, a, steps_done, nullptr); }
@@ -726,6 +728,16 @@ int a2s_note_decoder_fwd_grammar_impl(hipStream_t st, const NoteDecArgs& a, cons
     A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_grammar: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
     A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_grammar: null bookkeeping or output buffers");
     return note_decoder_fwd(st, a, steps_done, &g);
+}
+
+// ... and under the metre of the bar: the same call, row r's metre state in mt->row_metre.
+int a2s_note_decoder_fwd_metre_impl(hipStream_t st, const NoteDecArgs& a, const a2s_grammar_ref& g, const a2s_metre_ref* mt, int* steps_done) {
+    A2S_REQUIRE(!a.gt && !a.tf_flags_dev, "note_decoder_fwd_metre: greedy decoding only (ground truth given)");
+    A2S_REQUIRE(!a.gates && !a.attw && !a.drop && !a.n_active && !a.row_list, "note_decoder_fwd_metre: inference only (training buffers or row bookkeeping given)");
+    A2S_REQUIRE(a2s_grammar_ref_ok(g, a.R, a.V), "note_decoder_fwd_metre: needs a table of 1..127 states, row states and V <= 256 (got %d states, V = %d)", g.n_states, a.V);
+    A2S_REQUIRE(mt && a2s_metre_ref_ok(*mt), "note_decoder_fwd_metre: needs the duration, class and fillable tables and the rows' metre states");
+    A2S_REQUIRE(a.R > 0 && a.steps >= 0 && a.n_done && a.eos_seen && a.lengths && a.logits && a.probs, "note_decoder_fwd_metre: null bookkeeping or output buffers");
+    return note_decoder_fwd(st, a, steps_done, &g, mt);
 }
 
 // Decoding with the audio alignment of every step: the launch-per-step loop -- greedy, greedy under a

@@ -300,6 +300,10 @@ class Engine:
         # forward `decoded` = {"up": (ids (B, bars, U) int32, lengths (B, bars) int64), "lo": ...}, None otherwise
         self.kern_grammar = None
         self.decoded = None
+        # kern_grammar.KernMetre or None (needs kern_grammar): greedy decoding also keeps every bar inside the metre of the time signature the bar-level
+        # head predicts for it (csrc/a2s_grammar.hip).  The heads of a bar are then issued before its note decoders; greedy and
+        # bar by bar only: with beam_size >= 2 or alignment the forward raises.  None (default): nothing of it is allocated, enqueued or read.
+        self.kern_metre = None
         # beam search over the note sequences of every (bar, staff) call: beam_size slots per clip, 1 .. 4; 1 = greedy, and
         # nothing of the beam path is touched.  With >= 2 the greedy, non-training calls keep each clip's best hypothesis under
         # score / len^beam_length_penalty; `decoded` is set as under the grammar (which composes with the beam) and
@@ -510,12 +514,13 @@ class Engine:
                                i64=ids_are_i64, hsave=hsave))
 
     def _decode_staff(self, S, prefix, keys, enc, h0, max_steps, probs_bar, gt_bar, steps, tf_flags, training, drop_p, B, T, attn_ws=None, gemm_ws=None,
-                      active=None, drop=None, flags_dev=None, persist=False, defer_launch=False):
+                      active=None, drop=None, flags_dev=None, persist=False, defer_launch=False, ts_ids=None):
         """One NoteDecoder.decode_notes call over B rows.  probs_bar: view (B, max_steps, V) of the output tensor (strided).
         tf_flags: per step, bit g = teacher-force the rows of group g.
         active: optional dict(until: (B,) int32, order / rank: (n_clips,) int32 device tensors; n_active: host int array per step;
         n_clips) -- the rows are B/n_clips fused bars of the same clips and row r's attention is skipped from step until[r] on (see
-        Engine.forward: skip_finished_rows / fuse_bars)."""
+        Engine.forward: skip_finished_rows / fuse_bars).
+        ts_ids: (B,) int32 device tensor, the time-signature id of every row's bar -- the call decodes under Engine.kern_metre."""
         L = hip.lib()
         H, E, V = self.cfg["hidden_size"], self.cfg["note_emb_size"], VOCAB_SIZE
         H2, ldx = 2 * H, E + 2 * H
@@ -628,6 +633,14 @@ class Engine:
             saved["align"] = at
             if row_state is not None:
                 saved["row_state"] = row_state
+            return ids_, lengths_, saved
+        if grammar is not None and ts_ids is not None:
+            row_state = torch.full((B,), grammar.start, dtype=torch.int32, device=dev)
+            row_metre = hip.metre_rows(self.kern_metre, ts_ids)
+            hip.check(L.a2s_note_decoder_fwd_metre(hip.stream(), C.byref(a), hip._p(grammar.device_table(dev)), grammar.n_states, hip._p(row_state),
+                                                   *hip.metre_ref(self.kern_metre, row_metre), C.byref(done)), "a2s_note_decoder_fwd_metre")
+            ids_, lengths_, saved = finish(done.value)
+            saved["row_state"], saved["row_metre"] = row_state, row_metre
             return ids_, lengths_, saved
         if grammar is not None:
             row_state = torch.full((B,), grammar.start, dtype=torch.int32, device=dev)
@@ -826,6 +839,15 @@ class Engine:
         beam = gt_cpu is None and not training and self._beam_slots() > 0
         greedy_graph = gt_cpu is None and not training and getattr(self, "greedy_graph", _GREEDY_GRAPH) and not beam and not align
         constrained = (self.kern_grammar is not None or beam) and gt_cpu is None and not training     # (the persistent decoder's epilogue holds its own argmax)
+        # the metre on top of the grammar: greedy calls only, each bar's heads before its note decoders
+        metrical = self.kern_metre is not None and gt_cpu is None and not training
+        if metrical:
+            if self.kern_grammar is None:
+                raise hip.A2SError("Engine.kern_metre needs Engine.kern_grammar: the metre is a predicate on top of the token grammar")
+            if self.kern_metre.grammar.vocab_size != self.kern_grammar.vocab_size:
+                raise hip.A2SError("Engine.kern_metre and Engine.kern_grammar are tables over different vocabularies")
+            if beam or align:
+                raise hip.A2SError("Engine.kern_metre decodes greedily: beam search (beam_size >= 2) and alignment do not carry a row's metre state yet")
         # the two staves of a segment run on two streams, each issued by its own host thread -- also in greedy decoding, where each
         # thread polls the done counter of its own stream (the hipGraph variant captures on one created stream and stays sequential)
         concurrent = getattr(self, "concurrent_staves", True) and not greedy_graph
@@ -1003,6 +1025,11 @@ class Engine:
                         rec["teacher_force"] = True
                 h0 = bar_saved[seg[0]]["hnew"] if nb == 1 else torch.cat([bar_saved[bar]["hnew"] for bar in seg], dim=0)
                 R = nb * Bg
+                if metrical:
+                    # the note decoders read the bar's time signature: its heads first, on this stream, which the staves' streams wait for
+                    # (the heads depend only on `headin`: the four outputs do not change)
+                    assert nb == 1
+                    bar_saved[seg[0]]["heads"] = bar_heads(seg[0], bar_saved[seg[0]]["headin"])
                 # (2) note decoders of the segment (models.py:261-275)
                 staff = {}
                 calls = []
@@ -1020,7 +1047,8 @@ class Engine:
                     # the dropout masks are drawn here, on the caller's thread and stream: one deterministic draw order per seed
                     drop = (rand((steps + 1, R, E)) >= 0.1).to(torch.uint8) if drop_on else None
                     calls.append((name, (S, prefix, keys_g[prefix], enc_g, h0, maxs, probs, gt_bar, steps, flags, training, 0.1 if drop_on else 0.0, R, T,
-                                         attn_ws[gi_idx], gemm_ws[gi_idx], active, drop, flags_dev, persist_g)))
+                                         attn_ws[gi_idx], gemm_ws[gi_idx], active, drop, flags_dev, persist_g) +
+                                  ((False, bar_saved[seg[0]]["heads"]["time_sig_out"][3]) if metrical else ())))
                 if concurrent_g and seg_plan[seg_i].get("pair") is not None:
                     _trace(f"g{gidx} seg {seg_i} staves forked (one loop)")
                     pair_join = fork_on_streams(dev, [streams[1]], [lambda cs=[args for _, args in calls], pr=seg_plan[seg_i]["pair"]: self._decode_pair(cs, streams, pr)])
@@ -1050,7 +1078,8 @@ class Engine:
                     join = lambda res=res: res
                 # (3) heads do not depend on the note decoders: they overlap with them on the main stream
                 for bar in seg:
-                    bar_saved[bar]["heads"] = bar_heads(bar, bar_saved[bar]["headin"])
+                    if not metrical:
+                        bar_saved[bar]["heads"] = bar_heads(bar, bar_saved[bar]["headin"])
                 _trace(f"g{gidx} seg {seg_i} heads issued, joining")
                 for (name, _), (ids, lengths, sv) in zip(calls, join()):     # the next token / next bar may read what the staves produced
                     sv["groups"] = nb

@@ -211,6 +211,43 @@ def grammar_launches():
     return int(lib().a2s_grammar_launches())
 
 
+def metre_ref(metre, row_metre):
+    """The metre reference of a kern_grammar.KernMetre and the rows' metre states row_metre (R, 16) int32 on the device (updated in place), as the
+    entry points take it: [dur_ticks, cls, fillable, n_fillable, row_metre]."""
+    if row_metre.dtype != torch.int32 or row_metre.dim() != 2 or row_metre.shape[1] != 16 or not row_metre.is_contiguous():
+        raise A2SError("metre_ref: expects the metre states as a contiguous (R, 16) int32 tensor")
+    tb = metre.device_tables(row_metre.device)           # (kept alive by the KernMetre)
+    return [_p(tb["dur_ticks"]), _p(tb["cls"]), _p(tb["fillable"]), tb["fillable"].numel(), _p(row_metre)]
+
+
+def metre_rows(metre, ts_ids):
+    """Fresh metre states (R, 16) int32 for rows whose bars have the time-signature ids ts_ids (R,) on the device; an id outside the list of
+    time signatures gives L = 0, an unmetred row.  Nothing is read back."""
+    ticks = metre.device_tables(ts_ids.device)["bar_ticks"]
+    ids = ts_ids.long()
+    rows = torch.zeros((ids.shape[0], 16), dtype=torch.int32, device=ts_ids.device)
+    rows[:, 0] = torch.where((ids >= 0) & (ids < ticks.numel()), ticks[ids.clamp(0, ticks.numel() - 1)], torch.zeros_like(ticks[:1]))
+    rows[:, 2] = 1
+    return rows
+
+
+def metre_argmax_rows(x, table, row_state, metre, row_metre, y=None, V=None):
+    """a2s_metre_argmax_rows: grammar_argmax_rows under the metre of kern_grammar.KernMetre `metre`; row_metre (R, 16) int32 is updated in place."""
+    V = table.shape[1] if V is None else V
+    R = x.shape[0]
+    if table.dtype != torch.int8 or row_state.dtype != torch.int32 or x.dtype != torch.float32 or not table.is_contiguous() or row_metre.shape[0] != R:
+        raise A2SError("metre_argmax_rows: expects float32 logits, a contiguous int8 table, int32 row states and one metre state per row")
+    choice = torch.empty(R, dtype=torch.int32, device=x.device)
+    check(lib().a2s_metre_argmax_rows(stream(), _p(x), x.stride(0), _p(y), y.stride(0) if y is not None else 0, _p(table), table.shape[0], _p(row_state),
+                                      *metre_ref(metre, row_metre), _p(choice), R, V), "a2s_metre_argmax_rows")
+    return choice
+
+
+def metre_launches():
+    """Metre step epilogues the library has launched in this process (a2s_metre_launches)."""
+    return int(lib().a2s_metre_launches())
+
+
 def beam_buffers(B, K, max_steps, V, device, pad_id, table=None, start=0, alpha=0.0):
     """The buffers of one beam-search call (a2s_beam_args) over B clips with K slots: -> (BeamArgs, dict of the tensors it points to).  Scores,
     finished flags and counters are those of the start: slot 0 alive at 0, the others dead; a2s_note_decoder_fwd_beam sets them again itself."""

@@ -124,6 +124,12 @@ class ASR(sb.Brain):
         v = getattr(self.hparams, "constrained_decoding", False)
         return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
 
+    def _metrical(self):
+        """--metrical_decoding=true (an optional override as --constrained_decoding, which it implies): VALID / TEST decode under the kern token grammar
+        AND the metre of the time signature predicted for each bar."""
+        v = getattr(self.hparams, "metrical_decoding", False)
+        return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
     def _beam_size(self):
         """--beam_size=K (an optional override as --constrained_decoding): VALID / TEST decode by beam search with K hypotheses per clip; 1 = greedy."""
         return int(getattr(self.hparams, "beam_size", 1))
@@ -163,6 +169,16 @@ class ASR(sb.Brain):
     def _set_constrained_decoding(self):
         self._set_beam()
         self._set_alignment()
+        if self._metrical():
+            model = self.modules.transcription
+            model = getattr(model, "module", model)                  # (a DistributedDataParallel wrapper)
+            if not hasattr(model, "metrical_decoding"):
+                raise ValueError(f"--metrical_decoding needs a transcription module that decodes under the metre; {type(model).__name__} has no "
+                                 "`metrical_decoding` attribute")
+            if self._beam_size() >= 2 or self._alignment():
+                raise ValueError("--metrical_decoding decodes greedily: it does not combine with --beam_size >= 2 or --alignment")
+            model.metrical_decoding = True
+            return
         if not self._constrained():
             return
         model = self.modules.transcription
@@ -259,7 +275,7 @@ class ASR(sb.Brain):
     def _record_predictions(self, predictions, targets, names, versions):
         ts_o, key_o, up_o, lo_o = predictions
         ts_t, key_t, up_t, lo_t = targets
-        if self._constrained() or self._beam_size() >= 2:
+        if self._constrained() or self._metrical() or self._beam_size() >= 2:
             # the ids the constrained / beam decoder EMITTED (the log-probabilities stay the unconstrained ones, their argmax is not what was decoded)
             model = self.modules.transcription
             decoded = getattr(model, "module", model).last_decoded
@@ -396,6 +412,14 @@ class ASR(sb.Brain):
         key_f1, key_f1_d = metrics.corpus_f1(self.key_pred, self.key_target)
         time_f1, time_f1_d = metrics.corpus_f1(self.time_sig_pred, self.time_sig_target)
         stats.update(key_f1=key_f1, time_f1=time_f1, WER_upper=wer_up, WER_lower=wer_lo, WER=(wer_up + wer_lo) / 2)
+        if hasattr(self.hparams, "metrical_decoding"):
+            # share of the decoded bars (both staves) that are complete under the time signature predicted for them -- for whatever decoder ran:
+            # --metrical_decoding=false reports it for the run's other settings (host side; without the override the stats are as before)
+            from piano_a2s_amd import kern_grammar
+            if not hasattr(self, "_kern_metre"):
+                self._kern_metre = kern_grammar.KernMetre()
+            both = {(cid, staff): rows for staff, pred in (("up", self.upper_pred), ("lo", self.lower_pred)) for cid, rows in pred.items()}
+            stats["complete_bars"] = kern_grammar.complete_share(both, {k: self.time_sig_pred[k[0]] for k in both}, self._kern_metre)
         notes_d = None
         if self._note_metrics():
             notes_up, notes_up_d = metrics.corpus_note_f1(self.upper_pred, self.upper_target)

@@ -72,7 +72,7 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     recording's own features (piano_a2s_amd.beats; beats_per_bar 2, 3 or 4 fixes the meter) and then used as if they had been
     given; the result gains "tracking": {"beats_s", "downbeats_s", "beats_per_bar", "period_frames"}.
     -> {"sample_rate_in", "sample_rate", "frames_per_second", "windows": [{"start_s", "stop_s", "n_bars", "flags", "time_signature", "key",
-        "bars": [{"upper", "lower", "upper_ids", "lower_ids"}], ["alignment"]}]};  time_signature and key hold one entry per kept bar (key as in the
+        "bars": [{"upper", "lower", "upper_ids", "lower_ids", ["complete": with `metrical_decoding`]}], ["alignment"]}]};  time_signature and key hold one entry per kept bar (key as in the
         recipe's result files: class - 6), bars the first n_bars decoded bars."""
     check_downbeats(downbeats, beats_per_bar)
     core = getattr(model, "module", model)
@@ -102,7 +102,8 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
             with torch.no_grad():
                 ts_o, key_o, up_o, lo_o = model(spectrogram=feats[w0:w0 + int(batch_size)], inference=True, ground_truth=None, teacher_forcing_ratio=0.,
                                                 device=device)
-            if getattr(core, "constrained_decoding", False) or int(getattr(core, "beam_size", 1)) >= 2:
+            metrical = bool(getattr(core, "metrical_decoding", False))
+            if getattr(core, "constrained_decoding", False) or metrical or int(getattr(core, "beam_size", 1)) >= 2:
                 # the ids the constrained / beam decoder EMITTED (the log-probabilities stay the unconstrained ones)
                 up_ids, lo_ids = core.last_decoded["up"][0].cpu().numpy(), core.last_decoded["lo"][0].cpu().numpy()
             else:
@@ -119,6 +120,12 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
                        "time_signature": [ts_list[int(i)] for i in ts_ids[b][:n_bars]], "key": [int(i) - 6 for i in key_ids[b][:n_bars]],
                        "bars": [{"upper": metrics.ids_to_text([u], inv), "lower": metrics.ids_to_text([l], inv), "upper_ids": u.tolist(), "lower_ids": l.tolist()}
                                 for u, l in zip(up, lo)]}
+                if metrical:
+                    # both staves of the bar end in <eos> with every spine at the length of the bar's time signature
+                    km, eos = core._kern_metre(), core._kern_grammar().eos
+                    for i, bar in enumerate(win["bars"]):
+                        rows = (up_ids[b][i].tolist(), lo_ids[b][i].tolist())
+                        bar["complete"] = all(eos in r and km.complete(r, int(ts_ids[b][i])) for r in rows)
                 if al is not None:
                     win["alignment"] = _alignment_record(al, b, start / rate, fps, up, lo)
                 result["windows"].append(win)
@@ -192,6 +199,8 @@ def main(argv):
     ap.add_argument("--hop_seconds", type=float, default=None)
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--constrained_decoding", action="store_true", help="decode under the kern token grammar")
+    ap.add_argument("--metrical_decoding", action="store_true", help="decode under the grammar and the metre of each bar's predicted time signature; "
+                    'every bar of the output gains "complete"')
     ap.add_argument("--beam_size", type=int, default=1, help="1 .. 4 hypotheses per clip, 1 = greedy")
     ap.add_argument("--beam_length_penalty", type=float, default=0.0)
     ap.add_argument("--alignment", action="store_true", help="also report where in the recording every decoded bar and token lies")
@@ -205,12 +214,15 @@ def main(argv):
         overrides[k] = yaml.safe_load(v)
     if not 1 <= a.beam_size <= 4:
         ap.error(f"--beam_size must be in 1 .. 4 (got {a.beam_size})")
+    if a.metrical_decoding and (a.beam_size >= 2 or a.alignment):
+        ap.error("--metrical_decoding decodes greedily: it does not combine with --beam_size >= 2 or --alignment")
     if len(a.audio) > 1 and a.downbeats:
         ap.error("--downbeats belongs to one recording")
     if a.beats_per_bar is not None and not a.track_downbeats:
         ap.error("--beats_per_bar belongs to --track_downbeats")
     model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
     model.constrained_decoding, model.alignment = bool(a.constrained_decoding), bool(a.alignment)
+    model.metrical_decoding = bool(a.metrical_decoding)
     model.beam_size, model.beam_length_penalty = a.beam_size, a.beam_length_penalty
     downbeats = read_downbeats(a.downbeats) if a.downbeats else ("track" if a.track_downbeats else None)
     os.makedirs(a.out, exist_ok=True)

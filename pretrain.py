@@ -5,7 +5,7 @@
 Same command line, yaml keys and recipe hooks as the reference's pretrain.py (:251-305); the recipe class lives in
 piano_a2s_amd/recipe.py.  ``--synthetic_clips=N`` trains on N seeded synthetic clips instead of a rendered corpus; with
 ``--synthetic_scores=rendered`` their audio is the sound of their (well-formed) score, synthesised on the GPU.  Optional overrides of the
-VALID / TEST decoder: ``--constrained_decoding=true`` (kern grammar), ``--beam_size=K [--beam_length_penalty=A]`` (beam search, K in 1 .. 4); of their scoring: ``--note_metrics=true`` (note-level F1 beside the WER).  Optional override of the TRAIN stage:
+VALID / TEST decoder: ``--constrained_decoding=true`` (kern grammar), ``--metrical_decoding=true`` (the grammar and the metre of each bar's predicted time signature; the stats gain ``complete_bars``), ``--beam_size=K [--beam_length_penalty=A]`` (beam search, K in 1 .. 4); of their scoring: ``--note_metrics=true`` (note-level F1 beside the WER).  Optional override of the TRAIN stage:
 ``--transpose_augment=K [--detune_bins=D]`` (every clip transposed by -K .. K semitones, K in 0 .. 6, and detuned by up to D feature bins, D <= 2.5, on the GPU),
 ``--tempo_augment=R`` (every clip played 1 - R .. 1 + R times as slowly, R <= 0.25, its content kept inside the window; the features are time-stretched on the GPU, the score stays),
 ``--eq_augment_db=E --noise_augment_db="(lo, hi)" --mask_time=Wt --mask_freq=Wf [--mask_count=m]`` (the colour of the recording, each part on its own: an equaliser curve of at most
