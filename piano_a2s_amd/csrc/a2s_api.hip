@@ -116,6 +116,7 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "attn_dk_ahead_launches")) return (int)a2s_attn_dk_ahead_launches();
     if (!strcmp(key, "attn_denc_launches")) return (int)a2s_attn_denc_launches();
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
+    if (!strcmp(key, "dec_cmb_launches")) return a2s_dec_cmb_launches();
     if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
     if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
     if (!strcmp(key, "conv_rows16_c20_launches")) return (int)a2s_conv_rows16_c20_launches();

@@ -205,6 +205,7 @@ long a2s_attn_pair_bwd_launches(void);
 size_t a2s_note_step_fused_head_floats(void);
 size_t a2s_note_step_workspace_floats_impl(int H, int E);
 int a2s_dec_mid_launches(void);
+int a2s_dec_cmb_launches(void);
 bool a2s_dec_step_fusable(int R, int H, int E, int V, const void* const* ptrs, int nptrs, const float* ws, size_t ws_floats, bool greedy = false);
 int a2s_note_step_fused_fwd(hipStream_t st, const a2s_note_dec_args& a, int si, int so, int sv, int sv_next, int t, const int* t_base, int tf, bool last,
     int nrows, const int* rowmap, const a2s_attn_deferred* defer = nullptr);

@@ -878,6 +878,8 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // measurements, tests: the bulk calls' per-step products then run as library-style launches, the few-row path on the 16-row kernels only).
 static int g_dec_mid_launches = 0;          // dec_gru_mid / dec_bwd_mid launches of this process (tests: proof of the path taken)
 int a2s_dec_mid_launches(void) { return g_dec_mid_launches; }
+static int g_dec_cmb_launches = 0;          // dec_gru_step_cmb launches of this process (tests: the deferred combine ran inside the GRU step)
+int a2s_dec_cmb_launches(void) { return g_dec_cmb_launches; }
 static bool dec_use_mid(int nrows, int H2) { return a2s_sw(A2S_SW_dec_mid) && nrows > 160 && H2 % MID_KC == 0; }
 // greedy: the call is a greedy decode (no ground truth, no backward).  There the 4-launch step wins at every batch size the workspace admits
 // (B = 256: 497 -> 536 clips/s, B = 64: 313 -> 317, profiles/r05_infer_variants.txt) -- one stream decodes a staff, nothing runs beside it that
@@ -914,6 +916,7 @@ int a2s_note_step_fused_fwd(hipStream_t st, const a2s_note_dec_args& a, int si, 
         c.G = defer->G; c.groups = defer->groups; c.n_clips = defer->n_clips; c.n_active = defer->n_active; c.step = defer->step; c.T = defer->T;
         c.Rall = R; c.E = a.E;
         hipLaunchKernelGGL(dec_gru_step_cmb, dim3(H2 / 16, a2s_cdiv(nrows, 16)), dim3(64 * NW), dec_cmb_lds_bytes(nrows < 16 ? nrows : 16), st, g, c);
+        __atomic_fetch_add(&g_dec_cmb_launches, 1, __ATOMIC_RELAXED);
     } else
     if (dec_use_mid(nrows, H2)) { hipLaunchKernelGGL(dec_gru_mid, dim3(H2 / 16, a2s_cdiv(nrows, 64)), dim3(256), 0, st, g); __atomic_fetch_add(&g_dec_mid_launches, 1, __ATOMIC_RELAXED); }
     else hipLaunchKernelGGL(dec_gru_step, dim3(H2 / 16, a2s_cdiv(nrows, 16)), dim3(64 * NW), 0, st, g);

@@ -1,6 +1,7 @@
 """The persistent few-clip note decoder (csrc/a2s_dec_persist.hip: one launch per NoteDecoder.decode_notes call, one clip per XCD) against
 the launch-per-step kernels it replaces: same inputs through both, every output and every per-step tensor the backward pass reads.
-(Against the reference itself the path is covered by the full-size golden tests -- g2 / g3 run B <= 4 clips, i.e. through this path.)"""
+(Against an independent reference: tests/test_gpu_note_decoder_call.py holds one persistent call -- 1, 6, 15 and 40 rows, T 37 / 38 / 39 / 1201 -- to the float64
+oracle of the call, tensor by tensor; the full-size golden tests g2 / g3 run B <= 4 clips, i.e. through this path, against the reference at model level.)"""
 import random
 
 import pytest
