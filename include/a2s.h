@@ -579,6 +579,25 @@ int a2s_tempogram(void* stream, const float* env, long stride, const int* n, int
 int a2s_beat_dp(void* stream, const float* ls, long stride, const int* period, int J, int hop_b, const float* pen, int lag_min, int lag_max, const int* n,
                 int R, float* S, int* back, int* beats, int max_beats, int* count);
 int a2s_beat_launches(void);
+/* ---- agreement of two feature tensors, segment by segment (csrc/a2s_agree.hip): what the resynthesis of a decoded score is
+ * compared with the recording by (piano_a2s_amd/resynth.py).  x, y: device, B clips of T rows of F float32 each, rows contiguous, clip b at
+ * + b * clip_stride (the same layout for both); seg: device, S x 4 int32 = [clip, f0, f1, 0]; out: device, S x 5 doubles.  Over the cells
+ * x[clip][f0:f1][0:F] of segment s and the same cells of y,
+ *     out[s] = [sum x, sum y, sum x^2, sum y^2, sum x y].
+ * A clip outside [0, B) gives five zeros; f0 and f1 are clamped to [0, T] and an empty range gives five zeros.  Segments may overlap, repeat and come
+ * in any order.  Nothing outside a clip's T * F cells is read (the stride padding may hold NaN) and nothing outside out[0 : 5 S] is written.
+ * Summation: the segment's run of n = (f1 - f0) * F cells is cut into chunks of 8192 cells; inside a chunk each of 256 lanes keeps fp32 partial sums
+ * over at most a2s_agreement_partial_cells() = 32 cells; everything above the lane partials is added in double, in an order that n alone fixes
+ * (the lanes by a tree, chunk c into slot c mod 64 in ascending order, the slots in ascending order).  A segment's five doubles are therefore
+ * bit-identical from run to run and do not depend on S, on its place in the table, on B, on T or on the other segments; inputs on a grid of 1/8 in
+ * [0, 1] give the exact sums.  16-byte loads where F % 4 == 0, clip_stride % 4 == 0 and x and y are 16-byte aligned, 4-byte loads otherwise (the two
+ * paths give a lane different cells, so the bits depend on which one runs).  No float atomics.  Two launches per 2048 segments; the slots are a device
+ * array of the library's own, so calls that may overlap must be on one stream.  The entry point allocates nothing, does not synchronise and reads
+ * nothing back.  Null pointers, B, T or F < 1, S < 0, clip_stride < T * F: A2S_ERR_ARG, nothing is launched; S = 0 returns 0 and launches nothing.
+ * a2s_agreement_launches: launches so far (proof of the path). */
+int a2s_segment_agreement(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, double* out);
+int a2s_agreement_launches(void);
+int a2s_agreement_partial_cells(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -193,6 +193,13 @@ def plan_flags(n_samples, sr=16000, downbeats=None, window_seconds=12.0, hop_sec
     return [w[3] for w in _plan(n_samples, sr, downbeats, window_seconds, hop_seconds, max_bars, max_samples)]
 
 
+def plan_bar_lines(n_samples, sr=16000, downbeats=None, window_seconds=12.0, hop_seconds=None, max_bars=5, max_samples=None):
+    """Per window of plan_windows its n_bars + 1 bar lines, in samples from the window's start: strictly ascending, the first 0, the last stop - start
+    (for a "bar_cut" window: [0, the window's length], the one bar ends where the window does).  Without downbeats the bars have no position: None per
+    window."""
+    return [w[4] for w in _plan(n_samples, sr, downbeats, window_seconds, hop_seconds, max_bars, max_samples)]
+
+
 def _plan(n_samples, sr, downbeats, window_seconds, hop_seconds, max_bars, max_samples):
     n_samples, max_bars = int(n_samples), int(max_bars)
     limit = min(int(round(float(window_seconds) * sr)), int(max_samples) if max_samples is not None else 12 * int(sr))
@@ -206,7 +213,7 @@ def _plan(n_samples, sr, downbeats, window_seconds, hop_seconds, max_bars, max_s
         start = 0
         while start < n_samples:
             stop = min(start + limit, n_samples)
-            out.append((start, stop, max_bars, ["short"] if stop - start < limit else []))
+            out.append((start, stop, max_bars, ["short"] if stop - start < limit else [], None))
             if stop == n_samples:
                 break
             start += hop
@@ -226,7 +233,8 @@ def _plan(n_samples, sr, downbeats, window_seconds, hop_seconds, max_bars, max_s
         stop, flags = db[i + keep], []
         if stop - db[i] > limit:                                            # (keep == 1: one bar longer than the window)
             stop, flags = db[i] + limit, ["bar_cut"]
-        out.append((db[i], stop, keep, flags))
+        lines = [t - db[i] for t in db[i:i + keep]] + [stop - db[i]]        # (ascending: the loop above keeps non-empty bars only)
+        out.append((db[i], stop, keep, flags, lines))
         i += keep
     return out
 

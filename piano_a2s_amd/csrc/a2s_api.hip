@@ -324,6 +324,11 @@ int a2s_beat_dp(void* stream, const float* ls, long stride, const int* period, i
     return a2s_beat_dp_impl(ST, ls, stride, period, J, hop_b, pen, lag_min, lag_max, n, R, S, back, beats, max_beats, count);
 }
 int a2s_beat_launches(void) { return a2s_beat_launches_impl(); }
+int a2s_segment_agreement(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, double* out) {
+    return a2s_segment_agreement_impl(ST, x, y, clip_stride, B, T, F, seg, S, out);
+}
+int a2s_agreement_launches(void) { return a2s_agreement_launches_impl(); }
+int a2s_agreement_partial_cells(void) { return a2s_agreement_partial_cells_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

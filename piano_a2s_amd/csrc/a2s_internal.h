@@ -336,6 +336,11 @@ int a2s_beat_dp_impl(hipStream_t st, const float* ls, long stride, const int* pe
                      const int* n, int R, float* S, int* back, int* beats, int max_beats, int* count);
 int a2s_beat_launches_impl(void);
 
+// ---- a2s_agree.hip
+int a2s_segment_agreement_impl(hipStream_t st, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, double* out);
+int a2s_agreement_launches_impl(void);
+int a2s_agreement_partial_cells_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 from .abi import PROTOTYPES, STRUCTS, A2SError          # the ABI as include/a2s.h declares it; the package's one error type
@@ -748,6 +749,60 @@ def beat_dp(ls, period, pen, n, hop_b=100, lag_min=20, max_beats=None, S=None, b
 def beat_launches():
     """Launches of the three beat-tracking kernels in this process (a2s_beat_launches)."""
     return int(lib().a2s_beat_launches())
+
+
+def segment_agreement(x, y, seg):
+    """a2s_segment_agreement: x, y float32 tensors of one shape (B, T, F) or (B, 1, T, F) on the device, unit stride along F, rows contiguous (row
+    stride F; the clips may lie further apart, both tensors with the same clip stride); seg: the HOST table, anything numpy reads as whole numbers of
+    shape (S, 3) [clip, f0, f1] or (S, 4) -> (S, 5) float64 on the device: [sum x, sum y, sum x^2, sum y^2, sum x y] over x[clip][f0:f1][:].
+    The table is checked here, before it is uploaded: 0 <= clip < B and 0 <= f0 <= f1 <= T (an empty range is allowed and gives zeros)."""
+    fn = "segment_agreement"
+    for name, t in (("x", x), ("y", y)):
+        _need(torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)), fn, name,
+              "must be a float32 tensor (B, T, F) or (B, 1, T, F) on the device")
+    if x.dim() == 4:
+        x = x[:, 0]
+    if y.dim() == 4:
+        y = y[:, 0]
+    _need(x.shape == y.shape and x.device == y.device, fn, "y", f"must have x's shape and device (got {tuple(y.shape)} for {tuple(x.shape)})")
+    B, T, F = x.shape
+    _need(not torch.is_tensor(seg) or not seg.is_cuda, fn, "seg", "is the host table (it is checked before it is uploaded)")
+    try:
+        table = np.asarray(seg.numpy() if torch.is_tensor(seg) else seg)
+        whole = table.size == 0 or (np.issubdtype(table.dtype, np.integer) or bool(np.all(table == np.rint(table))))
+    except (TypeError, ValueError):
+        table, whole = None, False
+    _need(whole, fn, "seg", "must hold whole numbers")
+    table = table.reshape(0, 4) if table.size == 0 else table
+    _need(table.ndim == 2 and table.shape[1] in (3, 4), fn, "seg", f"must be (S, 3) or (S, 4) (got {table.shape})")
+    S = table.shape[0]
+    out = torch.zeros((S, 5), dtype=torch.float64, device=x.device)
+    if S == 0:
+        return out
+    _need(B >= 1 and T >= 1 and F >= 1, fn, "x", f"has no cells (shape {tuple(x.shape)}) but the table has segments")
+    t64 = table[:, :3].astype(np.int64)
+    bad = np.nonzero((t64[:, 0] < 0) | (t64[:, 0] >= B) | (t64[:, 1] < 0) | (t64[:, 1] > t64[:, 2]) | (t64[:, 2] > T))[0]
+    _need(bad.size == 0, fn, "seg", f"row {int(bad[0]) if bad.size else 0} = {t64[bad[0]].tolist() if bad.size else []} is outside 0 <= clip < {B}, 0 <= f0 <= f1 <= {T}")
+    strides = []
+    for name, t in (("x", x), ("y", y)):
+        _need((t.stride(2) == 1 or F == 1) and (t.stride(1) == F or T == 1), fn, name, f"must have contiguous rows (strides {tuple(t.stride())})")
+        strides.append(t.stride(0) if B > 1 else T * F)
+    _need(strides[0] == strides[1] and strides[0] >= T * F, fn, "y", f"must have x's clip stride, at least T * F (got {strides[1]} and {strides[0]})")
+    host = np.zeros((S, 4), dtype=np.int32)
+    host[:, :3] = t64
+    dev = torch.from_numpy(host).to(x.device)
+    check(lib().a2s_segment_agreement(stream(), _p(x), _p(y), strides[0], B, T, F, _p(dev), S, _p(out)), "a2s_segment_agreement")
+    return out
+
+
+def agreement_launches():
+    """Launches of the two agreement kernels in this process (a2s_agreement_launches)."""
+    return int(lib().a2s_agreement_launches())
+
+
+def agreement_partial_cells():
+    """The most cells one fp32 partial sum of a2s_segment_agreement covers (a2s_agreement_partial_cells); everything above is added in double."""
+    return int(lib().a2s_agreement_partial_cells())
 
 
 def note_match(ref, ref_off, hyp, hyp_off, n_pairs, dur_ticks, midi, cls, out):

@@ -63,7 +63,7 @@ def check_downbeats(downbeats, beats_per_bar):
         raise ValueError(f"transcribe: beats_per_bar must be 2, 3 or 4 (got {beats_per_bar!r})")
 
 
-def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams):
+def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
@@ -73,8 +73,18 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     given; the result gains "tracking": {"beats_s", "downbeats_s", "beats_per_bar", "period_frames"}.
     -> {"sample_rate_in", "sample_rate", "frames_per_second", "windows": [{"start_s", "stop_s", "n_bars", "flags", "time_signature", "key",
         "bars": [{"upper", "lower", "upper_ids", "lower_ids", ["complete": with `metrical_decoding`]}], ["alignment"]}]};  time_signature and key hold one entry per kept bar (key as in the
-        recipe's result files: class - 6), bars the first n_bars decoded bars."""
+        recipe's result files: class - 6), bars the first n_bars decoded bars.
+    resynthesis=True (needs downbeats, given or tracked: without them the bars have no position, ValueError): the decoded score is played back on
+    piano_a2s_amd.resynth's instrument and compared with the recording bar by bar, whatever the decoding mode -- only the
+    emitted ids and the predicted time signatures are read.  Every bar gains "agreement" (the Pearson correlation of the recording's and the
+    resynthesis's features over the bar's frames, in [-1, 1]; None for a window without a note and for a bar in which nothing sounds) and "notes" ([[onset_s, length_s, midi]] in
+    recording time), every window "agreement" (the mean over its bars that have one, or None) and the flag "notes_truncated" where its notes did not
+    fit a render program; the result gains "resynthesis": {"sample_rate", "wave": float32 numpy (N,)}, the windows' renders overlap-added at their
+    starts (release tails included up to the render length), as long as the recording at the model's rate.  Off, nothing of this is allocated,
+    launched or returned."""
     check_downbeats(downbeats, beats_per_bar)
+    if resynthesis and downbeats is None:
+        raise ValueError("transcribe: resynthesis needs downbeats (given or tracked): in fixed windows the decoded bars have no position in the audio")
     core = getattr(model, "module", model)
     device = next(core.parameters()).device
     hop = int(_hp(hparams, "hop_length", 160))
@@ -91,6 +101,9 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     result = {"sample_rate_in": int(sr), "sample_rate": rate, "frames_per_second": fps, "windows": []}
     if tracking is not None:
         result["tracking"] = tracking
+    if resynthesis:
+        from . import resynth
+        result["resynthesis"] = {"sample_rate": rate, "wave": np.zeros(wave.shape[0], dtype=np.float32)}
     if not plan:
         return result
     feats = _vqt(device, hparams)(audio.cut_windows(wave, plan, length))
@@ -112,7 +125,8 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
             al = None
             if getattr(core, "alignment", False) and core.last_alignment is not None:
                 al = {k: {f: t.cpu().numpy() for f, t in v.items()} for k, v in core.last_alignment.items()}
-            for b, (start, stop, n_bars, flags) in enumerate(plan[w0:w0 + int(batch_size)]):
+            batch = []
+            for b, (start, stop, n_bars, flags, lines) in enumerate(plan[w0:w0 + int(batch_size)]):
                 n_bars = min(n_bars, up_ids.shape[1])
                 up = [metrics.unpad(r) for r in up_ids[b][:n_bars]]
                 lo = [metrics.unpad(r) for r in lo_ids[b][:n_bars]]
@@ -129,9 +143,35 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
                 if al is not None:
                     win["alignment"] = _alignment_record(al, b, start / rate, fps, up, lo)
                 result["windows"].append(win)
+                batch.append((win, start, lines, up, lo))
+            if resynthesis:
+                _resynthesise_batch(resynth, batch, feats[w0:w0 + int(batch_size)], _vqt(device, hparams), hop, rate, result["resynthesis"]["wave"])
     finally:
         model.train(was_training)
     return result
+
+
+def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total):
+    """The resynthesis of one batch of windows [(window dict, start sample, bar lines, upper rows, lower rows)]: fills the windows' and bars' new keys
+    and adds the renders into `total` (the recording-long waveform) at the windows' starts."""
+    windows = []
+    for win, start, lines, up, lo in batch:
+        lines = lines[:win["n_bars"] + 1]
+        events, truncated = resynth.score_events(up, lo, win["time_signature"], lines)
+        if truncated:
+            win["flags"].append("notes_truncated")
+        for i, bar in enumerate(win["bars"]):
+            notes, _ = resynth.score_events(up[i:i + 1], lo[i:i + 1], win["time_signature"][i:i + 1], lines[i:i + 2], max_events=1 << 30)
+            bar["notes"] = [[(start + int(o)) / rate, int(n) / rate, int(m)] for o, n, m in notes]
+        windows.append({"events": events, "bar_lines": lines})
+    waves, agreements = resynth.resynthesise(windows, feats, vqt, hop)
+    for (win, start, *_), w, agr in zip(batch, waves, agreements):
+        for bar, a in zip(win["bars"], agr):
+            bar["agreement"] = a
+        win["agreement"] = resynth.mean_agreement(agr)
+        if w is not None and start < len(total):
+            n = min(len(w), len(total) - start)
+            total[start:start + n] += w[:n]
 
 
 def _alignment_record(al, b, start_s, fps, up, lo):
@@ -204,6 +244,9 @@ def main(argv):
     ap.add_argument("--beam_size", type=int, default=1, help="1 .. 4 hypotheses per clip, 1 = greedy")
     ap.add_argument("--beam_length_penalty", type=float, default=0.0)
     ap.add_argument("--alignment", action="store_true", help="also report where in the recording every decoded bar and token lies")
+    ap.add_argument("--resynthesis", action="store_true", help="play the decoded score back and compare it with the recording bar by bar: every bar gains "
+                    '"agreement" and "notes", and DIR/NAME.resynth.wav holds the recording (left) beside the resynthesis (right), 16 bits, for A/B listening; '
+                    "needs --downbeats or --track_downbeats")
     ap.add_argument("--device", default="cuda:0")
     a, extra = ap.parse_known_args(argv)
     overrides = {}
@@ -220,6 +263,8 @@ def main(argv):
         ap.error("--downbeats belongs to one recording")
     if a.beats_per_bar is not None and not a.track_downbeats:
         ap.error("--beats_per_bar belongs to --track_downbeats")
+    if a.resynthesis and not (a.downbeats or a.track_downbeats):
+        ap.error("--resynthesis needs --downbeats or --track_downbeats: in fixed windows the decoded bars have no position in the audio")
     model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
     model.constrained_decoding, model.alignment = bool(a.constrained_decoding), bool(a.alignment)
     model.metrical_decoding = bool(a.metrical_decoding)
@@ -229,9 +274,16 @@ def main(argv):
     for path in a.audio:
         x, sr = audio.read_wav(path)
         result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
-                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp)
+                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
+        if a.resynthesis:
+            # the wave goes to a file of its own, not into the JSON: left the recording at the model's rate, right the resynthesis
+            res = result.pop("resynthesis")
+            rec = to_16k(x, sr, torch.device(a.device), hp)[0].cpu().numpy()
+            wav = out[:-len(".json")] + ".resynth.wav"
+            audio.write_wav(wav, np.stack([rec, res["wave"][:len(rec)]], axis=1), res["sample_rate"], bits=16)
+            result["resynthesis"] = {"sample_rate": res["sample_rate"], "file": os.path.basename(wav)}
         with open(out, "w") as f:
             json.dump(result, f, indent=1)
         print(f"{path}: {len(result['windows'])} windows -> {out}")

@@ -1,13 +1,15 @@
 """Is the rendered synthetic corpus learnable, and what do the decoders make of it?  (needs the GPU.)
 
-    python tools/rendered_corpus_eval.py --model small|full --steps N [--batch B] [--frames F] [--eval_clips M] [--note_metrics]
+    python tools/rendered_corpus_eval.py --model small|full --steps N [--batch B] [--frames F] [--eval_clips M] [--note_metrics] [--resynthesis]
                                          [--out profiles/rendered_corpus.json]
 
 1. trains on rendered clips (datasets.syn.RenderedClips, fresh clips every step) for N fused optimizer steps -- once with every clip's own audio and
    once, as the control, from the same initial weights with the audio permuted among the clips of each batch (uninformative audio);
 2. on held-out rendered clips reports per-staff WER and key / time-signature F1 of greedy, grammar-constrained and beam (K = 2, 4) decoding with the
    share of well-formed bars, for both models; with --note_metrics also the note-level F1 (pitch / onset / value, metrics.corpus_note_f1: DESIGN.md
-   section 17) of every decoding mode beside its WER;
+   section 17) of every decoding mode beside its WER; with --resynthesis also the mean bar agreement (piano_a2s_amd.resynth) of the
+   decoded scores with the audio they were decoded from, beside that of the ground-truth scores of that audio (the ceiling); the control run gives the
+   agreement of scores decoded from uninformative audio;
 3. reports the mean absolute difference between the forced-alignment centroids (teacher-forced forward over the true score) and the true onsets;
 4. writes the JSON.
 No threshold is applied to anything: the file records what the run shows.
@@ -68,6 +70,30 @@ def _unpad_rows(ids):
     return [metrics.unpad(r).tolist() for r in ids]
 
 
+def _bar_lines(clip, bars):
+    from fractions import Fraction
+    from piano_a2s_amd import scoregen
+    bar_q = Fraction(scoregen._BAR_UNITS[clip["time_sig"]], 4)
+    return [int(clip["lead"] + b * bar_q * clip["spq"]) for b in range(bars + 1)]
+
+
+def _batch_agreement(ds, first, heard, feats, front, up_ids, lo_ids, ts_ids):
+    """Bar agreements of one evaluation batch: clip b of the batch was decoded from the audio of clip first + heard[b] of `ds` (features feats[b]), so
+    its decoded bars are laid on THAT clip's bar lines -> (agreements of the decoded scores, of the heard clips' own scores), None entries dropped."""
+    from piano_a2s_amd import resynth, scoregen
+    sigs = scoregen.time_signatures()
+    dec, gt = [], []
+    for b, h in enumerate(heard):
+        clip = ds.clip(first + h)
+        bars = len(clip["ids"]["upper"])
+        lines = _bar_lines(clip, bars)
+        ev = resynth.score_events(_unpad_rows(up_ids[b]), _unpad_rows(lo_ids[b]), [sigs[int(t)] for t in ts_ids[b]], lines)[0]
+        dec.append({"events": ev, "bar_lines": lines})
+        gt.append({"events": resynth.score_events(clip["ids"]["upper"], clip["ids"]["lower"], [clip["time_sig"]] * bars, lines)[0], "bar_lines": lines})
+    flat = lambda w: [a for row in resynth.resynthesise(w, feats, front, scoregen.HOP)[1] for a in row]
+    return flat(dec), flat(gt)
+
+
 def _decode(model, ds, args, dev, front, permute, constrained, K):
     from data_processing.humdrum import LabelsMultiple
     from piano_a2s_amd import kern_grammar, metrics
@@ -76,6 +102,7 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
     model.constrained_decoding, model.beam_size, model.alignment = constrained, K, False
     pred = {k: {} for k in ("up", "lo", "key", "ts")}
     target = {k: {} for k in ("up", "lo", "key", "ts")}
+    agr_dec, agr_gt, first = [], [], 0
     with torch.no_grad():
         for batch in _batches(ds, args.eval_batch, 0):
             f = _features(batch, dev, front, permute)
@@ -84,6 +111,13 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
                 up_ids, lo_ids = model.last_decoded["up"][0].cpu().numpy(), model.last_decoded["lo"][0].cpu().numpy()
             else:
                 up_ids, lo_ids = up_o.argmax(-1).cpu().numpy(), lo_o.argmax(-1).cpu().numpy()
+            if args.resynthesis:
+                n = len(batch[7])
+                heard = [(b - 1) % n if permute else b for b in range(n)]          # (_features rolls the audio by one clip)
+                d, g = _batch_agreement(ds, first, heard, f[0], front, up_ids, lo_ids, ts_o.argmax(-1).cpu().numpy())
+                agr_dec += d
+                agr_gt += g
+                first += n
             for b, name in enumerate(batch[7]):
                 pred["up"][name], target["up"][name] = _unpad_rows(up_ids[b]), _unpad_rows(batch[3][b].numpy())
                 pred["lo"][name], target["lo"][name] = _unpad_rows(lo_ids[b]), _unpad_rows(batch[5][b].numpy())
@@ -99,6 +133,10 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
             out.update({f"note_f1_{level}_{staff}": means[f"f1_{level}"] for level in ("pitch", "onset", "value")})
             out[f"spelled_share_{staff}"], out[f"overflow_rows_{staff}"] = means["spelled_share"], means["overflow_rows"]
         out["note_f1"] = (out["note_f1_onset_upper"] + out["note_f1_onset_lower"]) / 2
+    if args.resynthesis:
+        from piano_a2s_amd import resynth
+        out["bar_agreement_decoded"], out["bar_agreement_ground_truth"] = resynth.mean_agreement(agr_dec), resynth.mean_agreement(agr_gt)
+        out["bars"], out["bars_without_agreement_decoded"] = len(agr_dec), sum(a is None for a in agr_dec)
     return out
 
 
@@ -177,6 +215,7 @@ def main():
     ap.add_argument("--log_every", type=int, default=10)
     ap.add_argument("--no_control", action="store_true")
     ap.add_argument("--note_metrics", action="store_true")
+    ap.add_argument("--resynthesis", action="store_true")
     ap.add_argument("--room", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -190,7 +229,7 @@ def main():
     train_set = RenderedClips(cfg, args.steps * args.batch, seed=args.seed, frames=args.frames)
     held_out = RenderedClips(cfg, args.eval_clips, seed=args.seed + 10_000_000, frames=args.frames)
     res = {"model": args.model, "cfg": {k: cfg[k] for k in ("hidden_size", "conv_feature_size", "max_length", "max_bars")}, "steps": args.steps,
-           "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "note_metrics": args.note_metrics, "runs": {}}
+           "batch": args.batch, "frames": args.frames, "eval_clips": args.eval_clips, "teacher_forcing": args.teacher_forcing, "note_metrics": args.note_metrics, "resynthesis": args.resynthesis, "runs": {}}
     torch.manual_seed(args.seed)
     init = {k: v.clone() for k, v in models.ScoreTranscription(**cfg).state_dict().items()}
     if args.room:
