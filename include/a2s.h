@@ -598,6 +598,39 @@ int a2s_beat_launches(void);
 int a2s_segment_agreement(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, double* out);
 int a2s_agreement_launches(void);
 int a2s_agreement_partial_cells(void);
+/* ---- dynamic time warping of two feature tensors, segment by segment (csrc/a2s_dtw.hip): where inside its bar the resynthesis
+ * of a decoded score is heard in the recording.  x, y, clip_stride, B, T, F: as for a2s_segment_agreement.  seg: device, S x 4 int32 =
+ * [clip, f0, f1, r]; f0 and f1 are clamped to [0, T], n = f1 - f0 rows, the same rows of both tensors; r is the Sakoe-Chiba half-width: cell (i, j),
+ * 0 <= i, j < n, is inside the band when |i - j| <= r, and r < 0 or r >= n means no band.  A clip outside [0, B) and an empty range give an empty
+ * segment.  Segments may overlap, repeat and come in any order.
+ * Buffers: n_max >= the longest segment, r_max >= the widest band (r_max < 0: some segment has none); w_max = n_max where r_max < 0 or
+ * 2 r_max + 1 > n_max, else 2 r_max + 1.  The block of segment s starts at element s * n_max * w_max of the cost buffer (float32) and of the
+ * workspace (one byte per cell), and holds, with W = 2 r + 1 where the segment has a band and 2 r + 1 < n, W = n otherwise,
+ *     W < n:   n rows of W cells, cell (i, j) at i * W + (j - i + r)           (banded);
+ *     W = n:   n rows of n cells, cell (i, j) at i * n + j                     (dense; cells outside a band are neither written nor read).
+ * A segment with n > n_max or W > w_max does not fit and is treated as empty.  a2s_dtw_cost_bytes / a2s_dtw_workspace_bytes: the bytes both need.
+ * a2s_dtw_cost: d[s][i][j] = sum_f e^2, e = (x[clip][f0 + i][f] - y[clip][f0 + j][f]) - off[s]; fp32, one chain per cell in ascending f,
+ * acc = fmaf(e, e, acc).  off: device, S floats, NULL = 0 (the subtraction is then left out; e - 0 is e).  Only cells inside the band are computed.
+ * Inputs on a grid of 1/8 in [0, 1] with off = 0 and F <= 2^18 give exact sums.  16-byte loads where F % 4 == 0, clip_stride % 4 == 0 and x and y are
+ * 16-byte aligned, 4-byte loads otherwise; the arithmetic is the same on both paths.  Nothing outside a clip's T * F cells is read (the stride padding
+ * may hold NaN).  One launch per 32768 segments.
+ * a2s_dtw_path: D[0][0] = d[0][0], D[i][j] = d[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) over the predecessors that exist and lie in the band;
+ * among equals the first in that order wins.  One fp32 addition per cell, no multiply: a float32 restatement on the same costs gives the same bits
+ * and the same path.  path: S rows of 2 n_max - 1 int32; row s receives steps[s] <= 2 n - 1 entries (i << 16) | j from (0, 0) to (n - 1, n - 1),
+ * ascending; entries behind steps[s] are not written.  total[s] = D[n-1][n-1].  An empty segment gives steps = 0 and total = 0 and writes nothing
+ * else.  The direction of every cell goes to the workspace; what is read back from it is clamped before it steers the walk, and the walk ends after
+ * 2 n - 1 cells whatever the workspace holds.  One launch per call, one workgroup per segment.
+ * Both: a segment's results do not depend on S, on its place in the table, on B, on T or on the other segments, and are bit-identical from run to
+ * run.  No atomics.  The entry points allocate nothing, do not synchronise and read nothing back.  Null pointers (off excepted), B, T or F < 1,
+ * T > 4096, S < 0, clip_stride < T * F, n_max outside [1, T], a cost buffer or workspace smaller than the bytes above: A2S_ERR_ARG, nothing is
+ * launched; S = 0 returns 0 and launches nothing.  a2s_dtw_launches: launches of the two kernels so far (proof of the path). */
+size_t a2s_dtw_cost_bytes(int S, int n_max, int r_max);
+size_t a2s_dtw_workspace_bytes(int S, int n_max, int r_max);
+int a2s_dtw_cost(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, const float* off, int n_max,
+                 int r_max, float* cost, size_t cost_bytes);
+int a2s_dtw_path(void* stream, const int* seg, int S, int B, int T, int n_max, int r_max, const float* cost, size_t cost_bytes, uint8_t* ws,
+                 size_t ws_bytes, int* path, int* steps, float* total);
+int a2s_dtw_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -176,6 +176,59 @@ def write_wav(path, x, sr, bits=16):
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+MIDI_TICKS_PER_QUARTER = 500
+MIDI_TEMPO_US = 500000          # per quarter: with 500 ticks per quarter one tick is one millisecond
+
+
+def _vlq(n):
+    """A MIDI variable-length quantity: 7 bits per byte, most significant first, the top bit set on every byte but the last."""
+    out = [n & 0x7F]
+    n >>= 7
+    while n:
+        out.append(0x80 | (n & 0x7F))
+        n >>= 7
+    return bytes(reversed(out))
+
+
+def midi_bytes(notes, velocity=64):
+    """notes [[onset_s, length_s, midi]] -> a Standard MIDI File, format 0: one track on channel 0, MIDI_TICKS_PER_QUARTER ticks per quarter at
+    MIDI_TEMPO_US microseconds per quarter, so a tick is 1 ms; every note at `velocity`.  Onset and end are rounded to ticks and a note lasts at
+    least one; at equal times the note-offs come first, then by pitch.  Onsets before 0 and pitches outside 0 .. 127 are ValueErrors."""
+    events = []
+    for onset, length, midi in notes:
+        on = int(round(float(onset) * 1e6 * MIDI_TICKS_PER_QUARTER / MIDI_TEMPO_US))
+        off = max(on + 1, int(round((float(onset) + float(length)) * 1e6 * MIDI_TICKS_PER_QUARTER / MIDI_TEMPO_US)))
+        if on < 0 or not 0 <= int(midi) <= 127 or int(midi) != midi:
+            raise ValueError(f"write_midi: not a note: onset {onset!r} s, pitch {midi!r}")
+        events += [(on, 1, int(midi)), (off, 0, int(midi))]
+    events.sort()
+    track, now = b"\x00\xff\x51\x03" + MIDI_TEMPO_US.to_bytes(3, "big"), 0
+    for tick, is_on, midi in events:
+        track += _vlq(tick - now) + bytes([0x90 if is_on else 0x80, midi, int(velocity)])
+        now = tick
+    track += b"\x00\xff\x2f\x00"
+    return b"MThd" + struct.pack(">IHHH", 6, 0, 1, MIDI_TICKS_PER_QUARTER) + b"MTrk" + struct.pack(">I", len(track)) + track
+
+
+def write_midi(path, notes, velocity=64):
+    """midi_bytes(notes) to a file.  notes: [[onset_s, length_s, midi]], or a result of transcribe_waveform (result_notes)."""
+    if not 1 <= int(velocity) <= 127:
+        raise ValueError(f"write_midi: velocity must be in 1 .. 127 (got {velocity!r})")
+    data = midi_bytes(result_notes(notes) if isinstance(notes, dict) else notes, velocity)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def result_notes(result):
+    """The notes of a transcription result in recording time: every bar's "performed" where it has one (align_notes), its "notes" otherwise
+    (resynthesis); bars without either give nothing."""
+    out = []
+    for win in result.get("windows", []):
+        for bar in win.get("bars", []):
+            out += [list(n) for n in bar.get("performed", bar.get("notes", []))]
+    return out
+
+
 # ------------------------------------------------------------------------------------------- windows
 def plan_windows(n_samples, sr=16000, downbeats=None, window_seconds=12.0, hop_seconds=None, max_bars=5, max_samples=None):
     """The clips a recording of n_samples is cut into: [(start, stop, n_bars)] in samples, each at most min(window_seconds * sr, max_samples) long

@@ -329,6 +329,17 @@ int a2s_segment_agreement(void* stream, const float* x, const float* y, long cli
 }
 int a2s_agreement_launches(void) { return a2s_agreement_launches_impl(); }
 int a2s_agreement_partial_cells(void) { return a2s_agreement_partial_cells_impl(); }
+size_t a2s_dtw_cost_bytes(int S, int n_max, int r_max) { return a2s_dtw_cost_bytes_impl(S, n_max, r_max); }
+size_t a2s_dtw_workspace_bytes(int S, int n_max, int r_max) { return a2s_dtw_workspace_bytes_impl(S, n_max, r_max); }
+int a2s_dtw_cost(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, const float* off, int n_max,
+                 int r_max, float* cost, size_t cost_bytes) {
+    return a2s_dtw_cost_impl(ST, x, y, clip_stride, B, T, F, seg, S, off, n_max, r_max, cost, cost_bytes);
+}
+int a2s_dtw_path(void* stream, const int* seg, int S, int B, int T, int n_max, int r_max, const float* cost, size_t cost_bytes, uint8_t* ws,
+                 size_t ws_bytes, int* path, int* steps, float* total) {
+    return a2s_dtw_path_impl(ST, seg, S, B, T, n_max, r_max, cost, cost_bytes, ws, ws_bytes, path, steps, total);
+}
+int a2s_dtw_launches(void) { return a2s_dtw_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

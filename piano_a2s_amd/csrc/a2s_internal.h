@@ -341,6 +341,15 @@ int a2s_segment_agreement_impl(hipStream_t st, const float* x, const float* y, l
 int a2s_agreement_launches_impl(void);
 int a2s_agreement_partial_cells_impl(void);
 
+// ---- a2s_dtw.hip
+size_t a2s_dtw_cost_bytes_impl(int S, int n_max, int r_max);
+size_t a2s_dtw_workspace_bytes_impl(int S, int n_max, int r_max);
+int a2s_dtw_cost_impl(hipStream_t st, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* seg, int S, const float* off,
+                      int n_max, int r_max, float* cost, size_t cost_bytes);
+int a2s_dtw_path_impl(hipStream_t st, const int* seg, int S, int B, int T, int n_max, int r_max, const float* cost, size_t cost_bytes, unsigned char* ws,
+                      size_t ws_bytes, int* path, int* steps, float* total);
+int a2s_dtw_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -756,7 +756,21 @@ def segment_agreement(x, y, seg):
     stride F; the clips may lie further apart, both tensors with the same clip stride); seg: the HOST table, anything numpy reads as whole numbers of
     shape (S, 3) [clip, f0, f1] or (S, 4) -> (S, 5) float64 on the device: [sum x, sum y, sum x^2, sum y^2, sum x y] over x[clip][f0:f1][:].
     The table is checked here, before it is uploaded: 0 <= clip < B and 0 <= f0 <= f1 <= T (an empty range is allowed and gives zeros)."""
-    fn = "segment_agreement"
+    x, y, (B, T, F), t64, stride = _segment_operands("segment_agreement", x, y, seg)
+    S = t64.shape[0]
+    out = torch.zeros((S, 5), dtype=torch.float64, device=x.device)
+    if S == 0:
+        return out
+    host = np.zeros((S, 4), dtype=np.int32)
+    host[:, :3] = t64[:, :3]
+    dev = torch.from_numpy(host).to(x.device)
+    check(lib().a2s_segment_agreement(stream(), _p(x), _p(y), stride, B, T, F, _p(dev), S, _p(out)), "a2s_segment_agreement")
+    return out
+
+
+def _segment_operands(fn, x, y, seg):
+    """The checks a2s_segment_agreement and the DTW entry points share -> (x and y as (B, T, F) views, (B, T, F), the host table as int64 (S, 3 or 4),
+    the clip stride -- None where S == 0: an empty table asks nothing of the tensors' cells)."""
     for name, t in (("x", x), ("y", y)):
         _need(torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)), fn, name,
               "must be a float32 tensor (B, T, F) or (B, 1, T, F) on the device")
@@ -775,24 +789,94 @@ def segment_agreement(x, y, seg):
     _need(whole, fn, "seg", "must hold whole numbers")
     table = table.reshape(0, 4) if table.size == 0 else table
     _need(table.ndim == 2 and table.shape[1] in (3, 4), fn, "seg", f"must be (S, 3) or (S, 4) (got {table.shape})")
-    S = table.shape[0]
-    out = torch.zeros((S, 5), dtype=torch.float64, device=x.device)
-    if S == 0:
-        return out
+    t64 = table.astype(np.int64)
+    if t64.shape[0] == 0:
+        return x, y, (B, T, F), t64, None
     _need(B >= 1 and T >= 1 and F >= 1, fn, "x", f"has no cells (shape {tuple(x.shape)}) but the table has segments")
-    t64 = table[:, :3].astype(np.int64)
     bad = np.nonzero((t64[:, 0] < 0) | (t64[:, 0] >= B) | (t64[:, 1] < 0) | (t64[:, 1] > t64[:, 2]) | (t64[:, 2] > T))[0]
-    _need(bad.size == 0, fn, "seg", f"row {int(bad[0]) if bad.size else 0} = {t64[bad[0]].tolist() if bad.size else []} is outside 0 <= clip < {B}, 0 <= f0 <= f1 <= {T}")
+    _need(bad.size == 0, fn, "seg", f"row {int(bad[0]) if bad.size else 0} = {t64[bad[0], :3].tolist() if bad.size else []} is outside 0 <= clip < {B}, 0 <= f0 <= f1 <= {T}")
     strides = []
     for name, t in (("x", x), ("y", y)):
         _need((t.stride(2) == 1 or F == 1) and (t.stride(1) == F or T == 1), fn, name, f"must have contiguous rows (strides {tuple(t.stride())})")
         strides.append(t.stride(0) if B > 1 else T * F)
     _need(strides[0] == strides[1] and strides[0] >= T * F, fn, "y", f"must have x's clip stride, at least T * F (got {strides[1]} and {strides[0]})")
-    host = np.zeros((S, 4), dtype=np.int32)
-    host[:, :3] = t64
-    dev = torch.from_numpy(host).to(x.device)
-    check(lib().a2s_segment_agreement(stream(), _p(x), _p(y), strides[0], B, T, F, _p(dev), S, _p(out)), "a2s_segment_agreement")
-    return out
+    return x, y, (B, T, F), t64, strides[0]
+
+
+DTW_T_MAX = 4096          # the longest clip a2s_dtw_cost / a2s_dtw_path take (csrc/a2s_dtw.hip)
+
+
+def dtw_geometry(table):
+    """(n_max, r_max) that hold every row [clip, f0, f1, r] of the int64 host table: the buffers of a2s_dtw_cost / a2s_dtw_path are sized by them
+    (include/a2s.h).  r_max = -1 where the widest block is a full square."""
+    n = table[:, 2] - table[:, 1]
+    r = table[:, 3]
+    banded = (r >= 0) & (2 * r + 1 < n)
+    width = np.where(banded, 2 * r + 1, n)
+    n_max, need = max(1, int(n.max())), int(width.max())
+    return n_max, (-1 if need >= n_max else need // 2)
+
+
+def dtw_cost(x, y, seg, off=None):
+    """a2s_dtw_cost: x, y and the HOST table seg as for segment_agreement, the table (S, 4) [clip, f0, f1, r] (or (S, 3): no band), S >= 1; off None or
+    (S,) float32 on the device -> (cost: flat float32 device tensor in the block layout of include/a2s.h, zero where the kernel does not write, the
+    table on the device (S, 4) int32, (B, T, n_max, r_max))."""
+    fn = "dtw_cost"
+    x, y, (B, T, F), t64, stride = _segment_operands(fn, x, y, seg)
+    S = t64.shape[0]
+    _need(S >= 1, fn, "seg", "must hold at least one segment")
+    _need(T <= DTW_T_MAX, fn, "x", f"must have at most {DTW_T_MAX} rows per clip (got {T})")
+    host = np.full((S, 4), -1, dtype=np.int64)
+    host[:, :t64.shape[1]] = t64
+    _need(bool(np.all(np.abs(host[:, 3]) < 2 ** 31)), fn, "seg", "holds a band width that is no int32")
+    if off is not None:
+        _need(torch.is_tensor(off) and off.dtype == torch.float32 and off.device == x.device and tuple(off.shape) == (S,) and off.is_contiguous(), fn, "off",
+              f"must be a contiguous float32 tensor ({S},) on x's device")
+    n_max, r_max = dtw_geometry(host)
+    dev = torch.from_numpy(host.astype(np.int32)).to(x.device)
+    cost = torch.zeros(int(lib().a2s_dtw_cost_bytes(S, n_max, r_max)) // 4, dtype=torch.float32, device=x.device)
+    check(lib().a2s_dtw_cost(stream(), _p(x), _p(y), stride, B, T, F, _p(dev), S, None if off is None else _p(off), n_max, r_max, _p(cost), cost.numel() * 4),
+          "a2s_dtw_cost")
+    return cost, dev, (B, T, n_max, r_max)
+
+
+def dtw_path(cost, dev, geometry):
+    """a2s_dtw_path on what dtw_cost returned (or on any cost buffer of that layout) -> (paths (S, 2 n_max - 1) int32, -1 behind a row's steps; steps
+    (S,) int32; totals (S,) float32), on the device."""
+    fn = "dtw_path"
+    B, T, n_max, r_max = (int(v) for v in geometry)
+    _need(torch.is_tensor(dev) and dev.dtype == torch.int32 and dev.is_cuda and dev.dim() == 2 and dev.shape[1] == 4 and dev.is_contiguous(), fn, "dev",
+          "must be the contiguous int32 table (S, 4) on the device")
+    S = dev.shape[0]
+    need = int(lib().a2s_dtw_cost_bytes(S, n_max, r_max)) // 4
+    _need(torch.is_tensor(cost) and cost.dtype == torch.float32 and cost.device == dev.device and cost.is_contiguous() and cost.numel() >= need, fn, "cost",
+          f"must be a contiguous float32 tensor of at least {need} elements on the table's device")
+    ws = torch.zeros(int(lib().a2s_dtw_workspace_bytes(S, n_max, r_max)), dtype=torch.uint8, device=dev.device)
+    paths = torch.full((S, 2 * n_max - 1), -1, dtype=torch.int32, device=dev.device)
+    steps = torch.zeros((S,), dtype=torch.int32, device=dev.device)
+    totals = torch.zeros((S,), dtype=torch.float32, device=dev.device)
+    if S == 0:
+        return paths, steps, totals
+    check(lib().a2s_dtw_path(stream(), _p(dev), S, B, T, n_max, r_max, _p(cost), cost.numel() * 4, _p(ws), ws.numel(), _p(paths), _p(steps), _p(totals)),
+          "a2s_dtw_path")
+    return paths, steps, totals
+
+
+def dtw_segments(x, y, seg, off=None):
+    """Dynamic time warping of y onto x, segment by segment (a2s_dtw_cost, then a2s_dtw_path): x, y and the HOST table as for
+    segment_agreement, the table (S, 4) [clip, f0, f1, r] with the Sakoe-Chiba half-width r (r < 0 or r >= f1 - f0: no band; (S, 3): no band); off None
+    or (S,) float32 on the device, subtracted from every difference x - y of the segment -> (paths (S, 2 n_max - 1) int32, entry k of row s =
+    (i << 16) | j, ascending from (0, 0) to (n - 1, n - 1), -1 behind the row's steps; steps (S,) int32; totals (S,) float32), on the device."""
+    if _segment_operands("dtw_segments", x, y, seg)[3].shape[0] == 0:
+        return (torch.zeros((0, 1), dtype=torch.int32, device=x.device), torch.zeros((0,), dtype=torch.int32, device=x.device),
+                torch.zeros((0,), dtype=torch.float32, device=x.device))
+    cost, dev, geometry = dtw_cost(x, y, seg, off)
+    return dtw_path(cost, dev, geometry)
+
+
+def dtw_launches():
+    """Launches of the two DTW kernels in this process (a2s_dtw_launches)."""
+    return int(lib().a2s_dtw_launches())
 
 
 def agreement_launches():

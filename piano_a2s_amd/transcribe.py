@@ -63,7 +63,7 @@ def check_downbeats(downbeats, beats_per_bar):
         raise ValueError(f"transcribe: beats_per_bar must be 2, 3 or 4 (got {beats_per_bar!r})")
 
 
-def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False):
+def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False, align_notes=False):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
@@ -81,10 +81,16 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     recording time), every window "agreement" (the mean over its bars that have one, or None) and the flag "notes_truncated" where its notes did not
     fit a render program; the result gains "resynthesis": {"sample_rate", "wave": float32 numpy (N,)}, the windows' renders overlap-added at their
     starts (release tails included up to the render length), as long as the recording at the model's rate.  Off, nothing of this is allocated,
-    launched or returned."""
+    launched or returned.
+    align_notes=True (needs resynthesis, ValueError without): inside every bar the resynthesis is warped onto the recording (banded dynamic time
+    warping of the two feature tensors).  Every bar gains "agreement_warped" (the agreement with the resynthesis read along the
+    warp: timing no longer counts; None where "agreement" is None) and "performed" ([[onset_s, length_s, midi]]: the bar's "notes" with onset and end
+    moved through the bar's warp, clamped to the bar, at least one frame long), every window "agreement_warped" (the mean over its bars)."""
     check_downbeats(downbeats, beats_per_bar)
     if resynthesis and downbeats is None:
         raise ValueError("transcribe: resynthesis needs downbeats (given or tracked): in fixed windows the decoded bars have no position in the audio")
+    if align_notes and not resynthesis:
+        raise ValueError("transcribe: align_notes aligns the resynthesis with the recording: it needs resynthesis=True")
     core = getattr(model, "module", model)
     device = next(core.parameters()).device
     hop = int(_hp(hparams, "hop_length", 160))
@@ -145,16 +151,17 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
                 result["windows"].append(win)
                 batch.append((win, start, lines, up, lo))
             if resynthesis:
-                _resynthesise_batch(resynth, batch, feats[w0:w0 + int(batch_size)], _vqt(device, hparams), hop, rate, result["resynthesis"]["wave"])
+                _resynthesise_batch(resynth, batch, feats[w0:w0 + int(batch_size)], _vqt(device, hparams), hop, rate, result["resynthesis"]["wave"],
+                                    align=align_notes)
     finally:
         model.train(was_training)
     return result
 
 
-def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total):
+def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=False):
     """The resynthesis of one batch of windows [(window dict, start sample, bar lines, upper rows, lower rows)]: fills the windows' and bars' new keys
-    and adds the renders into `total` (the recording-long waveform) at the windows' starts."""
-    windows = []
+    and adds the renders into `total` (the recording-long waveform) at the windows' starts.  align: also the keys of align_notes."""
+    windows, bar_notes = [], []
     for win, start, lines, up, lo in batch:
         lines = lines[:win["n_bars"] + 1]
         events, truncated = resynth.score_events(up, lo, win["time_signature"], lines)
@@ -163,12 +170,22 @@ def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total):
         for i, bar in enumerate(win["bars"]):
             notes, _ = resynth.score_events(up[i:i + 1], lo[i:i + 1], win["time_signature"][i:i + 1], lines[i:i + 2], max_events=1 << 30)
             bar["notes"] = [[(start + int(o)) / rate, int(n) / rate, int(m)] for o, n, m in notes]
+            bar_notes.append(notes)
         windows.append({"events": events, "bar_lines": lines})
-    waves, agreements = resynth.resynthesise(windows, feats, vqt, hop)
-    for (win, start, *_), w, agr in zip(batch, waves, agreements):
-        for bar, a in zip(win["bars"], agr):
+    waves, agreements, *aligned = resynth.resynthesise(windows, feats, vqt, hop, align=align)
+    bar_notes = iter(bar_notes)
+    for k, ((win, start, lines, *_), w, agr) in enumerate(zip(batch, waves, agreements)):
+        for i, (bar, a) in enumerate(zip(win["bars"], agr)):
             bar["agreement"] = a
+            if align:
+                al = aligned[0][k][i]
+                bar["agreement_warped"] = None if al is None else al["agreement_warped"]
+                moved = resynth.performed_notes(next(bar_notes), None if al is None else al["warp"], 0 if al is None else al["first_frame"], hop,
+                                                lines[i], lines[i + 1])
+                bar["performed"] = [[(start + o) / rate, n / rate, m] for o, n, m in moved]
         win["agreement"] = resynth.mean_agreement(agr)
+        if align:
+            win["agreement_warped"] = resynth.mean_agreement([bar["agreement_warped"] for bar in win["bars"]])
         if w is not None and start < len(total):
             n = min(len(w), len(total) - start)
             total[start:start + n] += w[:n]
@@ -247,6 +264,9 @@ def main(argv):
     ap.add_argument("--resynthesis", action="store_true", help="play the decoded score back and compare it with the recording bar by bar: every bar gains "
                     '"agreement" and "notes", and DIR/NAME.resynth.wav holds the recording (left) beside the resynthesis (right), 16 bits, for A/B listening; '
                     "needs --downbeats or --track_downbeats")
+    ap.add_argument("--align_notes", action="store_true", help="implies --resynthesis: warp the resynthesis onto the recording inside every bar; every bar "
+                    'gains "agreement_warped" and "performed" (its notes where they are heard), and DIR/NAME.mid holds the performed notes as a '
+                    "Standard MIDI File (format 0, 1 ms ticks, velocity 64)")
     ap.add_argument("--device", default="cuda:0")
     a, extra = ap.parse_known_args(argv)
     overrides = {}
@@ -263,6 +283,7 @@ def main(argv):
         ap.error("--downbeats belongs to one recording")
     if a.beats_per_bar is not None and not a.track_downbeats:
         ap.error("--beats_per_bar belongs to --track_downbeats")
+    a.resynthesis = a.resynthesis or a.align_notes
     if a.resynthesis and not (a.downbeats or a.track_downbeats):
         ap.error("--resynthesis needs --downbeats or --track_downbeats: in fixed windows the decoded bars have no position in the audio")
     model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
@@ -274,7 +295,7 @@ def main(argv):
     for path in a.audio:
         x, sr = audio.read_wav(path)
         result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
-                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis)
+                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis, align_notes=a.align_notes)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
         if a.resynthesis:
@@ -284,6 +305,10 @@ def main(argv):
             wav = out[:-len(".json")] + ".resynth.wav"
             audio.write_wav(wav, np.stack([rec, res["wave"][:len(rec)]], axis=1), res["sample_rate"], bits=16)
             result["resynthesis"] = {"sample_rate": res["sample_rate"], "file": os.path.basename(wav)}
+        if a.align_notes:
+            mid = out[:-len(".json")] + ".mid"
+            audio.write_midi(mid, result)
+            result["performance"] = {"file": os.path.basename(mid)}
         with open(out, "w") as f:
             json.dump(result, f, indent=1)
         print(f"{path}: {len(result['windows'])} windows -> {out}")
