@@ -631,6 +631,34 @@ int a2s_dtw_cost(void* stream, const float* x, const float* y, long clip_stride,
 int a2s_dtw_path(void* stream, const int* seg, int S, int B, int T, int n_max, int r_max, const float* cost, size_t cost_bytes, uint8_t* ws,
                  size_t ws_bytes, int* path, int* steps, float* total);
 int a2s_dtw_launches(void);
+/* ---- note dynamics by analysis by synthesis (csrc/a2s_dynamics.hip): the two device stages between the VQT of a resynthesis and
+ * its next render (piano_a2s_amd/resynth.py: estimate_dynamics).  x, y, clip_stride, B, T, F: as for a2s_segment_agreement (x the recording's features,
+ * y the resynthesis's).  rows: device, S x 8 int32 = [clip, fx, fy, n, b1, b2, b3, prog_row], one row per note; the rows of one clip are contiguous and
+ * first (device, B + 1 int32, ascending from 0 to S) holds the clips' offsets.
+ * a2s_note_levels: the cells of a row are the frames i < n crossed with the columns b_h - 1 .. b_h + 1 of every b_h >= 0; a cell counts only if its
+ * column is in [0, F) and BOTH fx + i and fy + i are in [0, T):
+ *     out[s] = [sum x[clip][fx + i][col], sum y[clip][fy + i][col], count]          (three doubles).
+ * A clip outside [0, B) or n <= 0 gives three zeros; n above 64 is read as 64.  Rows may repeat and come in any order.  One wavefront per row, four rows
+ * per workgroup: cell k = 9 i + 3 (h - 1) + (col - b_h + 1) belongs to lane k mod 64, a lane adds its cells in ascending k in double, and the lanes are
+ * combined by a butterfly.  A row's three doubles are therefore bit-identical from run to run and do not depend on S, on the row's place, on B or on T
+ * (beyond which cells count); inputs on a grid of 1/8 give the exact sums.  Nothing outside a clip's T * F cells is read (the stride padding may hold
+ * NaN) and nothing outside out[0 : 3 S] is written.  No atomics.  One launch per call.  Null pointers, B, T or F < 1, S < 0, clip_stride < T * F:
+ * A2S_ERR_ARG, nothing is launched; S = 0 returns 0 and launches nothing.
+ * a2s_note_amp_update: per clip b over its k = first[b + 1] - first[b] rows (at most 512; a longer run is cut there), in fp32, one operation per step:
+ *     d = (float)(80.0 * (Sx - Sy) / count)   (the division in double; d = 0 where count = 0);        c = cum + d;
+ *     med = the lower median of c, the (k - 1) / 2-th smallest;                                          cum' = min(max(c - med, -30), 12);
+ *     word 3 (the amplitude) of row prog_row of clip b's program = base_amp * exp2f(cum' * (log2(10) / 20));   cum = cum'.
+ * A numpy float32 restatement on the same sums gives the same bits of cum.  programs: device, B programs of program_stride rows of 8 int32 each, as
+ * a2s_render_notes reads them (its rows_per_clip); only word 3 of the listed rows is written, never the header, and a clip without rows is left alone.
+ * The table lives on the device and the entry point reads nothing back, so a prog_row outside 1 .. program_stride - 1 cannot be refused here: the
+ * kernel writes no amplitude for such a row (its cum is still updated), and piano_a2s_amd.hip.note_table refuses it on the host table before
+ * anything is uploaded.  One workgroup per clip, the median by rank counting in LDS (rank = the smaller values + the equal values at a lower index).
+ * One launch per call.  Null pointers, B < 1 or > 65535, program_stride < 2, base_amp not in (0, 1e30]: A2S_ERR_ARG, nothing is launched.
+ * Both entry points allocate nothing, do not synchronise and read nothing back.  a2s_dynamics_launches: launches of the two so far (proof of the path). */
+int a2s_note_levels(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* rows, int S, double* out);
+int a2s_note_amp_update(void* stream, const double* sums, const int* rows, const int* first, int B, float* cum, int* programs, int program_stride,
+                        float base_amp);
+int a2s_dynamics_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

@@ -191,27 +191,33 @@ def _vlq(n):
 
 
 def midi_bytes(notes, velocity=64):
-    """notes [[onset_s, length_s, midi]] -> a Standard MIDI File, format 0: one track on channel 0, MIDI_TICKS_PER_QUARTER ticks per quarter at
-    MIDI_TEMPO_US microseconds per quarter, so a tick is 1 ms; every note at `velocity`.  Onset and end are rounded to ticks and a note lasts at
-    least one; at equal times the note-offs come first, then by pitch.  Onsets before 0 and pitches outside 0 .. 127 are ValueErrors."""
+    """notes [[onset_s, length_s, midi]] or [[onset_s, length_s, midi, velocity]] -> a Standard MIDI File, format 0: one track on channel 0,
+    MIDI_TICKS_PER_QUARTER ticks per quarter at MIDI_TEMPO_US microseconds per quarter, so a tick is 1 ms; a note without a velocity of its own (or
+    with None) gets `velocity`.  Onset and end are rounded to ticks and a note lasts at least one; at equal times the note-offs come first, then by
+    pitch.  Onsets before 0, pitches outside 0 .. 127 and velocities outside 1 .. 127 are ValueErrors."""
     events = []
-    for onset, length, midi in notes:
+    for onset, length, midi, *own in notes:
+        given = bool(own) and own[0] is not None
+        vel = own[0] if given else velocity
         on = int(round(float(onset) * 1e6 * MIDI_TICKS_PER_QUARTER / MIDI_TEMPO_US))
         off = max(on + 1, int(round((float(onset) + float(length)) * 1e6 * MIDI_TICKS_PER_QUARTER / MIDI_TEMPO_US)))
         if on < 0 or not 0 <= int(midi) <= 127 or int(midi) != midi:
             raise ValueError(f"write_midi: not a note: onset {onset!r} s, pitch {midi!r}")
-        events += [(on, 1, int(midi)), (off, 0, int(midi))]
+        if len(own) > 1 or (given and (int(vel) != vel or not 1 <= int(vel) <= 127)):
+            raise ValueError(f"write_midi: not a velocity in 1 .. 127: {own!r}")
+        events += [(on, 1, int(midi), int(vel)), (off, 0, int(midi), int(vel))]
     events.sort()
     track, now = b"\x00\xff\x51\x03" + MIDI_TEMPO_US.to_bytes(3, "big"), 0
-    for tick, is_on, midi in events:
-        track += _vlq(tick - now) + bytes([0x90 if is_on else 0x80, midi, int(velocity)])
+    for tick, is_on, midi, vel in events:
+        track += _vlq(tick - now) + bytes([0x90 if is_on else 0x80, midi, vel])
         now = tick
     track += b"\x00\xff\x2f\x00"
     return b"MThd" + struct.pack(">IHHH", 6, 0, 1, MIDI_TICKS_PER_QUARTER) + b"MTrk" + struct.pack(">I", len(track)) + track
 
 
 def write_midi(path, notes, velocity=64):
-    """midi_bytes(notes) to a file.  notes: [[onset_s, length_s, midi]], or a result of transcribe_waveform (result_notes)."""
+    """midi_bytes(notes) to a file.  notes: [[onset_s, length_s, midi]] or [[onset_s, length_s, midi, velocity]], or a result of transcribe_waveform
+    (result_notes)."""
     if not 1 <= int(velocity) <= 127:
         raise ValueError(f"write_midi: velocity must be in 1 .. 127 (got {velocity!r})")
     data = midi_bytes(result_notes(notes) if isinstance(notes, dict) else notes, velocity)
@@ -221,11 +227,15 @@ def write_midi(path, notes, velocity=64):
 
 def result_notes(result):
     """The notes of a transcription result in recording time: every bar's "performed" where it has one (align_notes), its "notes" otherwise
-    (resynthesis); bars without either give nothing."""
+    (resynthesis); bars without either give nothing.  A bar with "dynamics" gives every note its velocity as a fourth entry (where it has one), and
+    the notes a bar marks in "quiet" are left out."""
     out = []
     for win in result.get("windows", []):
         for bar in win.get("bars", []):
-            out += [list(n) for n in bar.get("performed", bar.get("notes", []))]
+            notes = [list(n) for n in bar.get("performed", bar.get("notes", []))]
+            if "dynamics" in bar:
+                notes = [n + [d[1]] if d[1] is not None else n for n, d in zip(notes, bar["dynamics"])]
+            out += [n for n, q in zip(notes, bar.get("quiet", [False] * len(notes))) if not q]
     return out
 
 

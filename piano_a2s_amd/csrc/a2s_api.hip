@@ -340,6 +340,14 @@ int a2s_dtw_path(void* stream, const int* seg, int S, int B, int T, int n_max, i
     return a2s_dtw_path_impl(ST, seg, S, B, T, n_max, r_max, cost, cost_bytes, ws, ws_bytes, path, steps, total);
 }
 int a2s_dtw_launches(void) { return a2s_dtw_launches_impl(); }
+int a2s_note_levels(void* stream, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* rows, int S, double* out) {
+    return a2s_note_levels_impl(ST, x, y, clip_stride, B, T, F, rows, S, out);
+}
+int a2s_note_amp_update(void* stream, const double* sums, const int* rows, const int* first, int B, float* cum, int* programs, int program_stride,
+                        float base_amp) {
+    return a2s_note_amp_update_impl(ST, sums, rows, first, B, cum, programs, program_stride, base_amp);
+}
+int a2s_dynamics_launches(void) { return a2s_dynamics_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

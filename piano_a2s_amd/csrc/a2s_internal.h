@@ -350,6 +350,12 @@ int a2s_dtw_path_impl(hipStream_t st, const int* seg, int S, int B, int T, int n
                       size_t ws_bytes, int* path, int* steps, float* total);
 int a2s_dtw_launches_impl(void);
 
+// ---- a2s_dynamics.hip
+int a2s_note_levels_impl(hipStream_t st, const float* x, const float* y, long clip_stride, int B, int T, int F, const int* rows, int S, double* out);
+int a2s_note_amp_update_impl(hipStream_t st, const double* sums, const int* rows, const int* first, int B, float* cum, int* programs, int rows_per_clip,
+                             float base_amp);
+int a2s_dynamics_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

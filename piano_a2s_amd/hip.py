@@ -768,9 +768,8 @@ def segment_agreement(x, y, seg):
     return out
 
 
-def _segment_operands(fn, x, y, seg):
-    """The checks a2s_segment_agreement and the DTW entry points share -> (x and y as (B, T, F) views, (B, T, F), the host table as int64 (S, 3 or 4),
-    the clip stride -- None where S == 0: an empty table asks nothing of the tensors' cells)."""
+def _feature_pair(fn, x, y):
+    """x, y: float32 tensors of one shape (B, T, F) or (B, 1, T, F) on one device -> both as (B, T, F) views."""
     for name, t in (("x", x), ("y", y)):
         _need(torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)), fn, name,
               "must be a float32 tensor (B, T, F) or (B, 1, T, F) on the device")
@@ -779,6 +778,24 @@ def _segment_operands(fn, x, y, seg):
     if y.dim() == 4:
         y = y[:, 0]
     _need(x.shape == y.shape and x.device == y.device, fn, "y", f"must have x's shape and device (got {tuple(y.shape)} for {tuple(x.shape)})")
+    return x, y
+
+
+def _clip_stride(fn, x, y):
+    """The clip stride two (B, T, F) views share: unit stride along F, rows contiguous, clips at least T * F apart."""
+    B, T, F = x.shape
+    strides = []
+    for name, t in (("x", x), ("y", y)):
+        _need((t.stride(2) == 1 or F == 1) and (t.stride(1) == F or T == 1), fn, name, f"must have contiguous rows (strides {tuple(t.stride())})")
+        strides.append(t.stride(0) if B > 1 else T * F)
+    _need(strides[0] == strides[1] and strides[0] >= T * F, fn, "y", f"must have x's clip stride, at least T * F (got {strides[1]} and {strides[0]})")
+    return strides[0]
+
+
+def _segment_operands(fn, x, y, seg):
+    """The checks a2s_segment_agreement and the DTW entry points share -> (x and y as (B, T, F) views, (B, T, F), the host table as int64 (S, 3 or 4),
+    the clip stride -- None where S == 0: an empty table asks nothing of the tensors' cells)."""
+    x, y = _feature_pair(fn, x, y)
     B, T, F = x.shape
     _need(not torch.is_tensor(seg) or not seg.is_cuda, fn, "seg", "is the host table (it is checked before it is uploaded)")
     try:
@@ -795,12 +812,7 @@ def _segment_operands(fn, x, y, seg):
     _need(B >= 1 and T >= 1 and F >= 1, fn, "x", f"has no cells (shape {tuple(x.shape)}) but the table has segments")
     bad = np.nonzero((t64[:, 0] < 0) | (t64[:, 0] >= B) | (t64[:, 1] < 0) | (t64[:, 1] > t64[:, 2]) | (t64[:, 2] > T))[0]
     _need(bad.size == 0, fn, "seg", f"row {int(bad[0]) if bad.size else 0} = {t64[bad[0], :3].tolist() if bad.size else []} is outside 0 <= clip < {B}, 0 <= f0 <= f1 <= {T}")
-    strides = []
-    for name, t in (("x", x), ("y", y)):
-        _need((t.stride(2) == 1 or F == 1) and (t.stride(1) == F or T == 1), fn, name, f"must have contiguous rows (strides {tuple(t.stride())})")
-        strides.append(t.stride(0) if B > 1 else T * F)
-    _need(strides[0] == strides[1] and strides[0] >= T * F, fn, "y", f"must have x's clip stride, at least T * F (got {strides[1]} and {strides[0]})")
-    return x, y, (B, T, F), t64, strides[0]
+    return x, y, (B, T, F), t64, _clip_stride(fn, x, y)
 
 
 DTW_T_MAX = 4096          # the longest clip a2s_dtw_cost / a2s_dtw_path take (csrc/a2s_dtw.hip)
@@ -877,6 +889,78 @@ def dtw_segments(x, y, seg, off=None):
 def dtw_launches():
     """Launches of the two DTW kernels in this process (a2s_dtw_launches)."""
     return int(lib().a2s_dtw_launches())
+
+
+NOTE_ROWS_MAX = 512          # note rows per clip a2s_note_amp_update takes (csrc/a2s_dynamics.hip)
+
+
+def note_table(rows, first, n_clips, program_rows, device):
+    """The HOST note table of the dynamics kernels, checked and uploaded once: rows (S, 8) whole numbers [clip, fx, fy, n, b1,
+    b2, b3, prog_row], first (n_clips + 1,) the clips' offsets; program_rows: rows of one render program, header included.  The rows of clip b are
+    rows[first[b]:first[b + 1]], at most NOTE_ROWS_MAX, every one with clip == b and 1 <= prog_row < program_rows (the update kernel cannot refuse a
+    row: it reads nothing back) -> (rows, first) as contiguous int32 tensors on `device`."""
+    fn = "note_table"
+    try:
+        r, f = np.asarray(rows), np.asarray(first)
+        whole = all(t.size == 0 or np.issubdtype(t.dtype, np.integer) or bool(np.all(t == np.rint(t))) for t in (r, f))
+    except (TypeError, ValueError):
+        r, f, whole = None, None, False
+    _need(whole, fn, "rows", "and `first` must hold whole numbers")
+    r = r.reshape(0, 8) if r.size == 0 else r
+    _need(r.ndim == 2 and r.shape[1] == 8 and bool(np.all(np.abs(r.astype(np.int64)) < 2 ** 31)), fn, "rows", f"must be (S, 8) int32 values (got {r.shape})")
+    r, f = r.astype(np.int64), f.astype(np.int64).reshape(-1)
+    S = r.shape[0]
+    _need(n_clips >= 1 and f.shape == (n_clips + 1,) and f[0] == 0 and f[-1] == S and bool(np.all(np.diff(f) >= 0)), fn, "first",
+          f"must hold {n_clips + 1} ascending offsets from 0 to S = {S}")
+    _need(bool(np.all(np.diff(f) <= NOTE_ROWS_MAX)), fn, "first", f"gives a clip more than {NOTE_ROWS_MAX} rows")
+    _need(bool(np.array_equal(r[:, 0], np.repeat(np.arange(n_clips), np.diff(f)))), fn, "rows", "of one clip must be contiguous, in the order of `first`")
+    bad = np.nonzero((r[:, 7] < 1) | (r[:, 7] >= program_rows))[0]
+    _need(bad.size == 0, fn, "rows", f"row {int(bad[0]) if bad.size else 0} names program row {int(r[bad[0], 7]) if bad.size else 0}, outside 1 .. {program_rows - 1}")
+    return torch.from_numpy(r.astype(np.int32)).to(device), torch.from_numpy(f.astype(np.int32)).to(device)
+
+
+def note_levels(x, y, rows, out=None):
+    """a2s_note_levels: x, y as for segment_agreement; rows: (S, 8) int32 on their device (note_table) -> (S, 3) float64 on the device, per row
+    [sum x, sum y, count] over the cells of the row's partials (written into `out` when given)."""
+    fn = "note_levels"
+    x, y = _feature_pair(fn, x, y)
+    B, T, F = x.shape
+    _need(torch.is_tensor(rows) and rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 8 and rows.is_contiguous() and rows.device == x.device,
+          fn, "rows", "must be a contiguous int32 tensor (S, 8) on x's device")
+    S = rows.shape[0]
+    if out is None:
+        out = torch.zeros((S, 3), dtype=torch.float64, device=x.device)
+    _need(torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == (S, 3) and out.is_contiguous() and out.device == x.device, fn, "out",
+          f"must be a contiguous float64 tensor ({S}, 3) on x's device")
+    if S == 0:
+        return out
+    _need(B >= 1 and T >= 1 and F >= 1, fn, "x", f"has no cells (shape {tuple(x.shape)}) but the table has rows")
+    check(lib().a2s_note_levels(stream(), _p(x), _p(y), _clip_stride(fn, x, y), B, T, F, _p(rows), S, _p(out)), "a2s_note_levels")
+    return out
+
+
+def note_amp_update(sums, rows, first, cum, programs, base_amp):
+    """a2s_note_amp_update, in place: sums (S, 3) float64 of note_levels, rows (S, 8) and first (B + 1,) int32 of note_table (the table was checked
+    there), cum (S,) float32, programs (B, 1 + E, 8) int32, all contiguous on one device.  Per clip: cum += the level difference, minus the clip's
+    lower median, clamped to -30 .. 12 dB; the amplitude word of every listed program row becomes base_amp * 10^(cum / 20)."""
+    fn = "note_amp_update"
+    _need(torch.is_tensor(programs) and programs.dtype == torch.int32 and programs.dim() == 3 and programs.shape[2] == 8 and programs.shape[1] >= 2
+          and programs.is_contiguous() and programs.is_cuda, fn, "programs", "must be contiguous int32 programs (B, 1 + E, 8) on the device")
+    B, S = programs.shape[0], rows.shape[0] if torch.is_tensor(rows) else -1
+    for name, t, dtype, shape in (("sums", sums, torch.float64, (S, 3)), ("rows", rows, torch.int32, (S, 8)), ("first", first, torch.int32, (B + 1,)),
+                                  ("cum", cum, torch.float32, (S,))):
+        _need(torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == programs.device, fn, name,
+              f"must be a contiguous {dtype} tensor {shape} on the programs' device")
+    _need(0.0 < float(base_amp) <= 1e30, fn, "base_amp", f"must be positive and finite (got {base_amp!r})")
+    if S == 0 or B == 0:
+        return cum
+    check(lib().a2s_note_amp_update(stream(), _p(sums), _p(rows), _p(first), B, _p(cum), _p(programs), programs.shape[1], float(base_amp)), "a2s_note_amp_update")
+    return cum
+
+
+def dynamics_launches():
+    """Launches of the two dynamics kernels in this process (a2s_dynamics_launches)."""
+    return int(lib().a2s_dynamics_launches())
 
 
 def agreement_launches():

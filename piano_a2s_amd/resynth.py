@@ -7,7 +7,11 @@ those with the recording's features bar by bar.  The agreement of a bar is the P
 (all bins): the dB features sit on a non-zero background, which a plain cosine does not take out.  It needs no ground-truth score.
 
 What the number is not: a note accuracy.  The instrument is not a piano, tied chains sound short, and on a real recording timbre and reverberation
-lower it for a perfect transcription by an amount nobody has measured.  Host side: numpy, Fractions and torch only."""
+lower it for a perfect transcription by an amount nobody has measured.  Host side: numpy, Fractions and torch only.
+
+Note dynamics: `estimate_dynamics` closes the loop -- the level of every note's own partials in the recording against the
+resynthesis (`hip.note_levels`) moves the note's amplitude in the render program (`hip.note_amp_update`, csrc/a2s_dynamics.hip), and the score is
+rendered again."""
 import math
 from fractions import Fraction
 
@@ -21,6 +25,11 @@ from . import hip, metrics, render, scoregen
 RESYNTH_INSTRUMENT = dict(g=0.6, n_harm=8, tau=0.8, attack=80)
 RESYNTH_AMP = 0.5
 SAMPLE_RATE = scoregen.SR
+# note dynamics: a note is measured at its first three partials, over at most 12 frames from the frame behind its onset
+DYNAMICS_ROUNDS = 3
+DYNAMICS_FRAMES = 12
+DYNAMICS_BIN_OFFSETS = (0, 60, 95)                   # rint(60 log2 h), h = 1, 2, 3, in bins of a 60-per-octave VQT whose bin 0 is MIDI 21
+LEVEL_DB_RANGE = (-30.0, 12.0)
 
 
 def bar_ticks(time_signature):
@@ -69,12 +78,13 @@ def score_events(upper_rows, lower_rows, time_signatures, bar_lines, max_events=
     return np.array([e[:3] for e in ev[:max_events]], dtype=np.int64).reshape(-1, 3), truncated
 
 
-def program(events, n_samples, rows=scoregen.MAX_EVENTS):
+def program(events, n_samples, amps=None, rows=scoregen.MAX_EVENTS):
     """The render program (1 + rows, 8) int32 of `events` (n, 3) [onset, length, midi] on RESYNTH_INSTRUMENT, through scoregen.pack_program: the gain
-    rule (|wave| < 1) and the pitch-dependent decay are the corpus's."""
+    rule (|wave| < 1) and the pitch-dependent decay are the corpus's.  amps: one amplitude per event; None: RESYNTH_AMP for every note."""
     events = np.asarray(events, dtype=np.int64).reshape(-1, 3)
     inst = dict(RESYNTH_INSTRUMENT, noise_db=-200.0, noise_seed=0)
-    clip = dict(events=events, amps=np.full(len(events), RESYNTH_AMP, dtype=np.float32), instrument=inst, n_samples=int(n_samples))
+    amps = np.full(len(events), RESYNTH_AMP, dtype=np.float32) if amps is None else np.asarray(amps, dtype=np.float32).reshape(len(events))
+    clip = dict(events=events, amps=amps, instrument=inst, n_samples=int(n_samples))
     p = scoregen.pack_program(clip, rows=rows)
     p[0, 6] = 0                                                  # noise off: the level is exactly 0.0, not 10^-10
     return p
@@ -162,7 +172,55 @@ def performed_notes(notes, warp, first_frame, hop, bar_start, bar_stop):
     return out
 
 
-def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False):
+def note_rows(events, performed, hop, T, F, clip=0):
+    """The note table of the dynamics kernels (include/a2s.h: a2s_note_levels): events (n, 3) [onset, length, midi] in the order of their render
+    program, performed: the n onsets in samples where the notes are HEARD in the recording, or None (where the score has them) -> (n, 8) int32
+    [clip, fx, fy, n_frames, b1, b2, b3, prog_row]: fy = onset // hop + 1 the first frame wholly behind the onset in the score's render, fx the same of
+    the performed onset, n_frames = min(DYNAMICS_FRAMES, max(1, (onset + length) // hop - onset // hop)), b_h = 5 (midi - 21) + the offset of partial
+    h, -1 where that is no bin of [0, F), prog_row = the event's index + 1.  T is the clip's frame count: frames at or behind it stay in the table and
+    do not count on the device, where also negative ones are dropped."""
+    events = np.asarray(events, dtype=np.int64).reshape(-1, 3)
+    heard = events[:, 0] if performed is None else np.floor(np.asarray(performed, dtype=np.float64).reshape(len(events))).astype(np.int64)
+    hop, T, F = int(hop), int(T), int(F)
+    if hop < 1 or T < 1 or F < 1:
+        raise ValueError(f"resynth: note_rows needs hop, T, F >= 1 (got {hop}, {T}, {F})")
+    out = np.zeros((len(events), 8), dtype=np.int32)
+    out[:, 0] = clip
+    out[:, 1] = heard // hop + 1
+    out[:, 2] = events[:, 0] // hop + 1
+    out[:, 3] = np.minimum(DYNAMICS_FRAMES, np.maximum(1, (events[:, 0] + events[:, 1]) // hop - events[:, 0] // hop))
+    for h, off in enumerate(DYNAMICS_BIN_OFFSETS):
+        b = 5 * (events[:, 2] - 21) + off
+        out[:, 4 + h] = np.where((b >= 0) & (b < F), b, -1)
+    out[:, 7] = np.arange(1, len(events) + 1)
+    return out
+
+
+def velocity(level_db):
+    """MIDI velocity of a level in dB relative to the window's median note: 64 at 0 dB, 40 dB per decade of velocity, in 1 .. 127."""
+    return int(min(127, max(1, np.rint(64.0 * 10.0 ** (float(level_db) / 40.0)))))
+
+
+def estimate_dynamics(programs, x3, vqt, n_samples, rows, first, rounds=DYNAMICS_ROUNDS, y3=None):
+    """The device loop of DESIGN.md section 26: programs (B, 1 + E, 8) int32 on the device with every amplitude RESYNTH_AMP (they are UPDATED IN
+    PLACE), x3 the recording's features (B, T, F), rows / first the device tables of hip.note_table; y3: the features of the programs as they stand,
+    where the caller has rendered them already (they save round 1 its render and VQT).  `rounds` times render -> VQT -> hip.note_levels ->
+    hip.note_amp_update, with no host work and no read-back in between -> cum (S,) float32 on the device: every note's level in dB relative to its
+    clip's median note, in LEVEL_DB_RANGE.
+    The header's gain stays that of the first pack while the amplitudes move: the front end normalises the features to the window's peak, so a common
+    factor on the waveform does not reach them (and the synthesiser itself does not clip)."""
+    cum = torch.zeros(rows.shape[0], dtype=torch.float32, device=programs.device)
+    sums = torch.zeros((rows.shape[0], 3), dtype=torch.float64, device=programs.device)
+    for k in range(int(rounds)):
+        if k or y3 is None:
+            y = vqt(render.render(programs, n_samples))
+            y3 = y[:, 0] if y.dim() == 4 else y
+        hip.note_levels(x3, y3, rows, out=sums)
+        hip.note_amp_update(sums, rows, first, cum, programs, RESYNTH_AMP)
+    return cum
+
+
+def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics=0):
     """windows: per window of a batch a dict with "events" ((n, 3) int64 of score_events) and "bar_lines"; feats: the recording's features of the same
     windows, (W, 1, T, F) or (W, T, F) float32 on the device; vqt: the front end that made them (waveforms (B, N) -> features); hop: its hop length.
     -> (waves: per window the rendered waveform, float32 numpy (n_samples,), or None; agreements: per window a list with one entry per bar, a float in
@@ -173,7 +231,13 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False):
     align=True -> (waves, agreements, alignments): additionally ONE hip.dtw_segments call warps the resynthesis onto the
     recording inside every bar (band dtw_band(n); the offset of the differences is mean(recording) - mean(resynthesis) of the bar, from the five sums),
     and one more hip.segment_agreement call scores the recording against the resynthesis read along the inverse warp.  alignments: per window a
-    list with one entry per bar, {"first_frame", "frames", "warp", "inverse", "total", "agreement_warped"} or None where the bar has no agreement."""
+    list with one entry per bar, {"first_frame", "frames", "warp", "inverse", "total", "agreement_warped"} or None where the bar has no agreement.
+    dynamics=K > 0 -> one more result, dynamics: per window None or {"level_db" (n,) float32 and "velocity" (n,) int64 per event,
+    "agreement": per bar, ["agreement_warped": per bar, with align]}.  K rounds of estimate_dynamics set every note's amplitude from the recording
+    (round 1 reads the unit-amplitude pass; the warp of align is that pass's too and is not recomputed), the levels are read back ONCE, and the
+    programs are packed on the host and rendered once more with the final amplitudes, so that pack_program's gain rule keeps |wave| < 1: `waves`
+    are then THAT render and dynamics' agreements are scored on it as "agreements" and "agreement_warped" are on the first.  With 0 nothing of this
+    is allocated, launched or returned."""
     f3 = feats[:, 0] if feats.dim() == 4 else feats
     W, T, F = f3.shape
     if len(windows) != W:
@@ -183,10 +247,12 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False):
     agreements = [[None] * (len(win["bar_lines"]) - 1) for win in windows]
     live = [w for w, win in enumerate(windows) if len(win["events"])]
     alignments = [[None] * len(a) for a in agreements] if align else None
+    levels = [None] * W if dynamics else None
+    result = lambda: (waves, agreements) + ((alignments,) if align else ()) + ((levels,) if dynamics else ())
     if not live:
-        return (waves, agreements, alignments) if align else (waves, agreements)
-    progs = np.stack([program(windows[w]["events"], n_samples) for w in live])
-    wave = render.render(torch.from_numpy(progs).to(f3.device), n_samples)
+        return result()
+    progs = torch.from_numpy(np.stack([program(windows[w]["events"], n_samples) for w in live])).to(f3.device)
+    wave = render.render(progs, n_samples)
     y = vqt(wave)
     y3 = y[:, 0] if y.dim() == 4 else y
     if tuple(y3.shape[1:]) != (T, F):
@@ -196,21 +262,68 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False):
     sums = hip.segment_agreement(x3, y3, seg).cpu().numpy()
     for (i, b), row, s in zip(where, seg, sums):
         agreements[live[i]][b] = agreement(s, (int(row[2]) - int(row[1])) * F)
-    if align:
-        _align_bars(x3, y3, seg, where, sums, [live[i] for i, _ in where], agreements, alignments)
+    heard = _align_bars(x3, y3, seg, where, sums, [live[i] for i, _ in where], agreements, alignments) if align else None
+    if dynamics:
+        wave = _dynamics(windows, live, progs, x3, y3, vqt, int(hop), n_samples, int(dynamics), seg, where, alignments, heard, levels)
     host = wave.cpu().numpy()
     for i, w in enumerate(live):
         waves[w] = host[i]
-    return (waves, agreements, alignments) if align else (waves, agreements)
+    return result()
+
+
+def performed_onsets(events, bar_lines, aligned, hop):
+    """The onsets (samples, floats) at which the events (n, 3) of one window are heard: every note moved through the warp of its bar (aligned: the
+    window's entry of resynthesise's alignments; a bar without one moves nothing)."""
+    lines = [int(t) for t in bar_lines]
+    out = []
+    for ev in np.asarray(events, dtype=np.int64).reshape(-1, 3):
+        b = min(max(int(np.searchsorted(lines, ev[0], side="right")) - 1, 0), len(lines) - 2)
+        al = aligned[b]
+        out.append(performed_notes([ev], None if al is None else al["warp"], 0 if al is None else al["first_frame"], hop, lines[b], lines[b + 1])[0][0])
+    return np.array(out, dtype=np.float64)
+
+
+def _dynamics(windows, live, progs, x3, y3, vqt, hop, n_samples, rounds, seg, where, alignments, heard, levels):
+    """The dynamics=K half of resynthesise: fills `levels` for the live windows and returns the final render (len(live), n_samples) on the device."""
+    _, T, F = x3.shape
+    table = []
+    for i, w in enumerate(live):
+        ev = windows[w]["events"]
+        table.append(note_rows(ev, None if alignments is None else performed_onsets(ev, windows[w]["bar_lines"], alignments[w], hop), hop, T, F, clip=i))
+    first = np.concatenate([[0], np.cumsum([len(t) for t in table])])
+    rows, first_d = hip.note_table(np.concatenate(table), first, len(live), progs.shape[1], x3.device)
+    cum = estimate_dynamics(progs, x3.contiguous(), vqt, n_samples, rows, first_d, rounds, y3=y3).cpu().numpy()          # (the one read-back)
+    final = []
+    for i, w in enumerate(live):
+        db = cum[first[i]:first[i + 1]]
+        levels[w] = {"level_db": db, "velocity": np.array([velocity(v) for v in db], dtype=np.int64), "agreement": [None] * (len(windows[w]["bar_lines"]) - 1)}
+        final.append(program(windows[w]["events"], n_samples, amps=RESYNTH_AMP * 10.0 ** (db.astype(np.float64) / 20.0)))
+    wave = render.render(torch.from_numpy(np.stack(final)).to(x3.device), n_samples)
+    z = vqt(wave)
+    z3 = z[:, 0] if z.dim() == 4 else z
+    sums = hip.segment_agreement(x3, z3, seg).cpu().numpy()
+    for (i, b), row, s in zip(where, seg, sums):
+        levels[live[i]]["agreement"][b] = agreement(s, (int(row[2]) - int(row[1])) * F)
+    if alignments is not None:
+        for w in live:
+            levels[w]["agreement_warped"] = [None] * len(levels[w]["agreement"])
+        if heard is not None:
+            index, table4, at = heard
+            z3 = z3.contiguous()
+            warped = hip.segment_agreement(x3.contiguous(), z3[torch.arange(z3.shape[0], device=z3.device)[:, None], index], table4[:, :3]).cpu().numpy()
+            for k, s, row in zip(at, warped, table4):
+                levels[live[where[k][0]]]["agreement_warped"][where[k][1]] = agreement(s, int(row[2] - row[1]) * F)
+    return wave
 
 
 def _align_bars(x3, y3, seg, where, sums, window_of, agreements, alignments):
-    """The align=True half of resynthesise: fills `alignments` for the bars of the table `seg` that have an agreement."""
+    """The align=True half of resynthesise: fills `alignments` for the bars of the table `seg` that have an agreement -> (index: (clips, T) the score
+    frame heard at every recording frame, the aligned bars' table (S', 4), their rows of `seg`), or None where no bar has an agreement."""
     _, T, F = x3.shape
     x3, y3 = x3.contiguous(), y3.contiguous()          # (the gathered tensor below is contiguous, and both operands share one clip stride)
     rows = [k for k, ((_, b), w) in enumerate(zip(where, window_of)) if agreements[w][b] is not None]
     if not rows:
-        return
+        return None
     table = np.array([[seg[k][0], seg[k][1], seg[k][2], dtw_band(seg[k][2] - seg[k][1])] for k in rows], dtype=np.int64)
     cells = (table[:, 2] - table[:, 1]) * F
     off = torch.from_numpy(((sums[rows, 0] - sums[rows, 1]) / cells).astype(np.float32)).to(x3.device)
@@ -227,6 +340,7 @@ def _align_bars(x3, y3, seg, where, sums, window_of, agreements, alignments):
     for k, row, s, n in zip(rows, found, warped, cells):
         row["agreement_warped"] = agreement(s, int(n))
         alignments[window_of[k]][where[k][1]] = row
+    return index, table, rows
 
 
 def mean_agreement(values):

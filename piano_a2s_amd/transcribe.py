@@ -63,7 +63,8 @@ def check_downbeats(downbeats, beats_per_bar):
         raise ValueError(f"transcribe: beats_per_bar must be 2, 3 or 4 (got {beats_per_bar!r})")
 
 
-def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False, align_notes=False):
+def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False, align_notes=False,
+                        dynamics=False, dynamics_rounds=None, min_level_db=None):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
@@ -85,12 +86,25 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     align_notes=True (needs resynthesis, ValueError without): inside every bar the resynthesis is warped onto the recording (banded dynamic time
     warping of the two feature tensors).  Every bar gains "agreement_warped" (the agreement with the resynthesis read along the
     warp: timing no longer counts; None where "agreement" is None) and "performed" ([[onset_s, length_s, midi]]: the bar's "notes" with onset and end
-    moved through the bar's warp, clamped to the bar, at least one frame long), every window "agreement_warped" (the mean over its bars)."""
+    moved through the bar's warp, clamped to the bar, at least one frame long), every window "agreement_warped" (the mean over its bars).
+    dynamics=True (needs resynthesis, ValueError without; with or without align_notes): every note's loudness is estimated from the recording by
+    analysis by synthesis (dynamics_rounds rounds, default resynth.DYNAMICS_ROUNDS).  Every bar gains "dynamics" ([[level_db,
+    velocity]] parallel to "notes": dB relative to the window's median note in -30 .. 12, and the MIDI velocity 64 * 10^(level_db / 40) in 1 .. 127;
+    [None, None] for a note that did not fit the render program) and "agreement_dynamics" (the agreement with the resynthesis at those dynamics),
+    where the bar was aligned also "agreement_dynamics_warped"; every window the means of those; "resynthesis" is the render at the estimated
+    dynamics.  min_level_db=L: every bar also gains "quiet", one flag per note, True where the level is below L (audio.result_notes leaves those
+    out; the decoded bars keep them).  A level is relative to its window: loudness across windows is not recovered."""
     check_downbeats(downbeats, beats_per_bar)
     if resynthesis and downbeats is None:
         raise ValueError("transcribe: resynthesis needs downbeats (given or tracked): in fixed windows the decoded bars have no position in the audio")
     if align_notes and not resynthesis:
         raise ValueError("transcribe: align_notes aligns the resynthesis with the recording: it needs resynthesis=True")
+    if dynamics and not resynthesis:
+        raise ValueError("transcribe: dynamics sets the amplitudes of the resynthesis from the recording: it needs resynthesis=True")
+    if (dynamics_rounds is not None or min_level_db is not None) and not dynamics:
+        raise ValueError("transcribe: dynamics_rounds and min_level_db belong to dynamics=True")
+    if dynamics_rounds is not None and int(dynamics_rounds) < 1:
+        raise ValueError(f"transcribe: dynamics_rounds must be at least 1 (got {dynamics_rounds!r})")
     core = getattr(model, "module", model)
     device = next(core.parameters()).device
     hop = int(_hp(hparams, "hop_length", 160))
@@ -152,15 +166,16 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
                 batch.append((win, start, lines, up, lo))
             if resynthesis:
                 _resynthesise_batch(resynth, batch, feats[w0:w0 + int(batch_size)], _vqt(device, hparams), hop, rate, result["resynthesis"]["wave"],
-                                    align=align_notes)
+                                    align=align_notes, dynamics=(int(dynamics_rounds or resynth.DYNAMICS_ROUNDS) if dynamics else 0), min_level_db=min_level_db)
     finally:
         model.train(was_training)
     return result
 
 
-def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=False):
+def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=False, dynamics=0, min_level_db=None):
     """The resynthesis of one batch of windows [(window dict, start sample, bar lines, upper rows, lower rows)]: fills the windows' and bars' new keys
-    and adds the renders into `total` (the recording-long waveform) at the windows' starts.  align: also the keys of align_notes."""
+    and adds the renders into `total` (the recording-long waveform) at the windows' starts.  align: also the keys of align_notes; dynamics: the
+    rounds of the dynamics estimate (0: off) and its keys."""
     windows, bar_notes = [], []
     for win, start, lines, up, lo in batch:
         lines = lines[:win["n_bars"] + 1]
@@ -172,13 +187,14 @@ def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=Fals
             bar["notes"] = [[(start + int(o)) / rate, int(n) / rate, int(m)] for o, n, m in notes]
             bar_notes.append(notes)
         windows.append({"events": events, "bar_lines": lines})
-    waves, agreements, *aligned = resynth.resynthesise(windows, feats, vqt, hop, align=align)
+    waves, agreements, *more = resynth.resynthesise(windows, feats, vqt, hop, align=align, dynamics=dynamics)
+    alignments, levels = more[0] if align else None, more[-1] if dynamics else None
     bar_notes = iter(bar_notes)
     for k, ((win, start, lines, *_), w, agr) in enumerate(zip(batch, waves, agreements)):
         for i, (bar, a) in enumerate(zip(win["bars"], agr)):
             bar["agreement"] = a
             if align:
-                al = aligned[0][k][i]
+                al = alignments[k][i]
                 bar["agreement_warped"] = None if al is None else al["agreement_warped"]
                 moved = resynth.performed_notes(next(bar_notes), None if al is None else al["warp"], 0 if al is None else al["first_frame"], hop,
                                                 lines[i], lines[i + 1])
@@ -186,9 +202,30 @@ def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=Fals
         win["agreement"] = resynth.mean_agreement(agr)
         if align:
             win["agreement_warped"] = resynth.mean_agreement([bar["agreement_warped"] for bar in win["bars"]])
+        if dynamics:
+            _dynamics_keys(resynth, win, levels[k], align, min_level_db)
         if w is not None and start < len(total):
             n = min(len(w), len(total) - start)
             total[start:start + n] += w[:n]
+
+
+def _dynamics_keys(resynth, win, lv, align, min_level_db):
+    """The keys of dynamics=True of one window: lv is the window's entry of resynthesise's dynamics (None for a window without a note).  The window's
+    events are its bars' notes in order, cut at the render program's length."""
+    at = 0
+    for i, bar in enumerate(win["bars"]):
+        n = len(bar["notes"])
+        have = 0 if lv is None else max(0, min(n, len(lv["level_db"]) - at))
+        bar["dynamics"] = [[float(lv["level_db"][at + j]), int(lv["velocity"][at + j])] for j in range(have)] + [[None, None]] * (n - have)
+        bar["agreement_dynamics"] = None if lv is None else lv["agreement"][i]
+        if align and bar.get("agreement_warped") is not None:
+            bar["agreement_dynamics_warped"] = lv["agreement_warped"][i]
+        if min_level_db is not None:
+            bar["quiet"] = [d[0] is not None and d[0] < float(min_level_db) for d in bar["dynamics"]]
+        at += n
+    win["agreement_dynamics"] = resynth.mean_agreement([bar["agreement_dynamics"] for bar in win["bars"]])
+    if align:
+        win["agreement_dynamics_warped"] = resynth.mean_agreement([bar.get("agreement_dynamics_warped") for bar in win["bars"]])
 
 
 def _alignment_record(al, b, start_s, fps, up, lo):
@@ -267,6 +304,13 @@ def main(argv):
     ap.add_argument("--align_notes", action="store_true", help="implies --resynthesis: warp the resynthesis onto the recording inside every bar; every bar "
                     'gains "agreement_warped" and "performed" (its notes where they are heard), and DIR/NAME.mid holds the performed notes as a '
                     "Standard MIDI File (format 0, 1 ms ticks, velocity 64)")
+    ap.add_argument("--dynamics", action="store_true", help="implies --resynthesis: estimate every note's loudness from the recording by analysis by "
+                    'synthesis; every bar gains "dynamics" ([level_db, velocity] per note, relative to the window\'s median note) and '
+                    '"agreement_dynamics", DIR/NAME.resynth.wav plays the score at those dynamics and DIR/NAME.mid carries the velocities')
+    ap.add_argument("--dynamics_rounds", type=int, default=None, help="with --dynamics: rounds of render, measure, update (default 3)")
+    ap.add_argument("--min_level_db", type=float, default=None, help="with --dynamics: notes whose level is below this are left out of DIR/NAME.mid and "
+                    'marked in the bar\'s "quiet"; nothing is dropped from the decoded bars.  No default: the gap between notes that are not in the '
+                    "audio and quiet real notes has only been seen on renders")
     ap.add_argument("--device", default="cuda:0")
     a, extra = ap.parse_known_args(argv)
     overrides = {}
@@ -283,7 +327,11 @@ def main(argv):
         ap.error("--downbeats belongs to one recording")
     if a.beats_per_bar is not None and not a.track_downbeats:
         ap.error("--beats_per_bar belongs to --track_downbeats")
-    a.resynthesis = a.resynthesis or a.align_notes
+    if (a.dynamics_rounds is not None or a.min_level_db is not None) and not a.dynamics:
+        ap.error("--dynamics_rounds and --min_level_db belong to --dynamics")
+    if a.dynamics_rounds is not None and a.dynamics_rounds < 1:
+        ap.error(f"--dynamics_rounds must be at least 1 (got {a.dynamics_rounds})")
+    a.resynthesis = a.resynthesis or a.align_notes or a.dynamics
     if a.resynthesis and not (a.downbeats or a.track_downbeats):
         ap.error("--resynthesis needs --downbeats or --track_downbeats: in fixed windows the decoded bars have no position in the audio")
     model, hp = load_model(a.hparams, a.checkpoint, torch.device(a.device), overrides or None)
@@ -295,7 +343,8 @@ def main(argv):
     for path in a.audio:
         x, sr = audio.read_wav(path)
         result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
-                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis, align_notes=a.align_notes)
+                                     hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis, align_notes=a.align_notes,
+                                     dynamics=a.dynamics, dynamics_rounds=a.dynamics_rounds, min_level_db=a.min_level_db)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
         if a.resynthesis:
@@ -305,7 +354,7 @@ def main(argv):
             wav = out[:-len(".json")] + ".resynth.wav"
             audio.write_wav(wav, np.stack([rec, res["wave"][:len(rec)]], axis=1), res["sample_rate"], bits=16)
             result["resynthesis"] = {"sample_rate": res["sample_rate"], "file": os.path.basename(wav)}
-        if a.align_notes:
+        if a.align_notes or a.dynamics:
             mid = out[:-len(".json")] + ".mid"
             audio.write_midi(mid, result)
             result["performance"] = {"file": os.path.basename(mid)}
