@@ -10,7 +10,8 @@ split doubles as validation split.  ``--constrained_decoding=true``, ``--metrica
 of time or frequency, applied to the precomputed feature files' rows on the GPU (TRAIN batches only).
 Optional override of the rendered corpus: ``--synthetic_room=none|train|eval|all [--room_rt60="(lo, hi)" --room_drr_db="(lo, hi)" --room_predelay_ms="(lo, hi)"]``
 (with ``--synthetic_scores=rendered`` only: every clip is heard in a synthetic room of its own -- direct path, pre-delay, decaying diffuse tail, drawn from the
-clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none)."""
+clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none).
+``--tuning_correction=true`` as in pretrain.py: recordings of pianos that do not sit at A4 = 440 Hz are shifted back onto the grid, clip by clip, in all three stages."""
 import os
 import shutil
 import sys

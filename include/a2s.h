@@ -659,6 +659,41 @@ int a2s_note_levels(void* stream, const float* x, const float* y, long clip_stri
 int a2s_note_amp_update(void* stream, const double* sums, const int* rows, const int* first, int B, float* cum, int* programs, int program_stride,
                         float base_amp);
 int a2s_dynamics_launches(void);
+/* ---- the tuning of a recording, estimated from the model's own features (csrc/a2s_tuning.hip): the two device stages in front of
+ * a2s_shift_bins (piano_a2s_amd/tuning.py).  The features have S = bins_per_semitone bins per semitone and bin 0 is A0 at A4 = 440 Hz; a piano c cents
+ * away from that puts every partial c * S / 100 bins beside its column.  H = 100 histogram cells per semitone (one cent each), Q = 4096.  Both entry
+ * points take borrowed device pointers and a stream, allocate nothing, do not synchronise and read nothing back.
+ * a2s_tuning_profile: x = B clips of `rows` rows of F float32 (dB / 80 + 1), row t of clip b at x + b * x_bstride + t * x_rstride (unit stride along F);
+ * n_rows (B,) int32, clamped to [0, rows]: only the rows t < n_rows[b] count.  Over those rows and the bins 1 <= f <= F - 2, with a, c, e = x[t][f - 1],
+ * x[t][f], x[t][f + 1]: a peak is c > a && c >= e && c >= thr (false with a NaN: a plateau, silence and NaN give none).  For a peak, in double:
+ *     delta = 0.5 (a - e) / ((a - c) + (e - c))   (a NaN, which only cells at +-inf give, reads as 0);
+ *     u = ((f mod S) + delta) + S / 2, u -= S where u >= S;   cell = min(H - 1, floor(u * H / S));   weight = 1 + rint(min(c - thr, 1) * Q);
+ *     hist[b][cell] += weight;   hist[b][H] += 1   (the peak count).
+ * Cell k stands for a deviation of [k - 50, k - 49) cents from the equal-tempered grid at 440 Hz.  hist: B rows of H + 1 int64, OVERWRITTEN (zeroing it
+ * on the stream is part of the call).  One streaming pass, every cell read once (16-byte loads where F % 4 == 0, x is 16-byte aligned and both strides
+ * are multiples of 4); integer LDS atomics per wave, 64-bit integer global atomics into hist, no float atomics: the integers do not depend on the order
+ * of arrival, on B, on the strides or on a clip's place in the batch, and equal tests/tuning_oracle.py's.  Nothing outside a clip's rows x F cells is
+ * read (the stride padding may hold NaN).  F < 3 gives zeros (no kernel runs).  Null pointers, B < 0 or > 65535, rows < 1, F < 1, bins_per_semitone < 1
+ * or > 64, thr outside [0, 1] or not finite, a row stride < F or a clip stride < (rows - 1) * row stride + F: A2S_ERR_ARG, nothing is launched; B = 0
+ * returns 0 and launches nothing.
+ * a2s_tuning_estimate: group g is the clips first[g] .. first[g + 1] - 1 (first: device, G + 1 int32, ascending from 0 to B; a group may be empty; the
+ * kernel clamps what it reads to [0, B], the host table is checked by piano_a2s_amd.hip.tuning_estimate before it is uploaded).  h = the group's
+ * histograms added (int64); sm[k] = sum_{j = -6 .. 6} (7 - |j|) h[(k + j) mod H] (int64, exact); k* = the first arg max of sm; then in double:
+ *     conf = sm[k*] * H / sum(sm)   (0 where the sum is 0);      A, C, E = sm[k* - 1], sm[k*], sm[k* + 1] (circular), den = (A - C) + (E - C);
+ *     delta = 0.5 (A - E) / den where den < 0, else 0;          cents = ((k* + 0.5) + delta) * 100 / H - 50, cents -= 100 where it reaches 50;
+ *     est[g] = [cents, conf, peaks]   (three doubles, always written);      determined = peaks >= min_peaks && conf >= min_conf;
+ *     eff_bins[b] = (float)(determined ? -cents * S / 100 : 0.0) for every clip of the group: what a2s_shift_bins reads.
+ * A numpy restatement (piano_a2s_amd.tuning.estimate_host) gives the same bits.  A group of zeros (an empty one too) gives [-49.5, 0, 0] and is not
+ * determined.  cents lies in [-50, 50): a detuning beyond that is a transposition and cannot be told apart.  One workgroup per group, one launch.
+ * Null pointers (hist and eff_bins may be null where B = 0), G < 0 or > 65535, B < 0, bins_per_semitone < 1 or > 64, min_conf not finite,
+ * min_peaks < 0: A2S_ERR_ARG, nothing is launched; G = 0 returns 0 and launches nothing.
+ * Limits: real strings are inharmonic, their stretched partials pull the estimate sharp by an amount nobody has measured here; one tuning per group.
+ * a2s_tuning_launches: kernel launches of the two so far (proof of the path). */
+int a2s_tuning_profile(void* stream, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F, int bins_per_semitone,
+                       float thr, long long* hist);
+int a2s_tuning_estimate(void* stream, const long long* hist, const int* first, int G, int B, int bins_per_semitone, double min_conf, int min_peaks,
+                        double* est, float* eff_bins);
+int a2s_tuning_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

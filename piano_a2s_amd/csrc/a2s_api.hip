@@ -348,6 +348,15 @@ int a2s_note_amp_update(void* stream, const double* sums, const int* rows, const
     return a2s_note_amp_update_impl(ST, sums, rows, first, B, cum, programs, program_stride, base_amp);
 }
 int a2s_dynamics_launches(void) { return a2s_dynamics_launches_impl(); }
+int a2s_tuning_profile(void* stream, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F, int bins_per_semitone,
+                       float thr, long long* hist) {
+    return a2s_tuning_profile_impl(ST, x, x_bstride, x_rstride, n_rows, B, rows, F, bins_per_semitone, thr, hist);
+}
+int a2s_tuning_estimate(void* stream, const long long* hist, const int* first, int G, int B, int bins_per_semitone, double min_conf, int min_peaks,
+                        double* est, float* eff_bins) {
+    return a2s_tuning_estimate_impl(ST, hist, first, G, B, bins_per_semitone, min_conf, min_peaks, est, eff_bins);
+}
+int a2s_tuning_launches(void) { return a2s_tuning_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

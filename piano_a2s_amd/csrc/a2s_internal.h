@@ -356,6 +356,13 @@ int a2s_note_amp_update_impl(hipStream_t st, const double* sums, const int* rows
                              float base_amp);
 int a2s_dynamics_launches_impl(void);
 
+// ---- a2s_tuning.hip
+int a2s_tuning_profile_impl(hipStream_t st, const float* x, long x_bstride, long x_rstride, const int* n_rows, int B, int rows, int F,
+                            int bins_per_semitone, float thr, long long* hist);
+int a2s_tuning_estimate_impl(hipStream_t st, const long long* hist, const int* first, int G, int B, int bins_per_semitone, double min_conf, int min_peaks,
+                             double* est, float* eff_bins);
+int a2s_tuning_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

@@ -963,6 +963,84 @@ def dynamics_launches():
     return int(lib().a2s_dynamics_launches())
 
 
+TUNING_CELLS = 100           # histogram cells per semitone of the tuning kernels (csrc/a2s_tuning.hip): a row of hist holds TUNING_CELLS + 1 int64
+
+
+def tuning_profile(x, n_rows, thr=0.5, bins_per_semitone=5, out=None):
+    """a2s_tuning_profile: x (B, rows, F) or (B, 1, rows, F) float32 on the device, unit stride along F (the rows and the clips may be strided), n_rows
+    (B,) int32 -> hist (B, 101) int64 on the device (written into `out` when given; overwritten): per clip the histogram of its spectral peaks'
+    positions modulo one semitone, 100 cells of one cent each weighted by the peaks' heights, and in cell 100 the number of peaks."""
+    fn = "tuning_profile"
+    _need(torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and (x.dim() == 3 or (x.dim() == 4 and x.shape[1] == 1)), fn, "x",
+          "must be a float32 tensor (B, rows, F) or (B, 1, rows, F) on the device")
+    if x.dim() == 4:
+        x = x[:, 0]
+    B, rows, F = x.shape
+    S, = _whole(fn, bins_per_semitone=bins_per_semitone)
+    _need(1 <= S <= 64, fn, "bins_per_semitone", f"must be in 1 .. 64 (got {S})")
+    try:
+        t = float(thr)
+    except (TypeError, ValueError):
+        t = float("nan")
+    _need(0.0 <= t <= 1.0, fn, "thr", f"must be a number in 0 .. 1 (got {thr!r})")
+    _int_rows(fn, "n_rows", n_rows, (B,), x.device)
+    if out is None:
+        out = torch.zeros((B, TUNING_CELLS + 1), dtype=torch.int64, device=x.device)
+    _need(torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (B, TUNING_CELLS + 1) and out.is_contiguous() and out.device == x.device,
+          fn, "out", f"must be a contiguous int64 tensor ({B}, {TUNING_CELLS + 1}) on x's device")
+    if B == 0 or rows == 0 or F == 0:
+        _need(B == 0 or F > 0 or rows == 0, fn, "x", "has rows but no columns")
+        return out.zero_()
+    _need(x.stride(2) == 1 or F == 1, fn, "x", "must have unit stride along F")
+    xr = x.stride(1) if rows > 1 else max(x.stride(1), F)
+    xb = x.stride(0) if B > 1 else max(x.stride(0), (rows - 1) * xr + F)
+    _need(xr >= F and xb >= (rows - 1) * xr + F, fn, "x", f"has overlapping rows or clips (strides {tuple(x.stride())})")
+    check(lib().a2s_tuning_profile(stream(), _p(x), xb, xr, _p(n_rows), B, rows, F, S, t, _p(out)), "a2s_tuning_profile")
+    return out
+
+
+def tuning_estimate(hist, first, min_conf, min_peaks, bins_per_semitone=5):
+    """a2s_tuning_estimate: hist (B, 101) int64 on the device (tuning_profile); first: the groups' offsets, G + 1 whole numbers ascending from 0 to B
+    -- the HOST table (anything numpy reads), checked here before it is uploaded, or an int32 tensor on hist's device that an earlier call checked
+    (piano_a2s_amd.tuning.Tuner keeps one) -> (est (G, 3) float64 [cents, confidence, peaks], eff_bins (B,) float32: -cents * S / 100 for the
+    clips of every group with at least min_peaks peaks and a confidence of at least min_conf, else 0), both on the device."""
+    fn = "tuning_estimate"
+    _need(torch.is_tensor(hist) and hist.dtype == torch.int64 and hist.dim() == 2 and hist.shape[1] == TUNING_CELLS + 1 and hist.is_contiguous() and hist.is_cuda,
+          fn, "hist", f"must be a contiguous int64 tensor (B, {TUNING_CELLS + 1}) on the device")
+    B = hist.shape[0]
+    S, mp = _whole(fn, bins_per_semitone=bins_per_semitone, min_peaks=min_peaks)
+    _need(1 <= S <= 64, fn, "bins_per_semitone", f"must be in 1 .. 64 (got {S})")
+    _need(0 <= mp < 2 ** 31, fn, "min_peaks", f"must be in 0 .. 2^31 - 1 (got {mp})")
+    try:
+        mc = float(min_conf)
+    except (TypeError, ValueError):
+        mc = float("nan")
+    _need(np.isfinite(mc), fn, "min_conf", f"must be a finite number (got {min_conf!r})")
+    if torch.is_tensor(first) and first.is_cuda:
+        _need(first.dtype == torch.int32 and first.dim() == 1 and first.numel() >= 1 and first.is_contiguous() and first.device == hist.device, fn, "first",
+              "on the device must be a contiguous 1-D int32 tensor on hist's device")
+    else:
+        from .tuning import check_first
+        try:
+            table = check_first(first.cpu().numpy() if torch.is_tensor(first) else first, B)
+        except ValueError as e:
+            raise A2SError(f"{fn}: {e}") from None
+        first = torch.from_numpy(table.astype(np.int32)).to(hist.device)
+    G = first.numel() - 1
+    _need(G <= 65535, fn, "first", f"names {G} groups, more than 65535")
+    est = torch.zeros((G, 3), dtype=torch.float64, device=hist.device)
+    eff = torch.zeros((B,), dtype=torch.float32, device=hist.device)
+    if G == 0:
+        return est, eff
+    check(lib().a2s_tuning_estimate(stream(), _p(hist), _p(first), G, B, S, mc, mp, _p(est), _p(eff)), "a2s_tuning_estimate")
+    return est, eff
+
+
+def tuning_launches():
+    """Kernel launches of the two tuning kernels in this process (a2s_tuning_launches)."""
+    return int(lib().a2s_tuning_launches())
+
+
 def agreement_launches():
     """Launches of the two agreement kernels in this process (a2s_agreement_launches)."""
     return int(lib().a2s_agreement_launches())

@@ -110,6 +110,8 @@ class ASR(sb.Brain):
     # ------------------------------------------------------------------ forward / objective
     def compute_forward(self, batch, stage):
         batch = _features(batch, self.device, room=self._room(stage))
+        if stage != sb.Stage.TRAIN:
+            batch = self._correct_tuning(batch)       # (a TRAIN batch was corrected in _train_features, in front of the augmenters)
         spectrogram, ts_t, key_t, up_t, up_len, lo_t, lo_len = batch[:7]
         if stage == sb.Stage.TRAIN:
             return self.modules.transcription(spectrogram=spectrogram, inference=False,
@@ -156,6 +158,37 @@ class ASR(sb.Brain):
         (metrics.corpus_note_f1).  Off by default: no key is added and nothing of it runs."""
         v = getattr(self.hparams, "note_metrics", False)
         return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
+    def _tuning_correction(self):
+        """--tuning_correction=true (an optional override as --constrained_decoding): in all three stages every clip's tuning is estimated on the
+        device and its features are shifted back onto the grid at A4 = 440 Hz (piano_a2s_amd.tuning), every clip a group of
+        its own; in TRAIN in front of the augmenters.  Off by default: nothing is built, nothing is launched, no stat is added."""
+        v = getattr(self.hparams, "tuning_correction", False)
+        return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
+
+    def _correct_tuning(self, batch):
+        """The batch of `_features` with its features corrected, or as it is when the switch is off.  [sum of |cents| over the determined clips, the
+        determined clips, the clips] grow on the device; on_stage_end reads them once."""
+        if not self._tuning_correction():
+            return batch
+        if not hasattr(self, "_tuner"):
+            from piano_a2s_amd.tuning import Tuner
+            self._tuner = Tuner(self.device, bins_per_octave=int(getattr(self.hparams, "bins_per_octave", 60)))
+            self._tuning_sums = torch.zeros(3, dtype=torch.float64, device=self.device)
+        batch = list(batch)
+        batch[0], est, _ = self._tuner(batch[0])
+        determined = ((est[:, 2] >= self._tuner.min_peaks) & (est[:, 1] >= self._tuner.min_conf)).to(torch.float64)
+        self._tuning_sums += torch.stack([(est[:, 0].abs() * determined).sum(), determined.sum(), determined.new_tensor(float(est.shape[0]))])
+        return batch
+
+    def _tuning_stats(self):
+        """{"tuning_abs_cents": the mean |cents| over the stage's determined clips (0 without one), "tuning_determined": their share of the clips},
+        or {} when the switch is off: one small D2H per stage; the sums start again."""
+        if not self._tuning_correction() or not hasattr(self, "_tuning_sums"):
+            return {}
+        total, determined, clips = self._tuning_sums.tolist()
+        self._tuning_sums.zero_()
+        return {"tuning_abs_cents": total / determined if determined else 0.0, "tuning_determined": determined / clips if clips else 0.0}
 
     def _set_alignment(self):
         if not self._alignment():
@@ -241,7 +274,7 @@ class ASR(sb.Brain):
         """`_features` of a TRAIN batch, augmented when the run asks for it, in the order of AUGMENTERS: transposed first, then time-stretched, then
         coloured and masked.  Where an augmenter rewrites the targets in place, a tensor that was on the device before (and so is the caller's own) is
         copied first."""
-        out = _features(batch, self.device, room=self._room(sb.Stage.TRAIN))
+        out = self._correct_tuning(_features(batch, self.device, room=self._room(sb.Stage.TRAIN)))      # (--detune_bins then acts on a normalised clip)
         for cls, aug in self._augmenters():
             if cls.rewrites_targets:
                 for i in (2, 3, 5):
@@ -338,6 +371,9 @@ class ASR(sb.Brain):
         this, the first epoch after a resume, or after finetune.py's copy of the pretraining save/, ran at the yaml's initial lr."""
         self._augmenters()                        # (an augmentation switch out of range is refused before anything else happens)
         self._room(sb.Stage.TRAIN)                # (and a --synthetic_room)
+        if self._tuning_correction():             # (and a --tuning_correction on features whose bins do not divide the semitone)
+            from piano_a2s_amd.tuning import bins_per_semitone
+            bins_per_semitone(getattr(self.hparams, "bins_per_octave", 60))
         super().on_fit_start()
         self._set_constrained_decoding()          # (a module that cannot decode under the grammar is refused before the first epoch, not after it)
         fused = self._fused_step()
@@ -348,7 +384,7 @@ class ASR(sb.Brain):
     def fit_batch(self, batch):
         fused = self._fused_step()
         if not fused:
-            if self._augmenters():
+            if self._augmenters() or self._tuning_correction():
                 # the generic path reads the batch twice (compute_forward, compute_objectives): both see the augmented device batch, which
                 # `_features` and `_to_device` pass through as it is
                 batch = self._train_features(batch)
@@ -398,6 +434,7 @@ class ASR(sb.Brain):
                  "upper_loss": np.mean(self.upper_losses), "lower_loss": np.mean(self.lower_losses)}
         if not self.finetune:
             stats["teacher_forcing_ratio"] = self.teacher_forcing_ratio
+        stats.update(self._tuning_stats())
         if stage == sb.Stage.TRAIN:
             self.train_stats = stats
             for cls, aug in self._augmenters():

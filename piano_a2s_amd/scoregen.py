@@ -234,3 +234,13 @@ def pack_program(clip, rows=MAX_EVENTS):
     notes = [(int(o), int(l), int(m), float(a), 1.0 / (inst["tau"] * 2.0 ** ((60 - int(m)) / 24.0) * SR), g, nh) for (o, l, m), a in zip(ev, amps)]
     return pack_rows(clip["n_samples"], notes, attack=inst["attack"], rel_len=rel_len, rel_rate=1.0 / 800, gain=gain,
                      noise_level=10.0 ** (inst["noise_db"] / 20.0), noise_seed=inst["noise_seed"], rows=rows)
+
+
+def detune_program(program, cents):
+    """A copy of a render program ((1 + E, 8) int32, or a batch of them) whose notes sound `cents` cents beside their pitch: word 2 of every event
+    row, the phase increment of the fundamental, becomes rint(inc * 2^(cents / 1200)) on its uint32 view (at most 2^32 - 1).  The header rows and
+    everything else stay; 0 cents returns an equal program."""
+    p = np.array(program, dtype=np.int32, copy=True)
+    inc = p[..., 1:, 2].view(np.uint32).astype(np.float64)
+    p[..., 1:, 2] = np.minimum(np.rint(inc * 2.0 ** (float(cents) / 1200.0)), 2.0 ** 32 - 1).astype(np.uint32).view(np.int32)
+    return p

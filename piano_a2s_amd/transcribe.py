@@ -63,8 +63,17 @@ def check_downbeats(downbeats, beats_per_bar):
         raise ValueError(f"transcribe: beats_per_bar must be 2, 3 or 4 (got {beats_per_bar!r})")
 
 
+def check_tuning(tuning):
+    """What transcribe_waveform takes as `tuning`: None, the word "auto", or a finite number of cents -> None, "auto" or a float."""
+    if tuning is None or tuning == "auto":
+        return tuning
+    if isinstance(tuning, (str, bool)) or not isinstance(tuning, (int, float, np.integer, np.floating)) or not np.isfinite(tuning):
+        raise ValueError(f'transcribe: tuning must be None, "auto" or a number of cents (got {tuning!r})')
+    return float(tuning)
+
+
 def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False, align_notes=False,
-                        dynamics=False, dynamics_rounds=None, min_level_db=None):
+                        dynamics=False, dynamics_rounds=None, min_level_db=None, tuning=None):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
@@ -93,8 +102,15 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     [None, None] for a note that did not fit the render program) and "agreement_dynamics" (the agreement with the resynthesis at those dynamics),
     where the bar was aligned also "agreement_dynamics_warped"; every window the means of those; "resynthesis" is the render at the estimated
     dynamics.  min_level_db=L: every bar also gains "quiet", one flag per note, True where the level is below L (audio.result_notes leaves those
-    out; the decoded bars keep them).  A level is relative to its window: loudness across windows is not recovered."""
+    out; the decoded bars keep them).  A level is relative to its window: loudness across windows is not recovered.
+    tuning="auto": the recording's tuning is estimated on the device from the features of all its windows as one group (piano_a2s_amd.tuning, DESIGN.md
+    section 27) and the features are shifted back onto the grid at A4 = 440 Hz before the model and the resynthesis comparison see them (a tracker
+    keeps the uncorrected ones); tuning=CENTS (a number): the features are shifted by that much and nothing is estimated.  The result gains "tuning":
+    {"cents", "confidence", "peaks", "determined", "a4_hz"} (a4_hz = 440 * 2^(cents / 1200); with a given number confidence and peaks are None); an
+    estimate that is not determined leaves the features as they are.  One read-back of three doubles per recording.  The resynthesis and the MIDI
+    file stay at 440 Hz.  Any other string: ValueError.  Off, the result has no such key and neither tuning kernel runs."""
     check_downbeats(downbeats, beats_per_bar)
+    tuning = check_tuning(tuning)
     if resynthesis and downbeats is None:
         raise ValueError("transcribe: resynthesis needs downbeats (given or tracked): in fixed windows the decoded bars have no position in the audio")
     if align_notes and not resynthesis:
@@ -127,6 +143,14 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     if not plan:
         return result
     feats = _vqt(device, hparams)(audio.cut_windows(wave, plan, length))
+    if tuning is not None:
+        from . import tuning as tuning_
+        tuner = tuning_.Tuner(device, bins_per_octave=int(_hp(hparams, "bins_per_octave", 60)))
+        feats, est, _ = tuner(feats, first=[0, len(plan)], cents=None if tuning == "auto" else tuning)            # all windows: one group
+        if tuning == "auto":
+            result["tuning"] = tuning_.describe(est[0].cpu().numpy(), tuner.min_conf, tuner.min_peaks)
+        else:
+            result["tuning"] = {"cents": tuning, "confidence": None, "peaks": None, "determined": True, "a4_hz": tuning_.a4_hz(tuning)}
     inv, ts_list = labels.labels_map_inv, time_signatures()
     was_training = core.training
     model.eval()
@@ -311,6 +335,9 @@ def main(argv):
     ap.add_argument("--min_level_db", type=float, default=None, help="with --dynamics: notes whose level is below this are left out of DIR/NAME.mid and "
                     'marked in the bar\'s "quiet"; nothing is dropped from the decoded bars.  No default: the gap between notes that are not in the '
                     "audio and quiet real notes has only been seen on renders")
+    ap.add_argument("--tuning", default=None, metavar="auto|CENTS", help="auto: estimate how far the recording sits from A4 = 440 Hz (in -50 .. 50 cents, "
+                    "one value per recording) and shift the features back before the model sees them; a number: shift by that many cents without "
+                    'estimating; the output gains "tuning".  The resynthesis and the MIDI file stay at 440 Hz')
     ap.add_argument("--device", default="cuda:0")
     a, extra = ap.parse_known_args(argv)
     overrides = {}
@@ -331,6 +358,11 @@ def main(argv):
         ap.error("--dynamics_rounds and --min_level_db belong to --dynamics")
     if a.dynamics_rounds is not None and a.dynamics_rounds < 1:
         ap.error(f"--dynamics_rounds must be at least 1 (got {a.dynamics_rounds})")
+    if a.tuning is not None and a.tuning != "auto":
+        try:
+            a.tuning = float(a.tuning)
+        except ValueError:
+            ap.error(f"--tuning takes `auto` or a number of cents (got {a.tuning!r})")
     a.resynthesis = a.resynthesis or a.align_notes or a.dynamics
     if a.resynthesis and not (a.downbeats or a.track_downbeats):
         ap.error("--resynthesis needs --downbeats or --track_downbeats: in fixed windows the decoded bars have no position in the audio")
@@ -344,7 +376,7 @@ def main(argv):
         x, sr = audio.read_wav(path)
         result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
                                      hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis, align_notes=a.align_notes,
-                                     dynamics=a.dynamics, dynamics_rounds=a.dynamics_rounds, min_level_db=a.min_level_db)
+                                     dynamics=a.dynamics, dynamics_rounds=a.dynamics_rounds, min_level_db=a.min_level_db, tuning=a.tuning)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
         if a.resynthesis:

@@ -13,7 +13,9 @@ E <= 12 dB per clip that leaves the front end's floor where it is, a noise floor
 Wt <= 100 frames and Wf <= 60 bins; the features are re-normalised to their new peak on the GPU, after transposition and tempo; the score stays).
 Optional override of the rendered corpus: ``--synthetic_room=none|train|eval|all [--room_rt60="(lo, hi)" --room_drr_db="(lo, hi)" --room_predelay_ms="(lo, hi)"]``
 (with ``--synthetic_scores=rendered`` only: every clip is heard in a synthetic room of its own -- direct path, pre-delay, decaying diffuse tail, drawn from the
-clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none)."""
+clip's seed and applied to the waveform on the GPU -- in the TRAIN stage, in VALID and TEST, or in all three; the default is none).
+Optional override of all three stages: ``--tuning_correction=true`` (every clip's tuning against A4 = 440 Hz is estimated on the GPU and its features are shifted
+back onto the grid, in TRAIN in front of the augmenters; the stage stats gain ``tuning_abs_cents`` and ``tuning_determined``)."""
 import sys
 
 from piano_a2s_amd.recipe import ASR, sb, synthetic_sets, write_run_summary
