@@ -789,6 +789,10 @@ int a2s_gru_seq_bwd_ranged(void* stream, const float* dout, long do_bstride, lon
                            long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
                            float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes,
                            float* ranges_out, int* ranges_valid);
+/* Bytes of `workspace` (256-byte aligned) with which a2s_gru_seq_fwd and a2s_gru_seq_bwd / _ranged take their fastest path at B clips of width H:
+ * the transposed W_hh, the launch-per-step kernel's scratch and, at H = 256, the persistent launches' granule buffers.  With less the calls still
+ * compute the same values on slower kernels (a2s_debug_get "gru_persist_*_launches" / "gru_step_*_launches" tell which ran).  0: B < 1 or H < 1. */
+size_t a2s_gru_workspace_bytes(int B, int H);
 /* BPTT of the packed staff-embedding bi-GRU; grads: DEVICE array of 8 pointers (same order as gru_w) */
 int a2s_staff_emb_bwd(void* stream, const float* note_emb, const float* const* gru_w, float* const* grads, float* note_emb_grad,
                       const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,

@@ -118,6 +118,10 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "dec_mid_launches")) return a2s_dec_mid_launches();
     if (!strcmp(key, "dec_cmb_launches")) return a2s_dec_cmb_launches();
     if (!strcmp(key, "dec_persist_launches")) return a2s_dec_persist_launches();
+    if (!strcmp(key, "gru_persist_fwd_launches")) return (int)a2s_gru_persist_fwd_launches();
+    if (!strcmp(key, "gru_persist_bwd_launches")) return (int)a2s_gru_persist_bwd_launches();
+    if (!strcmp(key, "gru_step_fwd_launches")) return (int)a2s_gru_step_fwd_launches();
+    if (!strcmp(key, "gru_step_bwd_launches")) return (int)a2s_gru_step_bwd_launches();
     if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
     if (!strcmp(key, "conv_rows16_c20_launches")) return (int)a2s_conv_rows16_c20_launches();
     if (!strcmp(key, "device_cus")) return a2s_device_geometry().cus;
@@ -423,6 +427,7 @@ int a2s_gru_seq_bwd(void* stream, const float* dout, long do_bstride, long do_ts
     return a2s_gru_seq_bwd_impl(ST, dout, do_bstride, do_tstride, out, out_bstride, out_tstride, gates, w_hh, dhn, dgi_all, dgh_shift,
                                 dgh_first, dhbuf, dgh_tmp, B, T, H, reverse, workspace, workspace_bytes, nullptr, nullptr);
 }
+size_t a2s_gru_workspace_bytes(int B, int H) { return a2s_gru_workspace_bytes_impl(B, H); }
 int a2s_gru_seq_bwd_ranged(void* stream, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride, long out_tstride,
                            const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift, float* dgh_first,
                            float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* workspace, size_t workspace_bytes,

@@ -644,6 +644,17 @@ __global__ void transpose_f32(const float* __restrict__ in, float* __restrict__ 
     out[idx] = in[(long)r * cols + c];
 }
 
+// Workspace bytes with which a2s_gru_seq_fwd and a2s_gru_seq_bwd (below) take their fastest path at B clips: W_hh^T at the head (3H x H floats),
+// behind it the larger of the one-launch-per-step kernel's second dgh buffer (B x 3H floats) and the persistent BPTT's granule buffers; the
+// persistent forward launch needs less than the latter and starts at the head.
+size_t a2s_gru_workspace_bytes_impl(int B, int H) {
+    if (B < 1 || H < 1) return 0;
+    const size_t whh_t = sizeof(float) * 3 * (size_t)H * H, step = sizeof(float) * 3 * (size_t)B * H;
+    const size_t pf = a2s_gru_persist_ws_bytes_impl(B, H, 0), pb = a2s_gru_persist_ws_bytes_impl(B, H, 1);
+    const size_t bwd = whh_t + (step > pb ? step : pb);
+    return ((bwd > pf ? bwd : pf) + 255) & ~(size_t)255;
+}
+
 int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, long do_tstride, const float* out, long out_bstride,
                          long out_tstride, const float* gates, const float* w_hh, const float* dhn, float* dgi_all, float* dgh_shift,
                          float* dgh_first, float* dhbuf, float* dgh_tmp, int B, int T, int H, int reverse, float* ws, size_t ws_bytes,

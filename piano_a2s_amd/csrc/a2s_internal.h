@@ -136,6 +136,8 @@ int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t
     const float* save, const float* hprev, long ld_hprev, float* dgi, long ld_dgi, float* dgh_out, float* dgh2,
     long ld_dgh2, float* dhz_out, int R, int H);
 int a2s_skinny_gemm_acc_impl(hipStream_t st, const float* A, long lda, const float* Bt, long ldb, float* Cm, long ldc, int R, int N, int K);
+long a2s_gru_step_fwd_launches(void);
+long a2s_gru_step_bwd_launches(void);
 int a2s_gru_seq_fwd_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh,
     const float* b_hh, float* out, long out_bstride, long out_tstride, float* hbuf, float* gh,
     float* save, float* hn, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);
@@ -199,6 +201,7 @@ int a2s_gru_seq_bwd_impl(hipStream_t st, const float* dout, long do_bstride, lon
 int a2s_staff_emb_bwd_impl(hipStream_t st, const float* note_emb, const float* const* w, float* const* grads_dev, float* note_emb_grad,
     const long long* ids64, const int* ids32, long id_bstride, const long long* lengths, long len_stride,
     const float* dout, long lddo, int col0, const float* hsave, int R, int maxlen, int E, int S);
+size_t a2s_gru_workspace_bytes_impl(int B, int H);
 long a2s_attn_pair_bwd_launches(void);
 
 // ---- a2s_step.hip
@@ -397,6 +400,9 @@ int a2s_note_decoder_fwd_beam_impl(hipStream_t st, const a2s_note_dec_args& a, c
 unsigned* a2s_persist_latch_ptr(void);
 void a2s_persist_latch_set(void* p);
 a2s_device_geom a2s_device_geometry(void);
+size_t a2s_gru_persist_ws_bytes_impl(int B, int H, int bwd);       // granule buffers + header of one persistent launch; 0: shape not supported
+long a2s_gru_persist_fwd_launches(void);
+long a2s_gru_persist_bwd_launches(void);
 bool a2s_gru_seq_fwd_persist_ok(const float* w_hh, const float* gi, int B, int T, int H, float* ws, size_t ws_bytes);
 int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bstride, long gi_tstride, const float* w_hh, const float* b_hh, float* out,
     long out_bstride, long out_tstride, float* save, float* hn, int B, int T, int H, int reverse, float* ws, size_t ws_bytes);

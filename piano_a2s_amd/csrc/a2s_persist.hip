@@ -380,6 +380,11 @@ static size_t a2s_gru_persist_ws_bytes(int B, int H, int bwd) {
     const size_t rb = (size_t)(B + 15) / 16;
     return 256 + ((rb * 16 * sizeof(unsigned) + 255) & ~(size_t)255) + sizeof(u64) * 2 * rb * 16 * (size_t)(bwd ? 3 * H : H);
 }
+size_t a2s_gru_persist_ws_bytes_impl(int B, int H, int bwd) { return a2s_gru_persist_ws_bytes(B, H, bwd); }
+// a2s_debug_get("gru_persist_fwd_launches" / "gru_persist_bwd_launches"): the tests' proof of the path (two host threads issue a layer's directions)
+static long long g_gru_persist_fwd_launches = 0, g_gru_persist_bwd_launches = 0;
+long a2s_gru_persist_fwd_launches(void) { return (long)__atomic_load_n(&g_gru_persist_fwd_launches, __ATOMIC_RELAXED); }
+long a2s_gru_persist_bwd_launches(void) { return (long)__atomic_load_n(&g_gru_persist_bwd_launches, __ATOMIC_RELAXED); }
 // ---- device geometry, abort latch, test hooks (shared with csrc/a2s_dec_persist.hip)
 // The persistent kernels are ordinary launches whose workgroups wait for each other, so every workgroup of a launch must be resident at
 // once.  What the chip offers is asked of the runtime, once per device: compute units visible to this process (a CPX / DPX partition or a CU
@@ -437,6 +442,7 @@ int a2s_gru_seq_fwd_persist_impl(hipStream_t st, const float* gi_all, long gi_bs
                     g_abort_latch, a2s_persist_dbg()};
     hipLaunchKernelGGL(gru_seq_fwd_persist<256>, dim3((H / 16) * nrb), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_seq_fwd_persist");
+    __atomic_fetch_add(&g_gru_persist_fwd_launches, 1LL, __ATOMIC_RELAXED);
     return A2S_OK;
 }
 
@@ -460,6 +466,7 @@ int a2s_gru_seq_bwd_persist_impl(hipStream_t st, const float* dout, long do_bstr
                     g_abort_latch, a2s_persist_dbg()};
     hipLaunchKernelGGL(gru_seq_bwd_persist<256>, dim3((H / 16) * nrb), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_seq_bwd_persist");
+    __atomic_fetch_add(&g_gru_persist_bwd_launches, 1LL, __ATOMIC_RELAXED);
     if (ranges_out) {        // out of the header: the next launch on this workspace zeroes it, while the deferred products may still be waiting to run
         e = hipMemcpyAsync(ranges_out, base + 2 * sizeof(unsigned), 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) A2S_FAIL(A2S_ERR_HIP, "gru_seq_bwd_persist range words: %s", hipGetErrorString(e));

@@ -223,12 +223,19 @@ __global__ __launch_bounds__(256) void gru_bptt_step_fused(GruBpttStep a) {
     }
 }
 
+// a2s_debug_get("gru_step_fwd_launches" / "gru_step_bwd_launches"): launches of gru_step_fwd_fused / gru_bptt_step_fused, the tests' proof of the path
+// (the two directions of a layer are issued from two host threads)
+static long long g_gru_step_fwd_launches = 0, g_gru_step_bwd_launches = 0;
+long a2s_gru_step_fwd_launches(void) { return (long)__atomic_load_n(&g_gru_step_fwd_launches, __ATOMIC_RELAXED); }
+long a2s_gru_step_bwd_launches(void) { return (long)__atomic_load_n(&g_gru_step_bwd_launches, __ATOMIC_RELAXED); }
+
 int a2s_gru_bptt_step_impl(hipStream_t st, const float* dgh, const float* w_hh_t, const float* dhz_in, const float* dout, long ld_dout,
                            const float* save, const float* hprev, long ld_hprev, float* dgi, long ld_dgi, float* dgh_out, float* dgh2,
                            long ld_dgh2, float* dhz_out, int R, int H) {
     GruBpttStep a{dgh, w_hh_t, dhz_in, dout, ld_dout, save, hprev, ld_hprev, dgi, ld_dgi, dgh_out, dgh2, ld_dgh2, dhz_out, R, H};
     hipLaunchKernelGGL(gru_bptt_step_fused, dim3(H / 16, a2s_cdiv(R, 16)), dim3(256), 0, st, a);
     A2S_CHECK_LAUNCH("gru_bptt_step_fused");
+    __atomic_fetch_add(&g_gru_step_bwd_launches, 1LL, __ATOMIC_RELAXED);
     return A2S_OK;
 }
 
@@ -264,6 +271,7 @@ int a2s_gru_seq_fwd_impl(hipStream_t st, const float* gi_all, long gi_bstride, l
             hipLaunchKernelGGL(gru_step_fwd_fused, dim3(H / 16, a2s_cdiv(B, 16)), dim3(256), 0, st, gi_all + (long)t * gi_tstride, gi_bstride, w_hh, b_hh,
                                hp, hq, out + (long)t * out_tstride, out_bstride, save ? save + (long)t * B * 4 * H : nullptr, B, H);
             A2S_CHECK_LAUNCH("gru_step_fwd_fused");
+            __atomic_fetch_add(&g_gru_step_fwd_launches, 1LL, __ATOMIC_RELAXED);
             continue;
         }
         // gh = h W_hh^T + b_hh   (M=B, N=3H, K=H; W_hh is (3H, H): B(k,n) = W[n*H + k])

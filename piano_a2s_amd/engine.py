@@ -426,7 +426,7 @@ class Engine:
         H = self.cfg["hidden_size"]
         dev = x.device
         saved = {"layers": []}
-        gws = [hip.gemm_workspace(B, dev), hip.gemm_workspace(B, dev)]
+        gws = [hip.gru_workspace(B, H, dev), hip.gru_workspace(B, H, dev)]
         streams = encoder_streams(dev, B)        # the two directions of a layer are independent 1201-step chains: one stream each
         inp = x.reshape(B * T, -1)
         finals = []

@@ -580,7 +580,7 @@ def _encoder_bwd(eng, S, G, es, dEnc, d_hidden, B, T):
             hip.gemm(dpre, 1, 2 * H, hfin, H, 1, G["encoder.fc.weight"], 2 * H, H, H, B, beta=1.0, a_off=l * H, c_off=half * H)   # dW += dpre_l^T h_fin
             dhn.append(d)
         _colsum(dpre, 2 * H, G["encoder.fc.bias"], B, H, x_off=l * H)
-    gws = [hip.gemm_workspace(B, dev), hip.gemm_workspace(B, dev)]
+    gws = [hip.gru_workspace(B, H, dev), hip.gru_workspace(B, H, dev)]
     in_amax = hip.absmax(es["layers"][0]["in"])        # max of the ConvStack features (layer 0's input)
     dout = dEnc                                              # gradient wrt layer-1 outputs (B,T,2H)
     for layer in (1, 0):

@@ -184,6 +184,14 @@ def gemm_workspace(rows, device):
     return torch.empty(16 * max(rows, 1) * 2048, dtype=torch.float32, device=device)
 
 
+def gru_workspace(rows, H, device):
+    """Workspace of one direction of an encoder GRU layer (a2s_gru_seq_fwd / a2s_gru_seq_bwd): gemm_workspace(rows), and at least what the library
+    says the recurrences need at that batch (a2s_gru_workspace_bytes: the transposed W_hh, the step kernels' scratch, the persistent launches'
+    granule buffers), so that the backward of a few clips takes the path the forward takes."""
+    floats = (lib().a2s_gru_workspace_bytes(max(rows, 1), H) + 3) // 4
+    return torch.empty(max(16 * max(rows, 1) * 2048, floats), dtype=torch.float32, device=device)
+
+
 def step_workspace(H, E, device):
     """Scratch of the fused few-row decoder step kernels (csrc/a2s_step.hip): flags, ticket counters (must start at zero), logits,
     transposed weight copies."""

@@ -18,7 +18,7 @@ def dev():
 
 
 def _forward(L, hip, dev, gi, w_hh, b_hh, B, T, H, d):
-    ws = torch.empty(max(16 * B * 2048, 3 * H * H + (1 << 20)), dtype=torch.float32, device=dev)      # W_hh^T + the persistent launches' granule buffers
+    ws = hip.gru_workspace(B, H, dev)      # W_hh^T + the persistent launches' granule buffers
     out = torch.zeros(B, T, 2 * H, device=dev)
     hbuf, gh, hn = torch.empty(2, B, H, device=dev), torch.empty(B, 3 * H, device=dev), torch.empty(B, H, device=dev)
     gates = torch.empty(T, B, 4 * H, device=dev)

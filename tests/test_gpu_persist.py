@@ -22,9 +22,17 @@ def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
+_COUNTERS = ("gru_persist_fwd_launches", "gru_persist_bwd_launches", "gru_step_fwd_launches", "gru_step_bwd_launches")
+
+
+def _counters(L):
+    return {k: L.a2s_debug_get(k.encode()) for k in _COUNTERS}
+
+
 def _run_direction(L, hip, dev, gi, w_hh, b_hh, dout, dhn, B, T, H, d, persist):
     hip.check(L.a2s_debug_set(b"gru_persist", 1 if persist else 0), "debug_set")
-    ws = torch.empty(16 * B * 2048, dtype=torch.float32, device=dev)                  # engine.Engine.encoder passes hip.gemm_workspace(B)
+    ws = hip.gru_workspace(B, H, dev)                  # as engine.Engine.encoder and engine_bwd._encoder_bwd size it
+    c0 = _counters(L)
     out = torch.zeros(B, T, 2 * H, device=dev)
     hbuf, gh, hn = torch.empty(2, B, H, device=dev), torch.empty(B, 3 * H, device=dev), torch.empty(B, H, device=dev)
     gates = torch.empty(T, B, 4 * H, device=dev)
@@ -38,6 +46,10 @@ def _run_direction(L, hip, dev, gi, w_hh, b_hh, dout, dhn, B, T, H, d, persist):
                                 hip._p(dgi), hip._p(dghs), hip._p(dgh_first), hip._p(dhbuf), hip._p(dgh_tmp), B, T, H, d, hip._p(ws),
                                 C.c_size_t(ws.numel() * 4)), "bwd")
     torch.cuda.synchronize()
+    # the path taken, forward and backward: one persistent launch each, or one launch per step (the last processed step's gate backward is a kernel of its own)
+    c1 = _counters(L)
+    took = tuple(c1[k] - c0[k] for k in _COUNTERS)
+    assert took == ((1, 1, 0, 0) if persist else (0, 0, T, T - 1)), f"B = {B}, T = {T}, gru_persist = {int(persist)}: launches {dict(zip(_COUNTERS, took))}"
     return dict(out=out[..., d * H:(d + 1) * H].clone(), hn=hn, gates=gates, dgi=dgi, dghs=dghs, dgh_first=dgh_first)
 
 

@@ -22,7 +22,7 @@ def main():
     for d in range(2):
         bufs.append(dict(gi=torch.randn(B, T, 3 * H, device=dev) * 0.5, w=torch.randn(3 * H, H, device=dev) * 0.06, b=torch.zeros(3 * H, device=dev),
                          out=torch.empty(B, T, 2 * H, device=dev), hbuf=torch.empty(2, B, H, device=dev), gh=torch.empty(B, 3 * H, device=dev),
-                         gates=torch.empty(T, B, 4 * H, device=dev), hn=torch.empty(B, H, device=dev), ws=hip.gemm_workspace(B, dev),
+                         gates=torch.empty(T, B, 4 * H, device=dev), hn=torch.empty(B, H, device=dev), ws=hip.gru_workspace(B, H, dev),
                          dout=torch.randn(B, T, 2 * H, device=dev) * 0.01, dgi=torch.empty(B, T, 3 * H, device=dev), dghs=torch.empty(B, T, 3 * H, device=dev),
                          dgh_first=torch.empty(B, 3 * H, device=dev), dhbuf=torch.empty(2, B, H, device=dev), dgh_tmp=torch.empty(B, 3 * H, device=dev)))
 
