@@ -694,6 +694,37 @@ int a2s_tuning_profile(void* stream, const float* x, long x_bstride, long x_rstr
 int a2s_tuning_estimate(void* stream, const long long* hist, const int* first, int G, int B, int bins_per_semitone, double min_conf, int min_peaks,
                         double* est, float* eff_bins);
 int a2s_tuning_launches(void);
+/* ---- resynthesis at the performed timing (csrc/a2s_retime.hip): the two device stages between the DTW paths of a round and its
+ * next render (piano_a2s_amd/resynth.py: refine_timing).  Integers only: the device EQUALS tests/retime_oracle.py.  table: device, S x 4 int32 =
+ * [clip, f0, f1, r] as a2s_dtw_cost takes it; n = f1 - f0, read as 0 where it is outside [0, n_max].
+ * a2s_path_warp: paths = S rows of path_stride int32, row s holding steps[s] cells (i << 16) | j as a2s_dtw_path writes them (i the recording's frame,
+ * j the score's).  A path is TAKEN if n >= 1, n <= steps <= min(2 n - 1, path_stride), its first cell is (0, 0), its last (n - 1, n - 1) and every
+ * step is (1, 1), (1, 0) or (0, 1).  Then, per row s of warp2 (S rows of n_max + 1 int32):
+ *     warp2[j] = (first i matched to j) + (last i matched to j), j < n;      warp2[n] = warp2[n - 1] + 2;      warp2[j] = 2 j, n < j <= n_max
+ * (twice resynth.warp_from_path, and the slope 1 behind the last frame of resynth.warp_time); inverse2 (the same shape, or NULL: not written) is the
+ * same with i and j swapped.  A path that is not taken -- steps = 0, n = 0, a wrong end cell, cells outside [0, n) -- gives the identity 2 j over the
+ * whole row: a reader never sees an uninitialised word.  One workgroup per segment, the first and last cells of the columns and rows in LDS (a cell is
+ * the first of its column when the cell before it has another j, the last when the cell after it has another j), no atomics, one launch.
+ * a2s_retime_events: events = E x 8 int32 [clip, prog_row, seg, bar_start, bar_stop, 0, 0, 0]; programs = B programs of program_rows rows of 8 int32
+ * as a2s_render_notes reads them.  Words 0 (onset) and 1 (length) of row prog_row of clip's program are replaced, with h = hop, the row of warp2 of
+ * segment seg and
+ *     move(t):  p = min(max(t - f0 h, 0), n h);  k = min(p / h, n - 1);  rem = p - k h;
+ *               shift2 = (h - rem) (warp2[k] - 2 k) + rem (warp2[k + 1] - 2 (k + 1));  move = t + floor(shift2 / 2)   (towards -inf; move = t where n = 0)
+ *     on'  = min(clamp(move(onset), bar_start, bar_stop), bar_stop - 1);      end' = clamp(move(onset + length), bar_start, bar_stop);
+ *     len' = max(1, min(max(end' - on', h), bar_stop - on'))
+ * -- resynth.performed_notes in integers: within one sample per edge of it, non-decreasing in t, and the identity warp leaves every onset inside its
+ * bar as it is.  With n <= 4096 and h <= 65535 every step fits an int32.  A row writes NOTHING if clip is outside [0, B), prog_row outside
+ * [1, program_rows), seg outside [0, S), bar_stop <= bar_start, or the program row is a padding row (length <= 0): the table lives on the device and
+ * the entry point reads nothing back, so such a row cannot be refused here (piano_a2s_amd.hip.event_table refuses it on the host table).  One thread
+ * per event, two loads and two stores of the program per event, nothing else of the programs is touched.  Two rows that name the same program row
+ * race; event_table refuses them.  One launch.
+ * Both: no atomics, nothing allocated, no synchronisation, nothing read back; results do not depend on S, E or the place in a table.  Null pointers
+ * (inverse2 excepted), negative counts, n_max outside [1, 4096], path_stride < 1, hop outside [1, 65535]: A2S_ERR_ARG, nothing is launched; S = 0 (or
+ * E = 0) returns 0 and launches nothing.  a2s_retime_launches: launches of the two so far (proof of the path). */
+int a2s_path_warp(void* stream, const int* paths, long path_stride, const int* steps, const int* table, int S, int n_max, int* warp2, int* inverse2);
+int a2s_retime_events(void* stream, const int* warp2, int n_max, const int* table, int S, const int* events, int E, int hop, int* programs, int B,
+                      int program_rows);
+int a2s_retime_launches(void);
 /* Round 6: the two NoteDecoders of a segment (/root/reference/models.py:261-275: decode_notes of the upper and of the lower staff over the same
  * encoder_outputs) issued by ONE host loop on their two streams; while both staves run a step, the step's attention sweep is one launch that reads
  * the encoder outputs once for both (csrc/a2s_seq.hip: attn_fwd_split256_pair).  pair_order / pair_rank: device, n_clips ints -- the clips sorted by

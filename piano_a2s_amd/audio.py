@@ -226,13 +226,13 @@ def write_midi(path, notes, velocity=64):
 
 
 def result_notes(result):
-    """The notes of a transcription result in recording time: every bar's "performed" where it has one (align_notes), its "notes" otherwise
+    """The notes of a transcription result in recording time: every bar's "retimed" where it has one (performed_timing), else its "performed" (align_notes), its "notes" otherwise
     (resynthesis); bars without either give nothing.  A bar with "dynamics" gives every note its velocity as a fourth entry (where it has one), and
     the notes a bar marks in "quiet" are left out."""
     out = []
     for win in result.get("windows", []):
         for bar in win.get("bars", []):
-            notes = [list(n) for n in bar.get("performed", bar.get("notes", []))]
+            notes = [list(n) for n in bar.get("retimed", bar.get("performed", bar.get("notes", [])))]
             if "dynamics" in bar:
                 notes = [n + [d[1]] if d[1] is not None else n for n, d in zip(notes, bar["dynamics"])]
             out += [n for n, q in zip(notes, bar.get("quiet", [False] * len(notes))) if not q]

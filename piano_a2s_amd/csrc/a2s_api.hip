@@ -361,6 +361,14 @@ int a2s_tuning_estimate(void* stream, const long long* hist, const int* first, i
     return a2s_tuning_estimate_impl(ST, hist, first, G, B, bins_per_semitone, min_conf, min_peaks, est, eff_bins);
 }
 int a2s_tuning_launches(void) { return a2s_tuning_launches_impl(); }
+int a2s_path_warp(void* stream, const int* paths, long path_stride, const int* steps, const int* table, int S, int n_max, int* warp2, int* inverse2) {
+    return a2s_path_warp_impl(ST, paths, path_stride, steps, table, S, n_max, warp2, inverse2);
+}
+int a2s_retime_events(void* stream, const int* warp2, int n_max, const int* table, int S, const int* events, int E, int hop, int* programs, int B,
+                      int program_rows) {
+    return a2s_retime_events_impl(ST, warp2, n_max, table, S, events, E, hop, programs, B, program_rows);
+}
+int a2s_retime_launches(void) { return a2s_retime_launches_impl(); }
 int a2s_note_decoder_fwd_pair(void* stream_upper, void* stream_lower, const a2s_note_dec_args* upper, const a2s_note_dec_args* lower,
                               const int* pair_order, const int* pair_rank, const int* pair_n_active, int* steps_done_upper, int* steps_done_lower) {
     if (!upper || !lower) { snprintf(a2s_err_msg, sizeof(a2s_err_msg), "note_decoder_fwd_pair: null args"); return A2S_ERR_ARG; }

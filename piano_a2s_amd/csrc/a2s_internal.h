@@ -366,6 +366,12 @@ int a2s_tuning_estimate_impl(hipStream_t st, const long long* hist, const int* f
                              double* est, float* eff_bins);
 int a2s_tuning_launches_impl(void);
 
+// ---- a2s_retime.hip
+int a2s_path_warp_impl(hipStream_t st, const int* paths, long path_stride, const int* steps, const int* table, int S, int n_max, int* warp2, int* inverse2);
+int a2s_retime_events_impl(hipStream_t st, const int* warp2, int n_max, const int* table, int S, const int* events, int E, int hop, int* programs, int B,
+                           int program_rows);
+int a2s_retime_launches_impl(void);
+
 // ---- a2s_beam.hip
 // argument block of the beam step epilogue (beam_step_finalize): rows = K slots x B clips, row = slot * B + clip
 struct BeamStepArgs {

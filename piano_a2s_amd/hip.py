@@ -971,6 +971,95 @@ def dynamics_launches():
     return int(lib().a2s_dynamics_launches())
 
 
+RETIME_N_MAX = 4096          # frames per segment a2s_path_warp takes (csrc/a2s_retime.hip)
+RETIME_HOP_MAX = 65535       # the largest hop at which a2s_retime_events stays inside an int32
+
+
+def _retime_table(fn, dev_table):
+    _need(torch.is_tensor(dev_table) and dev_table.dtype == torch.int32 and dev_table.is_cuda and dev_table.dim() == 2 and dev_table.shape[1] == 4
+          and dev_table.is_contiguous(), fn, "dev_table", "must be the contiguous int32 table (S, 4) on the device")
+    return dev_table.shape[0]
+
+
+def path_warp(paths, steps, dev_table, n_max, inverse=True):
+    """a2s_path_warp: paths (S, L) int32 and steps (S,) int32 on the device as dtw_segments returns them, dev_table (S, 4) int32 [clip, f0, f1, r] on
+    the same device, n_max >= the longest segment -> (warp2, inverse2), int32 (S, n_max + 1) each on the device (inverse2 None with inverse=False):
+    twice resynth.warp_from_path, warp2[n] = warp2[n - 1] + 2, the identity 2 j behind n and for a path that is not one (include/a2s.h)."""
+    fn = "path_warp"
+    S = _retime_table(fn, dev_table)
+    n_max = int(n_max)
+    _need(1 <= n_max <= RETIME_N_MAX, fn, "n_max", f"must be in 1 .. {RETIME_N_MAX} (got {n_max})")
+    _need(torch.is_tensor(paths) and paths.dtype == torch.int32 and paths.dim() == 2 and paths.shape[0] == S and paths.shape[1] >= 1 and paths.is_contiguous()
+          and paths.device == dev_table.device, fn, "paths", f"must be a contiguous int32 tensor ({S}, L >= 1) on the table's device")
+    _need(torch.is_tensor(steps) and steps.dtype == torch.int32 and tuple(steps.shape) == (S,) and steps.is_contiguous() and steps.device == dev_table.device,
+          fn, "steps", f"must be a contiguous int32 tensor ({S},) on the table's device")
+    warp2 = torch.empty((S, n_max + 1), dtype=torch.int32, device=dev_table.device)
+    inverse2 = torch.empty_like(warp2) if inverse else None
+    if S:
+        check(lib().a2s_path_warp(stream(), _p(paths), paths.shape[1], _p(steps), _p(dev_table), S, n_max, _p(warp2), None if inverse2 is None else _p(inverse2)),
+              "a2s_path_warp")
+    return warp2, inverse2
+
+
+def event_table(rows, n_clips, program_rows, table, device):
+    """The HOST event table of a2s_retime_events, checked and uploaded once: rows (E, 5) or (E, 8) whole numbers [clip, prog_row, seg, bar_start,
+    bar_stop(, 0, 0, 0)]; table: the HOST segment table (S, 3 or 4) [clip, f0, f1(, r)] the warps belong to.  Rows sorted by clip, 0 <= clip <
+    n_clips, 1 <= prog_row < program_rows and no program row named twice (the kernel cannot refuse a row: it reads nothing back), seg = -1 (the event
+    stays where it is) or a row of `table` of the same clip, everything an int32 -> (E, 8) int32 contiguous on `device`."""
+    fn = "event_table"
+    try:
+        r, t = np.asarray(rows), np.asarray(table)
+        whole = all(a.size == 0 or np.issubdtype(a.dtype, np.integer) or bool(np.all(a == np.rint(a))) for a in (r, t))
+    except (TypeError, ValueError):
+        r, t, whole = None, None, False
+    _need(whole, fn, "rows", "and `table` must hold whole numbers")
+    r = r.reshape(0, 8) if r.size == 0 else r
+    t = t.reshape(0, 4) if t.size == 0 else t
+    _need(r.ndim == 2 and r.shape[1] in (5, 8) and bool(np.all(np.abs(r.astype(np.int64)) < 2 ** 31)), fn, "rows", f"must be (E, 5) or (E, 8) int32 values (got {r.shape})")
+    _need(t.ndim == 2 and t.shape[1] in (3, 4), fn, "table", f"must be (S, 3) or (S, 4) (got {t.shape})")
+    r, t = r.astype(np.int64), t.astype(np.int64)
+    S = t.shape[0]
+    _need(int(n_clips) >= 1 and int(program_rows) >= 2, fn, "n_clips", f"and program_rows must be at least 1 and 2 (got {n_clips}, {program_rows})")
+    _need(bool(np.all((r[:, 0] >= 0) & (r[:, 0] < n_clips) & (np.diff(r[:, 0], prepend=0) >= 0))), fn, "rows", f"must be sorted by clip, 0 <= clip < {n_clips}")
+    bad = np.nonzero((r[:, 1] < 1) | (r[:, 1] >= program_rows))[0]
+    _need(bad.size == 0, fn, "rows", f"row {int(bad[0]) if bad.size else 0} names program row {int(r[bad[0], 1]) if bad.size else 0}, outside 1 .. {int(program_rows) - 1}")
+    _need(len(np.unique(r[:, 0] * int(program_rows) + r[:, 1])) == len(r), fn, "rows", "name a program row twice")
+    seg = r[:, 2]
+    fine = (seg >= -1) & (seg < S)
+    listed = fine & (seg >= 0)
+    fine[listed] = t[seg[listed], 0] == r[listed, 0]
+    bad = np.nonzero(~fine)[0]
+    _need(bad.size == 0, fn, "rows", f"row {int(bad[0]) if bad.size else 0} names segment {int(r[bad[0], 2]) if bad.size else 0}: neither -1 nor a row of the table of its clip")
+    out = np.zeros((len(r), 8), dtype=np.int32)
+    out[:, :5] = r[:, :5]
+    return torch.from_numpy(out).to(device)
+
+
+def retime_events(warp2, dev_table, events, hop, programs):
+    """a2s_retime_events, in place: warp2 (S, n_max + 1) int32 of path_warp, dev_table (S, 4) int32, events (E, 8) int32 of event_table (checked
+    there), programs (B, 1 + rows, 8) int32, all contiguous on one device.  Words 0 and 1 (onset, length) of every listed program row are moved
+    through the warp of the row's segment (include/a2s.h); nothing else is written.  Returns programs."""
+    fn = "retime_events"
+    S = _retime_table(fn, dev_table)
+    _need(torch.is_tensor(programs) and programs.dtype == torch.int32 and programs.dim() == 3 and programs.shape[2] == 8 and programs.shape[1] >= 2
+          and programs.is_contiguous() and programs.device == dev_table.device, fn, "programs", "must be contiguous int32 programs (B, 1 + E, 8) on the table's device")
+    _need(torch.is_tensor(warp2) and warp2.dtype == torch.int32 and warp2.dim() == 2 and warp2.shape[0] == S and 2 <= warp2.shape[1] <= RETIME_N_MAX + 1
+          and warp2.is_contiguous() and warp2.device == dev_table.device, fn, "warp2", f"must be a contiguous int32 tensor ({S}, n_max + 1), n_max <= {RETIME_N_MAX}, on the table's device")
+    _need(torch.is_tensor(events) and events.dtype == torch.int32 and events.dim() == 2 and events.shape[1] == 8 and events.is_contiguous()
+          and events.device == dev_table.device, fn, "events", "must be a contiguous int32 tensor (E, 8) on the table's device")
+    hop = int(hop)
+    _need(1 <= hop <= RETIME_HOP_MAX, fn, "hop", f"must be in 1 .. {RETIME_HOP_MAX} (got {hop})")
+    if S and events.shape[0] and programs.shape[0]:
+        check(lib().a2s_retime_events(stream(), _p(warp2), warp2.shape[1] - 1, _p(dev_table), S, _p(events), events.shape[0], hop, _p(programs),
+                                      programs.shape[0], programs.shape[1]), "a2s_retime_events")
+    return programs
+
+
+def retime_launches():
+    """Launches of the two retiming kernels in this process (a2s_retime_launches)."""
+    return int(lib().a2s_retime_launches())
+
+
 TUNING_CELLS = 100           # histogram cells per semitone of the tuning kernels (csrc/a2s_tuning.hip): a row of hist holds TUNING_CELLS + 1 int64
 
 

@@ -30,6 +30,8 @@ DYNAMICS_ROUNDS = 3
 DYNAMICS_FRAMES = 12
 DYNAMICS_BIN_OFFSETS = (0, 60, 95)                   # rint(60 log2 h), h = 1, 2, 3, in bins of a 60-per-octave VQT whose bin 0 is MIDI 21
 LEVEL_DB_RANGE = (-30.0, 12.0)
+# resynthesis at the performed timing: rounds of warp -> retime; round 1 reads the paths of the alignment pass
+RETIME_ROUNDS = 2
 
 
 def bar_ticks(time_signature):
@@ -220,7 +222,48 @@ def estimate_dynamics(programs, x3, vqt, n_samples, rows, first, rounds=DYNAMICS
     return cum
 
 
-def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics=0):
+def event_rows(events, bar_lines, seg_of_bar, clip=0):
+    """The event table of the retiming kernel (include/a2s.h: a2s_retime_events): events (n, 3) [onset, length, midi] in the order of their render
+    program, bar_lines the window's lines in samples, seg_of_bar: per bar the row of the segment table that holds the bar's warp, or -1 (the bar was
+    not aligned: its notes stay) -> (n, 8) int32 [clip, prog_row = index + 1, seg, bar_start, bar_stop, 0, 0, 0].  The bar of an event is the one its
+    onset lies in (a note ON a bar line belongs to the bar that starts there), as in performed_onsets."""
+    events = np.asarray(events, dtype=np.int64).reshape(-1, 3)
+    lines = np.asarray([int(t) for t in bar_lines], dtype=np.int64)
+    if len(lines) < 2 or len(seg_of_bar) != len(lines) - 1:
+        raise ValueError(f"resynth: event_rows needs one segment (or -1) per bar: {len(lines) - 1} bars, {len(seg_of_bar)} entries")
+    bar = np.clip(np.searchsorted(lines, events[:, 0], side="right") - 1, 0, len(lines) - 2)
+    out = np.zeros((len(events), 8), dtype=np.int32)
+    out[:, 0] = clip
+    out[:, 1] = np.arange(1, len(events) + 1)
+    out[:, 2] = np.asarray(seg_of_bar, dtype=np.int64)[bar] if len(events) else 0
+    out[:, 3], out[:, 4] = lines[bar], lines[bar + 1]
+    return out
+
+
+def refine_timing(programs, x3, vqt, n_samples, hop, table, events, paths, steps, rounds=RETIME_ROUNDS):
+    """The device loop of DESIGN.md section 28: programs (B, 1 + E, 8) int32 on the device (their onsets and lengths are UPDATED IN PLACE), x3 the
+    recording's features (B, T, F), table the HOST segment table (S, 4) [clip, f0, f1, band] of the aligned bars, events the device table of
+    hip.event_table over that table, paths / steps the device tensors of the alignment pass's hip.dtw_segments on these programs.  Round 1 turns those
+    paths into warps (hip.path_warp) and moves every event through the warp of its bar (hip.retime_events); every later round renders the programs as
+    they stand, -> VQT -> hip.segment_agreement -> the offsets (sum x - sum y) / cells with torch -> hip.dtw_segments -> warp -> retime, and moves the
+    events from where they now stand.  No per-note or per-path host work and no read-back in between -> words 0 and 1 of every program row,
+    (B, 1 + E, 2) int64 numpy: the one read-back."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 4)
+    dev_table = torch.from_numpy(table.astype(np.int32)).to(programs.device)
+    n_max = max(1, int((table[:, 2] - table[:, 1]).max())) if len(table) else 1
+    cells = torch.from_numpy(((table[:, 2] - table[:, 1]) * x3.shape[2]).astype(np.float64)).to(programs.device)
+    for k in range(int(rounds)):
+        if k:
+            y = vqt(render.render(programs, n_samples))
+            y3 = (y[:, 0] if y.dim() == 4 else y).contiguous()
+            sums = hip.segment_agreement(x3, y3, table)
+            paths, steps, _ = hip.dtw_segments(x3, y3, table, ((sums[:, 0] - sums[:, 1]) / cells).to(torch.float32))
+        warp2, _ = hip.path_warp(paths, steps, dev_table, n_max, inverse=False)
+        hip.retime_events(warp2, dev_table, events, hop, programs)
+    return programs[:, :, :2].cpu().numpy().astype(np.int64)
+
+
+def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics=0, retime=0):
     """windows: per window of a batch a dict with "events" ((n, 3) int64 of score_events) and "bar_lines"; feats: the recording's features of the same
     windows, (W, 1, T, F) or (W, T, F) float32 on the device; vqt: the front end that made them (waveforms (B, N) -> features); hop: its hop length.
     -> (waves: per window the rendered waveform, float32 numpy (n_samples,), or None; agreements: per window a list with one entry per bar, a float in
@@ -237,7 +280,20 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics
     (round 1 reads the unit-amplitude pass; the warp of align is that pass's too and is not recomputed), the levels are read back ONCE, and the
     programs are packed on the host and rendered once more with the final amplitudes, so that pack_program's gain rule keeps |wave| < 1: `waves`
     are then THAT render and dynamics' agreements are scored on it as "agreements" and "agreement_warped" are on the first.  With 0 nothing of this
-    is allocated, launched or returned."""
+    is allocated, launched or returned.
+    retime=R > 0 (needs align, ValueError without) -> one more result behind alignments, retimed: per window None or {"events":
+    (n, 3) int64, the window's events at the PERFORMED timing (same order, same pitches), "agreement": per bar the PLAIN agreement of the recording
+    with the render of those events -- no gather and no warp}.  R rounds of refine_timing move the programs' onsets and lengths on the device, words 0
+    and 1 are read back ONCE, the programs are packed on the host at the moved events (pack_program's gain rule follows the notes' new overlaps) and
+    rendered: `waves` are then THAT render.  With dynamics=K as well, the dynamics rounds run on the retimed programs against the retimed render:
+    a note is read at the same frames of both (fx = fy), the final pack holds the moved events at the estimated amplitudes, `waves` and dynamics'
+    "agreement" are of that render, and dynamics' "agreement_warped" entries are None: the render is at the performed timing already, and the
+    warp of the alignment pass does not belong to it.  "agreements" and alignments stay those of the first, straight pass.  With 0 nothing of this is
+    allocated, launched or returned."""
+    if retime and not align:
+        raise ValueError("resynth: retime moves the notes through the warps of align=True: it needs align")
+    if int(retime) < 0:
+        raise ValueError(f"resynth: retime counts rounds: it must not be negative (got {retime!r})")
     f3 = feats[:, 0] if feats.dim() == 4 else feats
     W, T, F = f3.shape
     if len(windows) != W:
@@ -248,7 +304,8 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics
     live = [w for w, win in enumerate(windows) if len(win["events"])]
     alignments = [[None] * len(a) for a in agreements] if align else None
     levels = [None] * W if dynamics else None
-    result = lambda: (waves, agreements) + ((alignments,) if align else ()) + ((levels,) if dynamics else ())
+    retimed = [None] * W if retime else None
+    result = lambda: (waves, agreements) + ((alignments,) if align else ()) + ((retimed,) if retime else ()) + ((levels,) if dynamics else ())
     if not live:
         return result()
     progs = torch.from_numpy(np.stack([program(windows[w]["events"], n_samples) for w in live])).to(f3.device)
@@ -263,8 +320,13 @@ def resynthesise(windows, feats, vqt, hop, n_samples=None, align=False, dynamics
     for (i, b), row, s in zip(where, seg, sums):
         agreements[live[i]][b] = agreement(s, (int(row[2]) - int(row[1])) * F)
     heard = _align_bars(x3, y3, seg, where, sums, [live[i] for i, _ in where], agreements, alignments) if align else None
+    if retime:
+        wave, progs, y3, windows = _retime(windows, live, progs, x3.contiguous(), vqt, int(hop), n_samples, int(retime), seg, where, heard, retimed)
     if dynamics:
-        wave = _dynamics(windows, live, progs, x3, y3, vqt, int(hop), n_samples, int(dynamics), seg, where, alignments, heard, levels)
+        wave = _dynamics(windows, live, progs, x3, y3, vqt, int(hop), n_samples, int(dynamics), seg, where, None if retime else alignments,
+                         None if retime else heard, levels)
+        for w in live if retime else ():
+            levels[w]["agreement_warped"] = [None] * len(levels[w]["agreement"])
     host = wave.cpu().numpy()
     for i, w in enumerate(live):
         waves[w] = host[i]
@@ -308,7 +370,7 @@ def _dynamics(windows, live, progs, x3, y3, vqt, hop, n_samples, rounds, seg, wh
         for w in live:
             levels[w]["agreement_warped"] = [None] * len(levels[w]["agreement"])
         if heard is not None:
-            index, table4, at = heard
+            index, table4, at = heard[:3]
             z3 = z3.contiguous()
             warped = hip.segment_agreement(x3.contiguous(), z3[torch.arange(z3.shape[0], device=z3.device)[:, None], index], table4[:, :3]).cpu().numpy()
             for k, s, row in zip(at, warped, table4):
@@ -318,7 +380,8 @@ def _dynamics(windows, live, progs, x3, y3, vqt, hop, n_samples, rounds, seg, wh
 
 def _align_bars(x3, y3, seg, where, sums, window_of, agreements, alignments):
     """The align=True half of resynthesise: fills `alignments` for the bars of the table `seg` that have an agreement -> (index: (clips, T) the score
-    frame heard at every recording frame, the aligned bars' table (S', 4), their rows of `seg`), or None where no bar has an agreement."""
+    frame heard at every recording frame, the aligned bars' table (S', 4), their rows of `seg`, (paths, steps) of the DTW as they lie on the device),
+    or None where no bar has an agreement."""
     _, T, F = x3.shape
     x3, y3 = x3.contiguous(), y3.contiguous()          # (the gathered tensor below is contiguous, and both operands share one clip stride)
     rows = [k for k, ((_, b), w) in enumerate(zip(where, window_of)) if agreements[w][b] is not None]
@@ -327,7 +390,8 @@ def _align_bars(x3, y3, seg, where, sums, window_of, agreements, alignments):
     table = np.array([[seg[k][0], seg[k][1], seg[k][2], dtw_band(seg[k][2] - seg[k][1])] for k in rows], dtype=np.int64)
     cells = (table[:, 2] - table[:, 1]) * F
     off = torch.from_numpy(((sums[rows, 0] - sums[rows, 1]) / cells).astype(np.float32)).to(x3.device)
-    paths, steps, totals = (t.cpu().numpy() for t in hip.dtw_segments(x3, y3, table, off))
+    on_device = hip.dtw_segments(x3, y3, table, off)
+    paths, steps, totals = (t.cpu().numpy() for t in on_device)
     index = np.tile(np.arange(T, dtype=np.int64), (x3.shape[0], 1))             # (clips, T): the score frame heard at every recording frame
     found = []
     for k, (clip, f0, f1, _) in enumerate(table):
@@ -340,7 +404,36 @@ def _align_bars(x3, y3, seg, where, sums, window_of, agreements, alignments):
     for k, row, s, n in zip(rows, found, warped, cells):
         row["agreement_warped"] = agreement(s, int(n))
         alignments[window_of[k]][where[k][1]] = row
-    return index, table, rows
+    return index, table, rows, on_device[:2]
+
+
+def _retime(windows, live, progs, x3, vqt, hop, n_samples, rounds, seg, where, heard, retimed):
+    """The retime=R half of resynthesise: fills `retimed` for the live windows -> (the render at the performed timing (len(live), n_samples) on the
+    device, its programs on the device, its features, the windows with their events moved)."""
+    F = x3.shape[2]
+    moved = [np.array(windows[w]["events"], dtype=np.int64).reshape(-1, 3) for w in live]
+    if heard is not None:
+        _, table, at, (paths, steps) = heard
+        seg_of = {where[k]: t for t, k in enumerate(at)}                        # (live window, bar) -> row of the aligned bars' table
+        rows = [event_rows(moved[i], windows[w]["bar_lines"], [seg_of.get((i, b), -1) for b in range(len(windows[w]["bar_lines"]) - 1)], clip=i)
+                for i, w in enumerate(live)]
+        events = hip.event_table(np.concatenate(rows), len(live), progs.shape[1], table, x3.device)
+        words = refine_timing(progs, x3, vqt, n_samples, hop, table, events, paths, steps, rounds)          # (the one read-back)
+        for i, ev in enumerate(moved):
+            ev[:, :2] = words[i, 1:1 + len(ev)]
+    out = list(windows)
+    for i, w in enumerate(live):
+        out[w] = dict(windows[w], events=moved[i])
+    progs = torch.from_numpy(np.stack([program(ev, n_samples) for ev in moved])).to(x3.device)
+    wave = render.render(progs, n_samples)
+    z = vqt(wave)
+    z3 = z[:, 0] if z.dim() == 4 else z
+    sums = hip.segment_agreement(x3, z3, seg).cpu().numpy()
+    for i, w in enumerate(live):
+        retimed[w] = {"events": moved[i], "agreement": [None] * (len(windows[w]["bar_lines"]) - 1)}
+    for (i, b), row, s in zip(where, seg, sums):
+        retimed[live[i]]["agreement"][b] = agreement(s, (int(row[2]) - int(row[1])) * F)
+    return wave, progs, z3, out
 
 
 def mean_agreement(values):

@@ -73,7 +73,7 @@ def check_tuning(tuning):
 
 
 def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, window_seconds=12.0, hop_seconds=None, batch_size=16, hparams, resynthesis=False, align_notes=False,
-                        dynamics=False, dynamics_rounds=None, min_level_db=None, tuning=None):
+                        dynamics=False, dynamics_rounds=None, min_level_db=None, tuning=None, performed_timing=None):
     """Decode the recording x ((frames,) or (frames, channels) at the rate sr) with `model` (models.ScoreTranscription on the GPU), run in evaluation
     mode exactly as the recipe's VALID / TEST stages run it; `constrained_decoding`, `beam_size` (with `beam_length_penalty`) and `alignment` are
     honoured as the caller set them on the module.  hparams: the yaml's geometry (sample_rate, hop_length, max_frame_num, max_bars, VQT keys).
@@ -108,7 +108,15 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
     keeps the uncorrected ones); tuning=CENTS (a number): the features are shifted by that much and nothing is estimated.  The result gains "tuning":
     {"cents", "confidence", "peaks", "determined", "a4_hz"} (a4_hz = 440 * 2^(cents / 1200); with a given number confidence and peaks are None); an
     estimate that is not determined leaves the features as they are.  One read-back of three doubles per recording.  The resynthesis and the MIDI
-    file stay at 440 Hz.  Any other string: ValueError.  Off, the result has no such key and neither tuning kernel runs."""
+    file stay at 440 Hz.  Any other string: ValueError.  Off, the result has no such key and neither tuning kernel runs.
+    performed_timing=R (needs align_notes, ValueError without; 0 or None: off; R < 0: ValueError): the resynthesis itself is moved to the performed
+    timing: R rounds on the device move every note through the warp of its bar and render and align again.  Every bar gains
+    "retimed" ([[onset_s, length_s, midi]] parallel to "notes": where the notes stand after the last round; a note that did not fit the render
+    program keeps its "performed" entry) and "agreement_retimed" (the PLAIN agreement of the recording with the render at that timing), every window
+    the mean; "resynthesis" is that render, and audio.result_notes and the MIDI file take "retimed" before "performed".  "performed",
+    "agreement" and "agreement_warped" keep their values: they describe the first, straight pass.  With dynamics=True the dynamics keys are measured
+    on the retimed render, every note read at the same frames of the recording and the render, and "agreement_dynamics_warped" is None: that render
+    is at the performed timing already."""
     check_downbeats(downbeats, beats_per_bar)
     tuning = check_tuning(tuning)
     if resynthesis and downbeats is None:
@@ -121,6 +129,11 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
         raise ValueError("transcribe: dynamics_rounds and min_level_db belong to dynamics=True")
     if dynamics_rounds is not None and int(dynamics_rounds) < 1:
         raise ValueError(f"transcribe: dynamics_rounds must be at least 1 (got {dynamics_rounds!r})")
+    performed_timing = int(performed_timing or 0)
+    if performed_timing < 0:
+        raise ValueError(f"transcribe: performed_timing counts rounds: it must not be negative (got {performed_timing!r})")
+    if performed_timing and not align_notes:
+        raise ValueError("transcribe: performed_timing moves the notes through the warps of align_notes: it needs align_notes=True")
     core = getattr(model, "module", model)
     device = next(core.parameters()).device
     hop = int(_hp(hparams, "hop_length", 160))
@@ -190,16 +203,17 @@ def transcribe_waveform(model, x, sr, *, downbeats=None, beats_per_bar=None, win
                 batch.append((win, start, lines, up, lo))
             if resynthesis:
                 _resynthesise_batch(resynth, batch, feats[w0:w0 + int(batch_size)], _vqt(device, hparams), hop, rate, result["resynthesis"]["wave"],
-                                    align=align_notes, dynamics=(int(dynamics_rounds or resynth.DYNAMICS_ROUNDS) if dynamics else 0), min_level_db=min_level_db)
+                                    align=align_notes, dynamics=(int(dynamics_rounds or resynth.DYNAMICS_ROUNDS) if dynamics else 0), min_level_db=min_level_db,
+                                    retime=performed_timing)
     finally:
         model.train(was_training)
     return result
 
 
-def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=False, dynamics=0, min_level_db=None):
+def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=False, dynamics=0, min_level_db=None, retime=0):
     """The resynthesis of one batch of windows [(window dict, start sample, bar lines, upper rows, lower rows)]: fills the windows' and bars' new keys
     and adds the renders into `total` (the recording-long waveform) at the windows' starts.  align: also the keys of align_notes; dynamics: the
-    rounds of the dynamics estimate (0: off) and its keys."""
+    rounds of the dynamics estimate (0: off) and its keys; retime: the rounds of performed_timing (0: off) and its keys."""
     windows, bar_notes = [], []
     for win, start, lines, up, lo in batch:
         lines = lines[:win["n_bars"] + 1]
@@ -211,8 +225,8 @@ def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=Fals
             bar["notes"] = [[(start + int(o)) / rate, int(n) / rate, int(m)] for o, n, m in notes]
             bar_notes.append(notes)
         windows.append({"events": events, "bar_lines": lines})
-    waves, agreements, *more = resynth.resynthesise(windows, feats, vqt, hop, align=align, dynamics=dynamics)
-    alignments, levels = more[0] if align else None, more[-1] if dynamics else None
+    waves, agreements, *more = resynth.resynthesise(windows, feats, vqt, hop, align=align, dynamics=dynamics, retime=retime)
+    alignments, levels, retimed = more[0] if align else None, more[-1] if dynamics else None, more[1] if retime else None
     bar_notes = iter(bar_notes)
     for k, ((win, start, lines, *_), w, agr) in enumerate(zip(batch, waves, agreements)):
         for i, (bar, a) in enumerate(zip(win["bars"], agr)):
@@ -226,11 +240,26 @@ def _resynthesise_batch(resynth, batch, feats, vqt, hop, rate, total, align=Fals
         win["agreement"] = resynth.mean_agreement(agr)
         if align:
             win["agreement_warped"] = resynth.mean_agreement([bar["agreement_warped"] for bar in win["bars"]])
+        if retime:
+            _retimed_keys(resynth, win, retimed[k], start, rate)
         if dynamics:
             _dynamics_keys(resynth, win, levels[k], align, min_level_db)
         if w is not None and start < len(total):
             n = min(len(w), len(total) - start)
             total[start:start + n] += w[:n]
+
+
+def _retimed_keys(resynth, win, rt, start, rate):
+    """The keys of performed_timing of one window: rt is the window's entry of resynthesise's retimed (None for a window without a note).  The window's
+    events are its bars' notes in order, cut at the render program's length."""
+    at = 0
+    for i, bar in enumerate(win["bars"]):
+        n = len(bar["notes"])
+        have = 0 if rt is None else max(0, min(n, len(rt["events"]) - at))
+        bar["retimed"] = [[(start + int(o)) / rate, int(ln) / rate, int(m)] for o, ln, m in (rt["events"][at:at + have] if have else [])] + [list(p) for p in bar["performed"][have:]]
+        bar["agreement_retimed"] = None if rt is None else rt["agreement"][i]
+        at += n
+    win["agreement_retimed"] = resynth.mean_agreement([bar["agreement_retimed"] for bar in win["bars"]])
 
 
 def _dynamics_keys(resynth, win, lv, align, min_level_db):
@@ -328,6 +357,9 @@ def main(argv):
     ap.add_argument("--align_notes", action="store_true", help="implies --resynthesis: warp the resynthesis onto the recording inside every bar; every bar "
                     'gains "agreement_warped" and "performed" (its notes where they are heard), and DIR/NAME.mid holds the performed notes as a '
                     "Standard MIDI File (format 0, 1 ms ticks, velocity 64)")
+    ap.add_argument("--performed_timing", type=int, nargs="?", const=2, default=0, metavar="R", help="implies --align_notes: move the resynthesis itself to "
+                    'the performed timing in R rounds (default 2) of warp, retime, render and align on the device; every bar gains "retimed" and '
+                    '"agreement_retimed", DIR/NAME.resynth.wav plays the score in time with the recording and DIR/NAME.mid holds the retimed notes')
     ap.add_argument("--dynamics", action="store_true", help="implies --resynthesis: estimate every note's loudness from the recording by analysis by "
                     'synthesis; every bar gains "dynamics" ([level_db, velocity] per note, relative to the window\'s median note) and '
                     '"agreement_dynamics", DIR/NAME.resynth.wav plays the score at those dynamics and DIR/NAME.mid carries the velocities')
@@ -363,6 +395,9 @@ def main(argv):
             a.tuning = float(a.tuning)
         except ValueError:
             ap.error(f"--tuning takes `auto` or a number of cents (got {a.tuning!r})")
+    if a.performed_timing < 0:
+        ap.error(f"--performed_timing counts rounds: it must not be negative (got {a.performed_timing})")
+    a.align_notes = a.align_notes or a.performed_timing > 0
     a.resynthesis = a.resynthesis or a.align_notes or a.dynamics
     if a.resynthesis and not (a.downbeats or a.track_downbeats):
         ap.error("--resynthesis needs --downbeats or --track_downbeats: in fixed windows the decoded bars have no position in the audio")
@@ -376,7 +411,8 @@ def main(argv):
         x, sr = audio.read_wav(path)
         result = transcribe_waveform(model, x, sr, downbeats=downbeats, beats_per_bar=a.beats_per_bar, window_seconds=a.window_seconds,
                                      hop_seconds=a.hop_seconds, batch_size=a.batch_size, hparams=hp, resynthesis=a.resynthesis, align_notes=a.align_notes,
-                                     dynamics=a.dynamics, dynamics_rounds=a.dynamics_rounds, min_level_db=a.min_level_db, tuning=a.tuning)
+                                     dynamics=a.dynamics, dynamics_rounds=a.dynamics_rounds, min_level_db=a.min_level_db, tuning=a.tuning,
+                                     performed_timing=a.performed_timing)
         result["audio"] = os.path.basename(path)
         out = os.path.join(a.out, os.path.splitext(os.path.basename(path))[0] + ".json")
         if a.resynthesis:

@@ -80,7 +80,8 @@ def _bar_lines(clip, bars):
 def _batch_agreement(ds, first, heard, feats, front, up_ids, lo_ids, ts_ids):
     """Bar agreements of one evaluation batch: clip b of the batch was decoded from the audio of clip first + heard[b] of `ds` (features feats[b]), so
     its decoded bars are laid on THAT clip's bar lines -> (agreements of the decoded scores, of the heard clips' own scores, warped agreements of the
-    decoded scores), one entry per bar, None where a bar has none."""
+    decoded scores, plain agreements of the decoded scores rendered at the performed timing (section 28)), one entry per bar,
+    None where a bar has none."""
     from piano_a2s_amd import resynth, scoregen
     sigs = scoregen.time_signatures()
     dec, gt = [], []
@@ -91,9 +92,11 @@ def _batch_agreement(ds, first, heard, feats, front, up_ids, lo_ids, ts_ids):
         ev = resynth.score_events(_unpad_rows(up_ids[b]), _unpad_rows(lo_ids[b]), [sigs[int(t)] for t in ts_ids[b]], lines)[0]
         dec.append({"events": ev, "bar_lines": lines})
         gt.append({"events": resynth.score_events(clip["ids"]["upper"], clip["ids"]["lower"], [clip["time_sig"]] * bars, lines)[0], "bar_lines": lines})
-    _, plain, aligned = resynth.resynthesise(dec, feats, front, scoregen.HOP, align=True)
+    _, plain, aligned, retimed = resynth.resynthesise(dec, feats, front, scoregen.HOP, align=True, retime=resynth.RETIME_ROUNDS)
     flat = lambda rows: [a for row in rows for a in row]
-    return flat(plain), flat(resynth.resynthesise(gt, feats, front, scoregen.HOP)[1]), [None if a is None else a["agreement_warped"] for a in flat(aligned)]
+    moved = flat([[None] * len(p) if r is None else r["agreement"] for p, r in zip(plain, retimed)])
+    return (flat(plain), flat(resynth.resynthesise(gt, feats, front, scoregen.HOP)[1]), [None if a is None else a["agreement_warped"] for a in flat(aligned)],
+            moved)
 
 
 def _decode(model, ds, args, dev, front, permute, constrained, K):
@@ -104,7 +107,7 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
     model.constrained_decoding, model.beam_size, model.alignment = constrained, K, False
     pred = {k: {} for k in ("up", "lo", "key", "ts")}
     target = {k: {} for k in ("up", "lo", "key", "ts")}
-    agr_dec, agr_gt, agr_warped, first = [], [], [], 0
+    agr_dec, agr_gt, agr_warped, agr_retimed, first = [], [], [], [], 0
     with torch.no_grad():
         for batch in _batches(ds, args.eval_batch, 0):
             f = _features(batch, dev, front, permute)
@@ -116,7 +119,8 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
             if args.resynthesis:
                 n = len(batch[7])
                 heard = [(b - 1) % n if permute else b for b in range(n)]          # (_features rolls the audio by one clip)
-                d, g, w = _batch_agreement(ds, first, heard, f[0], front, up_ids, lo_ids, ts_o.argmax(-1).cpu().numpy())
+                d, g, w, r = _batch_agreement(ds, first, heard, f[0], front, up_ids, lo_ids, ts_o.argmax(-1).cpu().numpy())
+                agr_retimed += r
                 agr_dec += d
                 agr_gt += g
                 agr_warped += w
@@ -140,6 +144,7 @@ def _decode(model, ds, args, dev, front, permute, constrained, K):
         from piano_a2s_amd import resynth
         out["bar_agreement_decoded"], out["bar_agreement_ground_truth"] = resynth.mean_agreement(agr_dec), resynth.mean_agreement(agr_gt)
         out["bar_agreement_warped_decoded"] = resynth.mean_agreement(agr_warped)
+        out["bar_agreement_retimed_decoded"] = resynth.mean_agreement(agr_retimed)
         out["bars"], out["bars_without_agreement_decoded"] = len(agr_dec), sum(a is None for a in agr_dec)
     return out
 
