@@ -90,6 +90,7 @@ int a2s_debug_set(const char* key, int value) {
     if (!strcmp(key, "attn_deferred_fast")) { a2s_attn_deferred_fast = value ? 1 : 0; return A2S_OK; }
     if (!strcmp(key, "tallk_wgrad")) { a2s_tallk_wgrad_on = value ? 1 : 0; return A2S_OK; }
     if (!strcmp(key, "tallk_wgrad_max_splits")) { a2s_tallk_wgrad_max_splits = value > 0 ? value : 0; return A2S_OK; }
+    if (!strcmp(key, "conv_rows_stage")) { a2s_conv_rows_stage = value & 3; return A2S_OK; }
     if (!strcmp(key, "gemm_tile")) { a2s_gemm_debug_tile_impl(value); return A2S_OK; }          // write-only
     snprintf(a2s_err_msg, sizeof(a2s_err_msg), "a2s_debug_set: unknown key %s", key);
     return A2S_ERR_ARG;
@@ -124,6 +125,8 @@ int a2s_debug_get(const char* key) {
     if (!strcmp(key, "gru_step_bwd_launches")) return (int)a2s_gru_step_bwd_launches();
     if (!strcmp(key, "edit_distance_launches")) return (int)a2s_edit_distance_launches();
     if (!strcmp(key, "conv_rows16_c20_launches")) return (int)a2s_conv_rows16_c20_launches();
+    if (!strcmp(key, "conv_rows_stage")) return a2s_conv_rows_stage;
+    if (!strcmp(key, "conv_rows_stage_launches")) return (int)a2s_conv_rows_stage_launches();
     if (!strcmp(key, "device_cus")) return a2s_device_geometry().cus;
     if (!strcmp(key, "device_xccs")) return a2s_device_geometry().xccs;
     return -1;

@@ -703,7 +703,11 @@ __device__ __forceinline__ float rw_rol4(float x) {
 // fills set t & 1 while the df-combination, scaling, stores and statistics of row t - 1 -- set (t - 1) & 1, complete since the last barrier --
 // are issued between its k-steps, one m-tile per k-step.  A wave issues one MFMA per ~32 clocks when two waves share a SIMD: the ~350 vector
 // instructions of an epilogue ride in the issue slots in between.  The barrier per row stays (ring slot hand-off, boundary rows).
-template <int CIN, int COUT, bool AFFINE, bool BNRED, bool PIPE = false>
+// SN ("stage narrow", a2s_debug_set("conv_rows_stage")): the input rows are loaded, converted and written to the ring by waves 4-7 alone (items
+// e = (tid - 256) + 256 it).  Those waves carry a third of the MFMAs and of the epilogue of waves 0-3, and every SIMD holds one of each: the row time
+// is the wide wave's, which now issues fragment reads, MFMAs and its epilogue only.  Which thread converts an element is all that changes: same
+// arithmetic, same ring image, same barriers.
+template <int CIN, int COUT, bool AFFINE, bool BNRED, bool PIPE = false, bool SN = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     using G = RwGeom<CIN>;
     using N = R16Geom<COUT>;
@@ -712,7 +716,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     // second weight term in LDS instead of registers: the two-set form, and the 20 -> 20 data gradient (138 registers otherwise: with the 24 of the
     // term back it stays under 128, and two workgroups share a CU -- the instance has little else to cover its barrier per row with)
     constexpr bool B1L = PIPE || (CIN == 20 && COUT == 20 && BNRED);
-    constexpr int XIT = (G::ITEMS + NTHR - 1) / NTHR;
+    constexpr int NSTG = SN ? 256 : NTHR;                 // threads that stage the input rows
+    constexpr int XIT = (G::ITEMS + NSTG - 1) / NSTG;
     __shared__ __attribute__((aligned(16))) unsigned char ring[R16_SLOTS * G::SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char b1img[B1L ? N::NTILES * G::KS * 1024 : 16];      // second fp16 term of the weights: [tile][k-step][lane x 16 B]
     // accumulator rows that cross the boundary between neighbouring column ranges of a channel group, as TRUE values (sign undone):
@@ -724,7 +729,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
     __shared__ float tab[(AFFINE ? 2 * CIN : 0) + (BNRED ? 4 * COUT : 0) + 4];
     // where the threads without an item in the last staging round put their (meaningless) 8 + 8 bytes: the conversion then has no
     // branch, and the scheduler can weave it between the MFMAs
-    __shared__ __attribute__((aligned(16))) unsigned char dump[(G::ITEMS % NTHR) ? NTHR * 16 : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char dump[(G::ITEMS % NSTG) ? NSTG * 16 : 16];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -801,28 +806,31 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             rw_block<CIN>(8 * s + 4 * r + g, dt, cb);
             aaddr[s][r] = (unsigned)(dt * G::SLOT + (4 * cb + q / 4) * RW_SROW + (q % 4) * 8 + m0 * 32);
         }
-    // ---- staging: every thread, items e = tid + NTHR it (channel e >> 5, positions 4 (e & 31) ..)
+    // ---- staging: every thread (SN: those of waves 4-7), items e = stid + NSTG it (channel e >> 5, positions 4 (e & 31) ..)
+    const bool stager = !SN || !wide;                    // wave-uniform
+    const int stid = SN ? tid - (NTHR - NSTG) : tid;
     const float* __restrict__ xclip = a.x + (long)b * a.T * CIN * a.F;
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xclip), 0, (unsigned)((long)a.T * CIN * a.F * 4), 0x00020000);
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const int fcol = f_base - 4 + 4 * (tid & 31);
-    const bool colok = fcol >= 0 && fcol < a.F;          // (NTHR is a multiple of 32: the column group is the same for all items of a thread)
+    const bool colok = fcol >= 0 && fcol < a.F;          // (NSTG is a multiple of 32: the column group is the same for all items of a thread)
     auto issue = [&](int row, f32x4 (&xr)[XIT]) {
+        if (!stager) return;
         const int rbase = row * CIN * a.F + f_base - 4;
-        int tl = tid;
+        int tl = stid;
         asm volatile("" : "+v"(tl));
 #pragma unroll
         for (int it = 0; it < XIT; ++it) {
-            const int e = tl + NTHR * it;
+            const int e = tl + NSTG * it;
             const int goff = (e >> 5) * a.F + 4 * (e & 31) + rbase;
             xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (colok && e < G::ITEMS) ? goff * 4 : -4, 0, 0));
         }
     };
     auto commit_item = [&](int it, bool ok, unsigned char* base, const f32x4& x) {
-        int tl = tid;
+        int tl = stid;
         asm volatile("" : "+v"(tl));
-        const int e = tl + NTHR * it;
-        const bool has = (it + 1) * NTHR <= G::ITEMS || e < G::ITEMS;
+        const int e = tl + NSTG * it;
+        const bool has = (it + 1) * NSTG <= G::ITEMS || e < G::ITEMS;
         const int ch = has ? e >> 5 : 0;
         unsigned char* const p0 = has ? base + ch * RW_SROW + (e & 31) * 8 : dump + tl * 16;
         unsigned char* const p1 = has ? p0 + G::TS : p0 + 8;
@@ -894,9 +902,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             // (the conversion has no branch: the compiler's scheduler weaves it and the next k-step's fragment reads between the MFMAs.
             // Measured without gain: explicit sched_group_barrier interleaving, hand double-buffered fragments -- 244 registers in the
             // data-gradient instance, slower.)
+            if constexpr (!SN || NT == NNT) {      // (SN: the narrow waves' instantiation)
 #pragma unroll
-            for (int it = 0; it < XIT; ++it)
-                if (it * KS / XIT == s) commit_item(it, cok, cbase, xr[it]);
+                for (int it = 0; it < XIT; ++it)
+                    if (it * KS / XIT == s) commit_item(it, cok, cbase, xr[it]);
+            }
         }
     };
     auto advance = [&]() {
@@ -988,8 +998,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         issue(t_lo - 1 + r, xa);
+        if (stager) {
 #pragma unroll
-        for (int it = 0; it < XIT; ++it) commit_item(it, t_lo - 1 + r >= 0 && t_lo - 1 + r < a.T && colok, ring + r * G::SLOT, xa[it]);
+            for (int it = 0; it < XIT; ++it) commit_item(it, t_lo - 1 + r >= 0 && t_lo - 1 + r < a.T && colok, ring + r * G::SLOT, xa[it]);
+        }
     }
     issue(t_lo + 2, xa);
     __syncthreads();
@@ -1094,25 +1106,33 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
                     R16P_PRODUCT(0, bw[d][s][0])
 #undef R16P_PRODUCT
                 }
+                if constexpr (!SN || !WIDE) {
 #pragma unroll
-                for (int it = 0; it < XIT; ++it)
-                    if (it * KS / XIT == s) commit_item(it, cok, cbase, xr[it]);
+                    for (int it = 0; it < XIT; ++it)
+                        if (it * KS / XIT == s) commit_item(it, cok, cbase, xr[it]);
+                }
                 // the previous row's epilogue, spread over the k-steps
 #pragma unroll
                 for (int i = 0; i < NM; ++i)
                     if (i * KS / NM == s) epi_tile(WIDEc, std::integral_constant<int, 1 - CUR>{}, i, t_e, xl, xr_, ob, ylt[(BNRED && NM > KS) ? i - s * NM / KS : 0]);
             }
         };
+        // The rows of the strip.  ROLE 0: one loop, the wave's role tested per row.  SN: a loop of its own per role (1: wide, 2: narrow) with the SAME
+        // sequence of barriers -- one per row -- so that the staged row's registers (xa) are live in the narrow waves' code only.
+        auto rows_p = [&](auto ROLEc) {
+        constexpr int ROLE = decltype(ROLEc)::value;
+        const bool w = ROLE == 0 ? wide : ROLE == 1;
+        const int nmr = ROLE == 0 ? nm : ROLE == 1 ? WNM : 2;
         int slot_w = 3;
         auto row = [&](auto CURc, int t) {
             constexpr int CUR = decltype(CURc)::value;
-            if (wide) multiply_p(std::true_type{}, CURc, t - 1, t + 2, slot_w, xa);
+            if (w) multiply_p(std::true_type{}, CURc, t - 1, t + 2, slot_w, xa);
             else multiply_p(std::false_type{}, CURc, t - 1, t + 2, slot_w, xa);
-            const float d2first = wide ? accp[CUR][0][2][0] : dterm2(std::false_type{}, accp[CUR][0][0], accp[CUR][0][1], accp[CUR][0][2], 0);
-            if (bnd_r >= 0 && g == 3) xch[CUR][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? accp[CUR][WNM - 1][0][3] : accp[CUR][1][0][3]) * sg;
+            const float d2first = w ? accp[CUR][0][2][0] : dterm2(std::false_type{}, accp[CUR][0][0], accp[CUR][0][1], accp[CUR][0][2], 0);
+            if (bnd_r >= 0 && g == 3) xch[CUR][bnd_r >= 0 ? bnd_r : 0][0][q] = (w ? accp[CUR][WNM - 1][0][3] : accp[CUR][1][0][3]) * sg;
             if (bnd_l >= 0 && g == 0) xch[CUR][bnd_l >= 0 ? bnd_l : 0][1][q] = d2first * sg;
             __syncthreads();
-            issue(t + 3, xa);
+            if (ROLE != 1) issue(t + 3, xa);
             slot_w = slot_w == R16_SLOTS - 1 ? 0 : slot_w + 1;
             advance();
         };
@@ -1132,15 +1152,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
             asm volatile("" : "+v"(ob));
 #pragma unroll
             for (int i = 0; i < WNM; ++i) {
-                if (i < nm) {
+                if (i < nmr) {
                     const f32x4 ylt = BNRED ? yl_tile(i, t_hi - 1) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if (wide) { if (last) epi_tile(std::true_type{}, C1{}, i, t_hi - 1, xl, xr_, ob, ylt); else epi_tile(std::true_type{}, C0{}, i, t_hi - 1, xl, xr_, ob, ylt); }
+                    if (w) { if (last) epi_tile(std::true_type{}, C1{}, i, t_hi - 1, xl, xr_, ob, ylt); else epi_tile(std::true_type{}, C0{}, i, t_hi - 1, xl, xr_, ob, ylt); }
                     else if (i < 2) { if (last) epi_tile(std::false_type{}, C1{}, i < 2 ? i : 0, t_hi - 1, xl, xr_, ob, ylt); else epi_tile(std::false_type{}, C0{}, i < 2 ? i : 0, t_hi - 1, xl, xr_, ob, ylt); }
                 }
             }
         }
+        };
+        if constexpr (SN) {
+            if (wide) rows_p(std::integral_constant<int, 1>{});
+            else rows_p(std::integral_constant<int, 2>{});
+        } else rows_p(std::integral_constant<int, 0>{});
     } else {
-    int slot_w = 3, par = 0;
 #ifdef RW_TRACE
     const int rp = wave & 1, ng = wave >> 1;  // (stamp slots: [workgroup][column half][iteration], waves 0 / 1 = channel group 0)
     const int trace_first = (int)gridDim.x / 2;
@@ -1148,30 +1172,40 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows16(RowsArgs a) {
 #endif
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
     using IW = std::integral_constant<int, WNM>; using INt = std::integral_constant<int, NNT>;
+    // (ROLE: as in the two-set form above -- 0: one loop for both roles; SN: one loop per role, one barrier per row in each)
+    auto rows = [&](auto ROLEc) {
+    constexpr int ROLE = decltype(ROLEc)::value;
+    const bool w = ROLE == 0 ? wide : ROLE == 1;
+    int slot_w = 3, par = 0;
     for (int t = t_lo; t < t_hi; ++t) {
 #ifdef RW_TRACE
         const int trace_it = t - t_lo - 40;
 #endif
         RW_STAMP(0);
         yl_fetch(t);
-        if (wide) multiply(IW{}, I3{}, t + 2, slot_w, xa);
+        if (w) multiply(IW{}, I3{}, t + 2, slot_w, xa);
         else multiply(I2{}, INt{}, t + 2, slot_w, xa);
         RW_STAMP(1);
         // boundary rows for the neighbouring column ranges (lanes of 4-row group 3 / 0 hold them), as true values
-        const float d2first = wide ? acc[0][2][0] : dterm2(std::false_type{}, acc[0][0], acc[0][1], acc[0][2], 0);
-        if (bnd_r >= 0 && g == 3) xch[par][bnd_r >= 0 ? bnd_r : 0][0][q] = (wide ? acc[WNM - 1][0][3] : acc[1][0][3]) * sg;
+        const float d2first = w ? acc[0][2][0] : dterm2(std::false_type{}, acc[0][0], acc[0][1], acc[0][2], 0);
+        if (bnd_r >= 0 && g == 3) xch[par][bnd_r >= 0 ? bnd_r : 0][0][q] = (w ? acc[WNM - 1][0][3] : acc[1][0][3]) * sg;
         if (bnd_l >= 0 && g == 0) xch[par][bnd_l >= 0 ? bnd_l : 0][1][q] = d2first * sg;
         __syncthreads();
         RW_STAMP(2);
-        if (wide) epilogue(std::true_type{}, t, par);
+        if (w) epilogue(std::true_type{}, t, par);
         else epilogue(std::false_type{}, t, par);
         RW_STAMP(3);
-        issue(t + 3, xa);
+        if (ROLE != 1) issue(t + 3, xa);
         RW_STAMP(4);
         slot_w = slot_w == R16_SLOTS - 1 ? 0 : slot_w + 1;
         par ^= 1;
         advance();
     }
+    };
+    if constexpr (SN) {
+        if (wide) rows(std::integral_constant<int, 1>{});
+        else rows(std::integral_constant<int, 2>{});
+    } else rows(std::integral_constant<int, 0>{});
     }
 
     // ---- statistics: a column's four 4-row groups, then the column ranges of the group
@@ -1228,19 +1262,49 @@ size_t a2s_conv_rows_workspace_floats(int Cin) {
 static long long g_rows16_c20_launches = 0;          // conv3x3_rows16<*, 20> launches of this process (a2s_debug_get("conv_rows16_c20_launches"): the tests' proof of the path)
 long a2s_conv_rows16_c20_launches(void) { return (long)__atomic_load_n(&g_rows16_c20_launches, __ATOMIC_RELAXED); }
 
+// "conv_rows_stage" (a key beside the switch list, a2s_switches.h) -- bit 0: the instances listed in rows16_stage_narrow run their SN form (waves 4-7
+// stage the input rows); 0 = every thread stages.  Bit 1 (with bit 0): the 40 -> 40 data gradient runs its two-accumulator-set form, which fits the
+// registers in the SN form only.  "conv_rows_stage_launches" counts the SN launches (the tests' proof of the path).
+int a2s_conv_rows_stage = 3;
+static long long g_rows_stage_launches = 0;
+long a2s_conv_rows_stage_launches(void) { return (long)__atomic_load_n(&g_rows_stage_launches, __ATOMIC_RELAXED); }
+// The instances whose SN form is built and selected: those it is faster for by the project's rule (medians apart by more than the larger spread,
+// profiles/conv_rows_stage_b256.txt); the others keep the all-thread form and their SN variant is not compiled.
+//   * 20 -> 20 data gradient: slower (8.41 -> 8.77 ms at B = 256: its narrow waves, with 12 MFMAs per row, have nothing to hide three items' conversion under);
+//   * 40 -> 20 data gradient with two accumulator sets: no difference by the rule (and slower than its one-set SN form either way);
+//   * 20 -> 40 data gradient: no layer of the model launches it, so nothing was measured.
+// (-DR16_SN_ALL builds every SN variant, for measuring them again.)
+constexpr bool rows16_stage_narrow(int cin, int cout, bool affine, bool bnred, bool pipe) {
+#ifdef R16_SN_ALL
+    return true;
+#else
+    return !(bnred && ((cin == 20 && cout == 20) || (cin == 20 && cout == 40) || (cin == 40 && cout == 20 && pipe)));
+#endif
+}
+
+template <int CIN, int COUT, bool AFFINE, bool BNRED, bool PIPE>
+static void rows16_launch_form(hipStream_t st, const RowsArgs& a, int nwork) {
+    if constexpr (rows16_stage_narrow(CIN, COUT, AFFINE, BNRED, PIPE)) {
+        if (a2s_conv_rows_stage & 1) {
+            __atomic_fetch_add(&g_rows_stage_launches, 1LL, __ATOMIC_RELAXED);
+            hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, AFFINE, BNRED, PIPE, true>), dim3(nwork), dim3(512), 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, AFFINE, BNRED, PIPE, false>), dim3(nwork), dim3(512), 0, st, a);
+}
 template <int CIN, int COUT>
 static int rows16_launch(hipStream_t st, const RowsArgs& a, bool affine, bool bnred, int nwork) {
-    constexpr int NT = 512;
     if (COUT == 20) __atomic_fetch_add(&g_rows16_c20_launches, 1LL, __ATOMIC_RELAXED);
     // the two-accumulator-set form (round 6): bit 2 the forward instances, bit 3 the data-gradient instance (24 spilled registers at 40 -> 40)
     // (20 -> 20 has one form only: a second accumulator set costs it the 128 registers at which two workgroups share a CU -- measured slower)
     constexpr bool SETS2 = !(CIN == 20 && COUT == 20);
     const int en = SETS2 ? a2s_sw(A2S_SW_conv_rows) : 0;
-    if (affine && (en & 4)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false, SETS2>), dim3(nwork), dim3(NT), 0, st, a);
-    else if (affine) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, true, false>), dim3(nwork), dim3(NT), 0, st, a);
-    else if (bnred && (en & 8)) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true, SETS2>), dim3(nwork), dim3(NT), 0, st, a);
-    else if (bnred) hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, true>), dim3(nwork), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_rows16<CIN, COUT, false, false>), dim3(nwork), dim3(NT), 0, st, a);
+    if (affine && (en & 4)) rows16_launch_form<CIN, COUT, true, false, SETS2>(st, a, nwork);
+    else if (affine) rows16_launch_form<CIN, COUT, true, false, false>(st, a, nwork);
+    else if (bnred && ((en & 8) || (CIN == 40 && COUT == 40 && (a2s_conv_rows_stage & 3) == 3))) rows16_launch_form<CIN, COUT, false, true, SETS2>(st, a, nwork);
+    else if (bnred) rows16_launch_form<CIN, COUT, false, true, false>(st, a, nwork);
+    else rows16_launch_form<CIN, COUT, false, false, false>(st, a, nwork);
     A2S_CHECK_LAUNCH("conv3x3_rows16");
     return A2S_OK;
 }

@@ -96,6 +96,8 @@ bool a2s_conv_rows_eligible(int F, int Cin);
 int a2s_conv_rows_blocks(int B, int T, int F);
 size_t a2s_conv_rows_workspace_floats(int Cin);
 long a2s_conv_rows16_c20_launches(void);
+extern int a2s_conv_rows_stage;                     // the key "conv_rows_stage" beside the switch list (a2s_switches.h)
+long a2s_conv_rows_stage_launches(void);
 int a2s_conv3x3_rows_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
     const float* in_absmax, float* stat_partial, float* out_absmax, int B, int T, int F, int Cin, int Cout, int flip,
     float* ws, const float* yl, const float* yl_mean, const float* yl_invstd, const float* yl_scale, const float* yl_shift,

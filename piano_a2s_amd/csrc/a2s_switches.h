@@ -68,12 +68,15 @@
     X(persist_inject_abort, 0, ONOFF, 0)
 // Not in the list, because they are not stored integers (a2s_debug_set / a2s_debug_get, a2s_api.hip): "gemm_tile" is write-only
 // (a2s_gemm_debug_tile); the "*_launches" counters and "device_cus" / "device_xccs" are read-only.
-// Two on/off keys are kept beside the list, because the list is a recorded contract (tests/test_switches_cpu.py spells its keys out):
+// Three keys are kept beside the list, because the list is a recorded contract (tests/test_switches_cpu.py spells its keys out):
 // "attn_deferred_fast" (default 1; a2s_attn_deferred_fast, a2s_bwd.hip) -- the deferred attention gradients on attn_dk_accum_ahead and
 // attn_denc_accum; 0 = attn_dk_accum and the batched GEMM.  No environment variable.
 // "tallk_wgrad" (default 1; a2s_tallk_wgrad_on, a2s_linear.hip) -- the encoder GRU's weight gradients and the attention key products on
 // a2s_tallk_wgrad (a2s_tallk_wgrad_eligible answers 0 while it is off); 0 = the generic split-K GEMM and the column-sum passes.  No environment variable.
 // Its test aid "tallk_wgrad_max_splits" (default 0 = no cap) bounds the kernel's split over the rows, so that a small shape runs long row ranges.
+// "conv_rows_stage" (bits, default 3; a2s_conv_rows_stage, a2s_conv_rows.hip) -- bit 0: conv3x3_rows16 stages its input rows with the narrow-group waves
+// alone (the instances of rows16_stage_narrow; bit-identical results); 0 = every thread stages.  Bit 1 (with bit 0): the 40 -> 40 data gradient with two
+// accumulator sets.  "conv_rows_stage_launches" counts the narrow-staging launches (read-only).  No environment variable.
 
 enum a2s_switch {
 #define X(key, def, rule, env) A2S_SW_##key,

@@ -3,7 +3,10 @@ data gradient with the BatchNorm-backward statistics epilogue, plain data gradie
 the tiled kernels of round 2 (`conv_rows` = 0).  usage: python tools/conv_rows_check.py [B] [--no-check] [--no-time]
 --ab [--out FILE]: instead, the three 20-output-channel launches of the training step, one launch per HIP-event pair (packing pre-kernel
 included), alternating between the `conv_rows` settings (7 = rows16, 5 = the first-generation kernel for the same launch; 3 / 15 = rows16 with
-one accumulator set / with two sets for the data gradient as well): median and spread per launch and setting."""
+one accumulator set / with two sets for the data gradient as well): median and spread per launch and setting.
+--ab --stage [--out FILE]: the six rows16 launches of the training step under `conv_rows` = 7, alternating `conv_rows_stage` 0 / 1 / 3 (every thread
+stages the input rows / the narrow-group waves do / ... and the 40 -> 40 data gradient runs with two accumulator sets).  ROWS=3 / 15 in the environment
+selects the other `conv_rows` forms; --plain measures the plain flip launches (no statistics: not part of the training step) instead."""
 import os
 import sys
 
@@ -147,13 +150,28 @@ def bench(B):
         del x, y, yl
 
 
-def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
+AB_LAUNCHES_C20 = ((40, 20, "dgrad_ranged", "conv3 dgrad 40->20 bnstats+absmax"), (20, 20, "dgrad", "conv2 dgrad 20->20 bnstats"),
+                   (20, 20, "fwd", "conv2 fwd 20->20 affine+stats"))
+AB_LAUNCHES_C40 = ((20, 40, "fwd", "conv3 fwd 20->40 affine+stats"), (40, 40, "fwd", "conv4 fwd 40->40 affine+stats"),
+                   (40, 40, "dgrad_ranged", "conv4 dgrad 40->40 bnstats+absmax"))
+
+
+AB_LAUNCHES_PLAIN = ((40, 40, "flip", "plain flip 40->40"), (40, 20, "flip", "plain flip 40->20"), (20, 40, "flip", "plain flip 20->40"),
+                     (20, 20, "flip", "plain flip 20->20"))
+
+
+def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10, stage=False, plain=False):
+    """stage: the settings are values of `conv_rows_stage` under `conv_rows` = 7, over all six launches."""
     T, F = 1201, 480
-    lines = [f"B = {B}, T = {T}, F = {F}; {warm} warm-up + {iters} timed launches per setting, alternating; ms per launch (packing pre-kernel included)",
-             f"{'launch':34s} {'conv_rows':>9s} {'median':>8s} {'min':>8s} {'max':>8s} {'spread':>8s}"]
+    key = b"conv_rows_stage" if stage else b"conv_rows"
+    restore = L.a2s_debug_get(key) if stage else ROWS
+    if stage:
+        settings = (0, 1, 3)
+        hip.check(L.a2s_debug_set(b"conv_rows", ROWS), "set")
+    lines = [f"conv_rows = {ROWS}; B = {B}, T = {T}, F = {F}; {warm} warm-up + {iters} timed launches per setting, alternating; ms per launch (packing pre-kernel included)",
+             f"{'launch':34s} {key.decode():>15s} {'median':>8s} {'min':>8s} {'max':>8s} {'spread':>8s}"]
     verdicts = []
-    for ci, co, mode, what in ((40, 20, "dgrad_ranged", "conv3 dgrad 40->20 bnstats+absmax"), (20, 20, "dgrad", "conv2 dgrad 20->20 bnstats"),
-                               (20, 20, "fwd", "conv2 fwd 20->20 affine+stats")):
+    for ci, co, mode, what in (AB_LAUNCHES_PLAIN if plain else AB_LAUNCHES_C40 + AB_LAUNCHES_C20 if stage else AB_LAUNCHES_C20):
         fwd = mode == "fwd"
         x = torch.randn(B, T, ci, F, device=dev) * (1.0 if fwd else 1e-4)
         y = torch.empty(B, T, co, F, device=dev)
@@ -163,7 +181,7 @@ def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
         in_amax = x.abs().amax(dim=(0, 1, 3)).contiguous()
         out_amax = torch.zeros(co, device=dev)
         xmax = hip.absmax(x)
-        yl = None if fwd else torch.randn(B, T, co, F, device=dev)
+        yl = None if fwd or mode == "flip" else torch.randn(B, T, co, F, device=dev)
         bn = [torch.randn(co, device=dev) * 0.1, torch.rand(co, device=dev) + 0.5, torch.rand(co, device=dev) + 0.5, torch.randn(co, device=dev) * 0.1]
         partial = torch.empty(L.a2s_conv3x3_stat_blocks(B, T, F, ci), co, 2, device=dev)
         if fwd:
@@ -171,6 +189,8 @@ def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
         elif mode == "dgrad":
             fn = lambda: hip.check(L.a2s_conv3x3_dgrad_bnstats_scaled(hip.stream(), hip._p(x), hip._p(w), hip._p(y), hip._p(yl), hip._p(bn[0]), hip._p(bn[1]),
                                                                       hip._p(bn[2]), hip._p(bn[3]), hip._p(partial), B, T, F, ci, co, hip._p(cws), hip._p(xmax)), "dgrad")
+        elif mode == "flip":          # (measures max |x| itself: one more pass, the same under every setting)
+            fn = lambda: hip.check(L.a2s_conv3x3(hip.stream(), hip._p(x), hip._p(w), hip._p(y), None, None, None, B, T, F, ci, co, 1, hip._p(cws)), "flip")
         else:
             fn = lambda: hip.check(L.a2s_conv3x3_dgrad_bnstats_ranged(hip.stream(), hip._p(x), hip._p(w), hip._p(y), hip._p(yl), hip._p(bn[0]), hip._p(bn[1]),
                                                                       hip._p(bn[2]), hip._p(bn[3]), hip._p(partial), B, T, F, ci, co, hip._p(cws), hip._p(xmax),
@@ -178,7 +198,7 @@ def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
         times = {r: [] for r in settings}
         for k in range(warm + iters):
             for rows in settings:
-                hip.check(L.a2s_debug_set(b"conv_rows", rows), "set")
+                hip.check(L.a2s_debug_set(key, rows), "set")
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 fn()
@@ -186,14 +206,20 @@ def ab(B, out=None, settings=(7, 5, 3, 15), warm=3, iters=10):
                 torch.cuda.synchronize()
                 if k >= warm:
                     times[rows].append(e0.elapsed_time(e1))
-        hip.check(L.a2s_debug_set(b"conv_rows", ROWS), "set")
+        hip.check(L.a2s_debug_set(key, restore), "set")
         stat = {}
         for rows in settings:
             t = sorted(times[rows])
             stat[rows] = (t[len(t) // 2], t[0], t[-1])
-            lines.append(f"{what:34s} {rows:9d} {stat[rows][0]:8.3f} {t[0]:8.3f} {t[-1]:8.3f} {t[-1] - t[0]:8.3f}")
+            lines.append(f"{what:34s} {rows:15d} {stat[rows][0]:8.3f} {t[0]:8.3f} {t[-1]:8.3f} {t[-1] - t[0]:8.3f}")
             print(lines[-1], flush=True)
-        if 7 in stat and 5 in stat:
+        for new in ((1, 3) if stage else ()):          # narrow-wave staging against every thread staging (3: only the 40 -> 40 data gradient differs from 1)
+            if new == 3 and not (ci == 40 and co == 40 and not fwd):
+                continue
+            d = stat[0][0] - stat[new][0]
+            spread = max(stat[0][2] - stat[0][1], stat[new][2] - stat[new][1])
+            verdicts.append(f"{what}: conv_rows_stage {new} - 0 = {-d:+.3f} ms, larger spread {spread:.3f} ms -> {'faster' if d > spread else 'slower' if -d > spread else 'no difference'}")
+        if not stage and 7 in stat and 5 in stat:
             d = stat[5][0] - stat[7][0]
             spread = max(stat[5][2] - stat[5][1], stat[7][2] - stat[7][1])
             verdicts.append(f"{what}: rows16 (7) - first generation (5) = {-d:+.3f} ms, larger spread {spread:.3f} ms -> {'faster' if d > spread else 'slower' if -d > spread else 'no difference'}")
@@ -213,7 +239,9 @@ if __name__ == "__main__":
         if "--out" in sys.argv:
             out = sys.argv[sys.argv.index("--out") + 1]
             args.remove(out)
-        ab(int(args[0]) if args else 256, out)
+        ab(int(args[0]) if args else 256, out, stage="--stage" in sys.argv, plain="--plain" in sys.argv)
+        if "--stage" in sys.argv:
+            hip.check(L.a2s_debug_set(b"conv_rows", ROWS), "set")
         sys.exit(0)
     if "--no-check" not in sys.argv:
         check()
