@@ -190,6 +190,13 @@ int a2s_bn_finalize(void* stream, const float* partial, int nblocks, int C, doub
                     float* mean, float* invstd, float* scale, float* shift, float eps, float momentum, int training);
 int a2s_bn_relu_apply(void* stream, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F);
 int a2s_col_stats(void* stream, const float* x, float* partial, long rows, int C, int rows_per_block);
+/* Column sums and sums of squares of x (rows, C) accumulated in double and written as two fp32 terms: partial[2 * nblocks][C][2] with
+ * nblocks = ceil(rows / rows_per_block) -- entries [0, nblocks) the fp32 heads, [nblocks, 2 nblocks) the remainders.  a2s_bn_finalize over
+ * 2 * nblocks entries then has the sums to ~48 bits: the variance of a few nearly equal rows is not lost in 2^-24 mean^2. */
+/* z (M, N) = relu(x * scale[k / period] + shift[k / period]) W^T for contiguous x (M, K) and W (N, K), products and sums in double (K % period == 0):
+ * the ConvStack's Linear in a training call of few rows, whose BatchNorm1d returns an error of z up to 1 / sqrt(eps) = 316-fold. */
+int a2s_linear_fwd_f64(void* stream, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period);
+int a2s_col_stats_split(void* stream, const float* x, float* partial, long rows, int C, int rows_per_block);
 int a2s_bn1d_relu_dropout(void* stream, const float* x, float* y, const float* scale, const float* shift,
                           const uint8_t* keep_mask, float inv_keep, long n, int C);
 

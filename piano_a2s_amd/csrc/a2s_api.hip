@@ -180,6 +180,12 @@ int a2s_bn_finalize(void* stream, const float* partial, int nblocks, int C, doub
 int a2s_bn_relu_apply(void* stream, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F) {
     return a2s_bn_relu_apply_impl(ST, x, y, scale, shift, n, C, F);
 }
+int a2s_linear_fwd_f64(void* stream, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period) {
+    return a2s_linear_fwd_f64_impl(ST, M, N, K, x, W, z, scale, shift, period);
+}
+int a2s_col_stats_split(void* stream, const float* x, float* partial, long rows, int C, int rows_per_block) {
+    return a2s_col_stats_split_impl(ST, x, partial, rows, C, rows_per_block);
+}
 int a2s_col_stats(void* stream, const float* x, float* partial, long rows, int C, int rows_per_block) {
     return a2s_col_stats_impl(ST, x, partial, rows, C, rows_per_block);
 }

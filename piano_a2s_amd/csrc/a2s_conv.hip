@@ -1039,6 +1039,50 @@ __global__ __launch_bounds__(256) void col_stats_partial(const float* __restrict
     }
 }
 
+// The same sums kept in double and written as TWO fp32 terms: entry blockIdx.x holds the fp32 heads of the block's sums, entry nblocks + blockIdx.x
+// what the heads left over.  bn_finalize adds the 2 * nblocks entries in double and gets the sums to ~48 bits, so var = E[x^2] - mean^2 stays exact
+// where the variance is far below mean^2 (few rows with nearly equal values: an fp32 sum of squares is off by 2^-24 mean^2 there, which against
+// var + eps = 1e-5 was 0.7 % of invstd in a two-row call).
+__global__ __launch_bounds__(256) void col_stats_partial_split(const float* __restrict__ x, float* __restrict__ partial,
+                                                               long rows, int C, int rows_per_block) {
+    const long r0 = (long)blockIdx.x * rows_per_block;
+    const long r1 = min(rows, r0 + rows_per_block);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double s = 0.0, s2 = 0.0;
+        for (long r = r0; r < r1; ++r) { const double v = (double)x[r * C + c]; s += v; s2 += v * v; }
+        const float sh = (float)s, s2h = (float)s2;
+        float* head = partial + ((long)blockIdx.x * C + c) * 2;
+        float* rest = partial + (((long)gridDim.x + blockIdx.x) * C + c) * 2;
+        head[0] = sh; head[1] = s2h;
+        rest[0] = (float)(s - (double)sh); rest[1] = (float)(s2 - (double)s2h);
+    }
+}
+
+// z[m][n] = sum_k relu(x[m][k] * scale[k / period] + shift[k / period]) W[n][k] with the products and the sum in double: the Linear of a call of
+// few rows.  Its BatchNorm1d in training mode divides by sqrt(var + 1e-5) of a handful of values, so an error of z comes back up to 316-fold in
+// scale and shift (two rows whose z agree to 0.03: 2e3 x the error of z0 - z1 in shift); the fp32 accumulation of the GEMM kernels (1.4e-6 of
+// max |z| over K = 5120) is then what the statistics show.  One workgroup per output element; a few-row call is far too small to care.
+__global__ __launch_bounds__(256) void linear_fwd_f64(const float* __restrict__ x, const float* __restrict__ W, float* __restrict__ z,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift, int period, int K, int N) {
+    const int n = blockIdx.x, m = blockIdx.y;
+    const float* xr = x + (long)m * K;
+    const float* wr = W + (long)n * K;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int c = k / period;
+        const float a = fmaxf(fmaf(xr[k], scale[c], shift[c]), 0.f);
+        acc = fma((double)a, (double)wr[k], acc);
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) z[(long)m * N + n] = (float)red[0];
+}
+
 // y[r,c] = relu(x[r,c]*scale[c]+shift[c]) (* dropout mask/keep when mask != null)
 __global__ void bn1d_relu_dropout(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ scale,
                                   const float* __restrict__ shift, const uint8_t* __restrict__ mask, float inv_keep,
@@ -1198,6 +1242,19 @@ int a2s_bn_relu_apply_impl(hipStream_t st, const float* x, float* y, const float
     return A2S_OK;
 }
 
+int a2s_linear_fwd_f64_impl(hipStream_t st, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period) {
+    A2S_REQUIRE(x && W && z && scale && shift, "linear_fwd_f64: null tensor");
+    A2S_REQUIRE(M > 0 && M <= 65535 && N > 0 && K > 0 && period > 0 && K % period == 0, "linear_fwd_f64: unsupported shape M=%d N=%d K=%d period=%d", M, N, K, period);
+    hipLaunchKernelGGL(linear_fwd_f64, dim3(N, M), dim3(256), 0, st, x, W, z, scale, shift, period, K, N);
+    A2S_CHECK_LAUNCH("linear_fwd_f64");
+    return A2S_OK;
+}
+int a2s_col_stats_split_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block) {
+    A2S_REQUIRE(x && partial && rows > 0 && C > 0 && rows_per_block > 0, "col_stats_split: null tensor or empty shape");
+    hipLaunchKernelGGL(col_stats_partial_split, dim3(a2s_cdiv(rows, rows_per_block)), dim3(256), 0, st, x, partial, rows, C, rows_per_block);
+    A2S_CHECK_LAUNCH("col_stats_partial_split");
+    return A2S_OK;
+}
 int a2s_col_stats_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block) {
     hipLaunchKernelGGL(col_stats_partial, dim3(a2s_cdiv(rows, rows_per_block)), dim3(256), 0, st, x, partial, rows, C, rows_per_block);
     A2S_CHECK_LAUNCH("col_stats_partial");

@@ -67,6 +67,8 @@ int a2s_bn_finalize_impl(hipStream_t st, const float* partial, int nblocks, int 
     float* invstd, float* scale, float* shift, float eps, float momentum, int training);
 int a2s_bn_relu_apply_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F);
 int a2s_col_stats_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
+int a2s_linear_fwd_f64_impl(hipStream_t st, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period);
+int a2s_col_stats_split_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
 int a2s_bn1d_relu_dropout_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift,
     const uint8_t* mask, float inv_keep, long n, int C);
 size_t a2s_conv3x3_wgrad_workspace_bytes_impl(int Cin, int Cout);

@@ -404,14 +404,24 @@ class Engine:
         a4 = None
         # two-term fp16 split: activations scaled by the power of two of their bound, the weights by that of max|W|
         saved["w_out_amax"] = hip.absmax(S["convstack.out.weight"])
-        z = hip.linear_forward(y4, S["convstack.out.weight"], (scale, shift, F), saved["abound"][3], saved["w_out_amax"])
         rows = B * T
         rpb = 64
         nblk = (rows + rpb - 1) // rpb
+        # A training call of one row block (at most 64 rows) is ill-conditioned in its BatchNorm1d: with few rows a channel's values can agree so closely
+        # that its variance lies far below mean^2 and beside eps, and scale / shift then carry an error of z up to 316-fold.  Such a call takes the Linear
+        # and the sums of its statistics in double (a2s_linear_fwd_f64; a2s_col_stats_split hands a2s_bn_finalize two fp32 terms per sum: an fp32 sum of
+        # squares lost 0.7 % of invstd in a two-row call).  Longer calls keep the two-term Linear and the fp32 sums, and with them the bits of every
+        # earlier recording.
+        split = nblk == 1
+        if training and split:
+            z = hip.linear_forward_f64(y4, S["convstack.out.weight"], (scale, shift, F))
+        else:
+            z = hip.linear_forward(y4, S["convstack.out.weight"], (scale, shift, F), saved["abound"][3], saved["w_out_amax"])
         partial = None
         if training:
+            nblk = 2 if split else nblk
             partial = self._empty(nblk, Cf, 2, dev=dev)
-            hip.check(L.a2s_col_stats(hip.stream(), hip._p(z), hip._p(partial), rows, Cf, rpb), "a2s_col_stats")
+            hip.check((L.a2s_col_stats_split if split else L.a2s_col_stats)(hip.stream(), hip._p(z), hip._p(partial), rows, Cf, rpb), "a2s_col_stats")
         mean, invstd, scale, shift = self._bn(S, "convstack.out_bn", partial, nblk, Cf, float(rows), training)
         out = self._empty(rows, Cf, dev=dev)
         hip.check(L.a2s_bn1d_relu_dropout(hip.stream(), hip._p(z), hip._p(out), hip._p(scale), hip._p(shift), hip._p(drop_mask), 1.0 / 0.8, out.numel(), Cf),

@@ -1328,6 +1328,14 @@ def linear_forward(x2d, weight, x_affine, x_bound, w_absmax, out=None):
     return linear(x2d, weight, out=out, x_affine=x_affine, two_term=(x_bound, w_absmax))
 
 
+def linear_forward_f64(x2d, weight, x_affine):
+    """The same Linear with products and sums in double (a2s_linear_fwd_f64): what Engine.convstack takes in a training call of at most 64 rows."""
+    M, K = x2d.shape
+    out = torch.empty((M, weight.shape[0]), dtype=torch.float32, device=x2d.device)
+    check(lib().a2s_linear_fwd_f64(stream(), M, weight.shape[0], K, _p(x2d), _p(weight), _p(out), _p(x_affine[0]), _p(x_affine[1]), x_affine[2]), "a2s_linear_fwd_f64")
+    return out
+
+
 def linear_wgrad(dz, x2d, x_affine, dz_absmax, x_bound, G):
     """G (N, K) += dz^T relu(bn(x)) for the ConvStack's 19200 -> 256 Linear on the kernel of csrc/a2s_linear.hip; returns False when the shape
     does not qualify (hip.LINEAR_KERNELS off: never) -- the caller then runs the generic split-K GEMM."""

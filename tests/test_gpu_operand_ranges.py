@@ -637,8 +637,10 @@ ALL_OFF = dict(conv_rows=0, conv_bf16x3=0, wgrad_rows=0, wgrad_bf16x3=0, wgrad_f
 @gpu
 @pytest.mark.parametrize("paths", ["default", "split operands off", "row kernels off"])
 def test_convstack_range_chain_with_every_layer_at_another_magnitude(dev, paths):
-    """Engine.convstack(training) + engine_bwd._convstack_bwd at B 3, T 23, F 128 (row kernels and the three Linear kernels eligible) with the
-    BatchNorm gammas of CHAIN_GAMMAS: the ranges the forward saved are the exact maxima / the a2s_act_bound formula, and output and parameter
+    """Engine.convstack(training) + engine_bwd._convstack_bwd at B 3, T 23, F 128 -- row kernels eligible; of the three Linear kernels the forward
+    and the weight gradient are, the data gradient is not (69 rows < its 128-row block: _assert_chain_shape_eligibility), so the plan's lin.dgrad
+    is "generic", the gradient entering layer 4 carries no range and layer 4 takes the "apply" form; the "own" -> layer-4 "rows" hand-off is
+    tests/test_gpu_convstack_call.py's -- with the BatchNorm gammas of CHAIN_GAMMAS: the ranges the forward saved are the exact maxima / the a2s_act_bound formula, and output and parameter
     gradients are finite and within 2e-4 of max |ref| of a float64 autograd restatement (the bar of test_small_model_all_gradients) -- with the
     default paths, with every split-operand path off (the data is not simply ill-conditioned; the fp32 figure on the CPU is in
     test_reference_helpers_against_autograd), and with the tiled two-term convolutions in place of the row kernels (conv_rows = 0: they get the
@@ -646,6 +648,7 @@ def test_convstack_range_chain_with_every_layer_at_another_magnitude(dev, paths)
     from piano_a2s_amd import engine, engine_bwd, hip
     cfg, st, x, d_out, out64, grads64, _ = _chain_ref64()
     B, T, F = CHAIN_SHAPE
+    _assert_chain_shape_eligibility()
     off = paths == "split operands off"
     prev_linear = hip.LINEAR_KERNELS
     try:
@@ -683,6 +686,21 @@ def test_convstack_range_chain_with_every_layer_at_another_magnitude(dev, paths)
     assert not failures, (paths, failures)
 
 
+def _assert_chain_shape_eligibility():
+    """What the library answers for the Linear at CHAIN_SHAPE (69 rows, K = 40 F = 5120, N = 256), so that the docstrings below cannot drift from it:
+    its forward and weight-gradient kernels take the shape, its data-gradient kernel does not, and every conv2-conv4 shape is eligible for the
+    row-streaming fused weight gradient."""
+    from piano_a2s_amd import hip
+    from piano_a2s_amd.conv_bwd_plan import CHANS
+    L = hip.lib()
+    B, T, F = CHAIN_SHAPE
+    rows, Cf = B * T, 256
+    assert L.a2s_linear_fwd_eligible(rows, Cf, 40 * F, F) == 1
+    assert L.a2s_linear_wgrad_eligible(rows, Cf, 40 * F, F) == 1
+    assert L.a2s_linear_dgrad_eligible(rows, 40 * F, Cf, F) == 0 and L.a2s_linear_dgrad_eligible(128, 40 * F, Cf, F) == 1
+    assert all(L.a2s_conv3x3_wgrad_bn_ranged_eligible(F, *c) == 1 for c in CHANS[1:])
+
+
 HOST_VARIANTS = {"_FUSE_BN_ROWS": False, "_DGRAD_BNSTATS": False, "_FUSE_BN_APPLY": True, "_FUSE_BN_APPLY_L1": False}
 
 
@@ -691,11 +709,12 @@ HOST_VARIANTS = {"_FUSE_BN_ROWS": False, "_DGRAD_BNSTATS": False, "_FUSE_BN_APPL
 def test_convstack_range_chain_on_the_host_variants(dev, attr):
     """The same chain, same float64 reference and same 2e-4 bar with one switch of engine_bwd (conv_bwd_plan.ConvBwdFlags) off its default: the
     BatchNorm-backward apply as a pass of its own, the plain data gradients with statistics passes of their own, the apply inside the tiled
-    weight gradient of every layer, and of none.  At 69 rows the Linear's statistics epilogue and the row kernels are eligible, so each variant
-    changes the launches."""
+    weight gradient of every layer, and of none.  At 69 rows the Linear's statistics epilogue (on the generic GEMM tiles: the Linear's own data
+    gradient needs 128 rows, _assert_chain_shape_eligibility) and the row kernels are eligible, so each variant changes the launches."""
     from piano_a2s_amd import engine, engine_bwd
     cfg, st, x, d_out, out64, grads64, _ = _chain_ref64()
     B, T, F = CHAIN_SHAPE
+    _assert_chain_shape_eligibility()
     prev = getattr(engine_bwd, attr)
     try:
         setattr(engine_bwd, attr, HOST_VARIANTS[attr])

@@ -380,6 +380,55 @@ def test_bn_finalize_matches_oracle_batch_norm(dev, training):
         assert _rel(Bd[k].float(), Bf[k].float()) < 1e-5, k
 
 
+@pytest.mark.parametrize("M,N,K,period", [(1, 5, 24, 24), (2, 256, 5120, 128), (64, 7, 1300, 130), (3, 256, 19200, 480)])
+def test_linear_fwd_f64_against_float64(dev, M, N, K, period):
+    """a2s_linear_fwd_f64: relu(x scale + shift) W^T with the activation formed in fp32 (one fma, as every consumer of y4 forms it) and the products
+    and sums in double -- against float64 from the same fp32 activation: what is left is the rounding of the fp32 result, 2^-24 |z| per element."""
+    from piano_a2s_amd import hip
+    g = torch.Generator().manual_seed(M + N + K)
+    x, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
+    ch = K // period
+    scale = (torch.rand(ch, generator=g) + 0.5) * torch.where(torch.arange(ch) % 3 == 0, -1.0, 1.0)
+    shift = torch.randn(ch, generator=g) * 0.3
+    a = torch.relu(torch.addcmul(shift.double().repeat_interleave(period), x.double(), scale.double().repeat_interleave(period)).float())      # fl(x scale + shift): the fma
+    ref = a.double() @ w.double().t()
+    z = hip.linear_forward_f64(x.to(dev), w.to(dev), (scale.to(dev), shift.to(dev), period))
+    torch.cuda.synchronize()
+    err = float(((z.cpu().double() - ref).abs() / ref.abs().clamp_min(1e-3)).max())
+    _report(f"linear_fwd_f64 ({M}, {N}, {K}) period {period} (relative to max(|ref|, 1e-3))", err)
+    assert err <= 2.0 ** -23, err
+
+
+@pytest.mark.parametrize("n", [2, 63, 130])
+def test_col_stats_split_keeps_a_variance_far_below_the_mean(dev, n):
+    """a2s_col_stats_split + a2s_bn_finalize over its 2 * nblocks entries on columns whose rows are nearly equal (mean ~ 3, spread 1e-3: variance 1e-6
+    against mean^2 = 9 and eps = 1e-5, what the BatchNorm1d of a two-row ConvStack call meets): mean and invstd against float64 from the float32
+    data, at the bar of the BatchNorm vectors (5e-6 of the largest entry).  The plain fp32 sums of a2s_col_stats are off by ~2^-24 mean^2 = 5e-7 in
+    the variance there -- reported, not asserted."""
+    from piano_a2s_amd import hip
+    L = hip.lib()
+    g = torch.Generator().manual_seed(n)
+    Cc, rpb = 300, 64                                                  # (more columns than threads of a workgroup)
+    x = (3.0 + torch.randn(1, Cc, generator=g)) + 1e-3 * torch.randn(n, Cc, generator=g)
+    xd, nblk = x.to(dev), (n + rpb - 1) // rpb
+    ones, zeros = torch.ones(Cc, device=dev), torch.zeros(Cc, device=dev)
+    ref_mean = x.double().mean(dim=0)
+    ref_invstd = 1 / torch.sqrt(x.double().var(dim=0, unbiased=False) + 1e-5)
+    errs = {}
+    for entry, blocks in (("a2s_col_stats_split", 2 * nblk), ("a2s_col_stats", nblk)):
+        part = torch.full((blocks, Cc, 2), float("nan"), device=dev)
+        hip.check(getattr(L, entry)(hip.stream(), hip._p(xd), hip._p(part), C.c_long(n), Cc, rpb), entry)
+        mean, invstd, scale, shift = (torch.empty(Cc, device=dev) for _ in range(4))
+        rm, rv, nbt = zeros.clone(), ones.clone(), torch.tensor(0, device=dev)
+        hip.check(L.a2s_bn_finalize(hip.stream(), hip._p(part), blocks, Cc, C.c_double(n), hip._p(ones), hip._p(zeros), hip._p(rm), hip._p(rv), hip._p(nbt),
+                                    hip._p(mean), hip._p(invstd), hip._p(scale), hip._p(shift), hip.f32(1e-5), hip.f32(0.1), 1), "bn_finalize")
+        torch.cuda.synchronize()
+        assert torch.isfinite(part).all(), entry
+        errs[entry] = (_rel(mean, ref_mean), _rel(invstd, ref_invstd))
+        _report(f"{entry} rows {n}, variance 1e-6 at mean 3: invstd", errs[entry][1])
+    assert errs["a2s_col_stats_split"][0] < 5e-6 and errs["a2s_col_stats_split"][1] < 5e-6, errs
+
+
 @pytest.mark.parametrize("H,T,B,split", [(32, 41, 3, False), (256, 1201, 2, False), (256, 1201, 2, True), (256, 1201, 70, True), (256, 37, 300, True)])
 def test_attention_step(dev, H, T, B, split):
     from piano_a2s_amd import hip
