@@ -139,7 +139,7 @@ int a2s_env_check(void);
  * persistent launch behaves as if a wait had timed out. */
 int a2s_persist_abort_latch(void* device_word);
 
-/* ---- ConvStack (models.py:475-502,:523-534).  Activations are (B, T, C, F); see csrc/a2s_conv.hip.
+/* ---- ConvStack (models.py:475-502,:523-534).  Activations are (B, T, C, F); see csrc/a2s_conv.hip (weight gradients: a2s_conv_wgrad.hip, BatchNorm: a2s_bn.hip).
  * conv3x3: y = conv(relu(x*in_scale+in_shift)) (scale/shift NULL: plain x), zero padding 1, no bias;
  * stat_partial [blocks][Cout][2] receives per-block sum / sum-of-squares of y (NULL to skip);
  * flip=1 runs the data-gradient form with w read as w'[ci][co][2-dt][2-df]. */

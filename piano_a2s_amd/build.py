@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "liba2s_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
-SOURCES = ["a2s_api.hip", "a2s_gemm.hip", "a2s_conv.hip", "a2s_conv_rows.hip", "a2s_conv_wrows.hip", "a2s_seq.hip", "a2s_bwd.hip", "a2s_opt.hip", "a2s_vqt.hip", "a2s_step.hip", "a2s_persist.hip", "a2s_dec_persist.hip", "a2s_linear.hip", "a2s_metrics.hip", "a2s_grammar.hip", "a2s_beam.hip", "a2s_align.hip", "a2s_render.hip", "a2s_augment.hip", "a2s_notes.hip", "a2s_tempo.hip", "a2s_room.hip", "a2s_specaug.hip", "a2s_resample.hip", "a2s_beat.hip", "a2s_agree.hip", "a2s_dtw.hip", "a2s_dynamics.hip", "a2s_tuning.hip", "a2s_retime.hip"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -26,7 +26,7 @@ def _stale(target, deps):
 
 
 def needs_build():
-    srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES]
     return _stale(LIB, srcs + _headers())
 
 
@@ -39,8 +39,6 @@ def build(force=False, verbose=False):
     jobs, objs = [], []
     for f in SOURCES:
         src = os.path.join(CSRC, f)
-        if not os.path.exists(src):
-            continue
         obj = os.path.join(OBJ, f[:-4] + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + headers):
@@ -68,6 +66,9 @@ def build_variant(name, extra_flags, sources=None):
     """A measurement build next to the product library: csrc/_obj/liba2s_hip_<name>.so with extra compiler flags (e.g. -DRW_TRACE); load it with
     A2S_LIB=<path>.  Only `sources` (default: all) are recompiled with the flags, the rest reuse the product objects."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    unknown = sorted(set(sources or ()) - set(SOURCES))
+    if unknown:
+        raise ValueError(f"build_variant: no such source in csrc/: {', '.join(unknown)}")
     build()
     vdir = os.path.join(OBJ, name)
     os.makedirs(vdir, exist_ok=True)

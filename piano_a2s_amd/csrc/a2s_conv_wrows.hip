@@ -6,7 +6,7 @@
 // they lie in memory -- a 16-byte global load of 4 positions of one channel becomes 8 + 8 bytes of the two fp16 term images
 // [channel][position] in LDS, and a fragment is one ds_read_b128 of 8 consecutive positions.  The only shift is df on the input side: a
 // lane reads its aligned 8 positions plus the 8 bytes before and after; df = 1 is the aligned window, df = 0 / 2 are four v_alignbit_b32
-// each (one window serves the three df fragments of a (dt, ci) column tile).  What round 2's kernel (conv3x3_wgrad_split, a2s_conv.hip:
+// each (one window serves the three df fragments of a (dt, ci) column tile).  What round 2's kernel (conv3x3_wgrad_split, a2s_conv_wgrad.hip:
 // 25 ms at B = 256 for 40 -> 40, 3x its HBM time) paid for and this one does not: it tiled (clip, 2 rows, 64 columns) and re-staged the
 // input rows for every tile (3/2 x 66/64), shifted the operand per (tap, channel tile) with 4-byte neighbour reads (4-way bank conflicts),
 // and ran its staging and multiply phases one after the other.
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_rows(WgRowsArgs a) {
                     const bool has = (it + 1) * 256 <= DITEMS || st + 256 * it < DITEMS;
                     unsigned char* const p0 = dzbuf + buf * DBUF + (has ? ((st >> 5) + 8 * it) * WR_SROW + (st & 31) * 8 : (st >> 5) * WR_SROW + 256);
                     if (BNF) {
-                        // dz = scale (g' - c1 - xhat c2), g' = g where bn(y) > 0 (bn_bwd_value of a2s_conv.hip): formed here, written once for the
+                        // dz = scale (g' - c1 - xhat c2), g' = g where bn(y) > 0 (bn_bwd_value of a2s_conv_wgrad.hip): formed here, written once for the
                         // data-gradient convolution (every dz element lies in exactly one strip), then split like a loaded dz row
                         const int ch = min((st >> 5) + 8 * it, COUT - 1);
                         const f32x4 k0 = *reinterpret_cast<const f32x4*>(tabk + 8 * ch);

@@ -42,6 +42,7 @@ int a2s_linear_dgrad_bnstats_impl(hipStream_t st, int M, int N, int K, const flo
 bool a2s_linear_fwd_ok(int M, int N, int K, long lda, long ldc, int period, const void* A, const void* W, const void* C);
 int a2s_linear_fwd_impl(hipStream_t st, int M, int N, int K, const float* A, long lda, const float* W, float* C, long ldc, const float* a_scale,
     const float* a_shift, int period, const float* a_absmax, const float* w_absmax, float* ws, size_t ws_bytes);
+int a2s_linear_fwd_f64_impl(hipStream_t st, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period);
 size_t a2s_linear_wgrad_ws_bytes_impl(int M, int K);
 bool a2s_linear_wgrad_ok(int M, int N, int K, long ldz, long lda, long ldg, int period, const void* dz, const void* A, const void* G);
 int a2s_linear_wgrad_impl(hipStream_t st, int M, int N, int K, const float* dz, long ldz, const float* A, long lda, float* G, long ldg, const float* a_scale,
@@ -55,6 +56,13 @@ int a2s_tallk_wgrad_impl(hipStream_t st, int M, int Np, int K, const float* P, l
     float* bias, const float* p_absmax, const float* a_absmax, float* ws, size_t ws_bytes);
 
 // ---- a2s_conv.hip
+// tile of the fp32-input kernels (forward / data gradient and weight gradient): rows x columns per workgroup, input channels per LDS chunk
+#define CV_TR 4
+#define CV_FT 32
+#define CV_CK 20
+// trace builds (-DC4_TRACE, tools/conv_trace.py): workgroups x stages of 8 stamps each, in a buffer per file (a2s_conv_trace_read, a2s_conv_wgrad_trace_read)
+#define C4_TRACE_WGS 8
+#define C4_TRACE_STAGES 24
 int a2s_act_bound_impl(hipStream_t st, const float* scale, const float* shift, const float* absmax, int C, float* out);
 size_t a2s_conv3x3_workspace_floats_impl(int Cin);
 int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, const float* in_scale,
@@ -62,20 +70,23 @@ int a2s_conv3x3_impl(hipStream_t st, const float* x, const float* w, float* y, c
     const float* yl, const float* yl_mean, const float* yl_invstd, const float* yl_scale, const float* yl_shift,
     const float* x_absmax, const float* in_absmax, float* out_absmax);
 int a2s_conv3x3_stat_blocks_impl(int B, int T, int F, int Cin);
-int a2s_bn_finalize_impl(hipStream_t st, const float* partial, int nblocks, int C, double count, const float* gamma,
-    const float* beta, float* running_mean, float* running_var, long long* nbt, float* mean,
-    float* invstd, float* scale, float* shift, float eps, float momentum, int training);
-int a2s_bn_relu_apply_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F);
-int a2s_col_stats_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
-int a2s_linear_fwd_f64_impl(hipStream_t st, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period);
-int a2s_col_stats_split_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
-int a2s_bn1d_relu_dropout_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift,
-    const uint8_t* mask, float inv_keep, long n, int C);
+
+// ---- a2s_conv_wgrad.hip
 size_t a2s_conv3x3_wgrad_workspace_bytes_impl(int Cin, int Cout);
 int a2s_conv3x3_wgrad_impl(hipStream_t st, const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dW,
     float* ws, size_t ws_bytes, int B, int T, int F, int Cin, int Cout, const float* bn_y, const float* bn_mean,
     const float* bn_invstd, const float* bn_scale, const float* bn_shift, const float* bn_c12, float* dy_out,
     const float* dy_absmax, const float* act_absmax);
+
+// ---- a2s_bn.hip
+int a2s_bn_finalize_impl(hipStream_t st, const float* partial, int nblocks, int C, double count, const float* gamma,
+    const float* beta, float* running_mean, float* running_var, long long* nbt, float* mean,
+    float* invstd, float* scale, float* shift, float eps, float momentum, int training);
+int a2s_bn_relu_apply_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift, long n, int C, int F);
+int a2s_col_stats_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
+int a2s_col_stats_split_impl(hipStream_t st, const float* x, float* partial, long rows, int C, int rows_per_block);
+int a2s_bn1d_relu_dropout_impl(hipStream_t st, const float* x, float* y, const float* scale, const float* shift,
+    const uint8_t* mask, float inv_keep, long n, int C);
 int a2s_bn_bwd_impl(hipStream_t st, const float* g, const float* x, const float* mean, const float* invstd, const float* scale,
     const float* shift, const uint8_t* mask, float inv_keep, float* dgamma, float* dbeta, float* dx, float* partial,
     float* c12, long rows, int C, int F, float* dx_absmax);
@@ -91,6 +102,7 @@ int a2s_bn_bwd_sums_from_partial_impl(hipStream_t st, const float* partial, int 
 int a2s_bn_bwd_c12_from_sums_impl(hipStream_t st, const float* sums_local, const float* sums_global, double count_global, float* dgamma, float* dbeta,
     float* c12, int C);
 size_t a2s_bn_bwd_partial_floats_impl(long rows, int C, int F);
+void a2s_absmax_small_launch(hipStream_t st, const float* w, int n, float* out);     // one workgroup; for a2s_conv3x3_impl, see the note at the kernel
 
 // ---- a2s_conv_rows.hip
 int a2s_channel_absmax_impl(hipStream_t st, const float* x, long rows, int C, int F, float* out);

@@ -426,6 +426,39 @@ int a2s_linear_fwd_impl(hipStream_t st, int M, int N, int K, const float* A, lon
     return A2S_OK;
 }
 
+// z[m][n] = sum_k relu(x[m][k] * scale[k / period] + shift[k / period]) W[n][k] with the products and the sum in double: the Linear of a call of
+// few rows.  Its BatchNorm1d in training mode divides by sqrt(var + 1e-5) of a handful of values, so an error of z comes back up to 316-fold in
+// scale and shift (two rows whose z agree to 0.03: 2e3 x the error of z0 - z1 in shift); the fp32 accumulation of the GEMM kernels (1.4e-6 of
+// max |z| over K = 5120) is then what the statistics show.  One workgroup per output element; a few-row call is far too small to care.
+__global__ __launch_bounds__(256) void linear_fwd_f64(const float* __restrict__ x, const float* __restrict__ W, float* __restrict__ z,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift, int period, int K, int N) {
+    const int n = blockIdx.x, m = blockIdx.y;
+    const float* xr = x + (long)m * K;
+    const float* wr = W + (long)n * K;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int c = k / period;
+        const float a = fmaxf(fmaf(xr[k], scale[c], shift[c]), 0.f);
+        acc = fma((double)a, (double)wr[k], acc);
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) z[(long)m * N + n] = (float)red[0];
+}
+
+int a2s_linear_fwd_f64_impl(hipStream_t st, int M, int N, int K, const float* x, const float* W, float* z, const float* scale, const float* shift, int period) {
+    A2S_REQUIRE(x && W && z && scale && shift, "linear_fwd_f64: null tensor");
+    A2S_REQUIRE(M > 0 && M <= 65535 && N > 0 && K > 0 && period > 0 && K % period == 0, "linear_fwd_f64: unsupported shape M=%d N=%d K=%d period=%d", M, N, K, period);
+    hipLaunchKernelGGL(linear_fwd_f64, dim3(N, M), dim3(256), 0, st, x, W, z, scale, shift, period, K, N);
+    A2S_CHECK_LAUNCH("linear_fwd_f64");
+    return A2S_OK;
+}
+
 // =========================================================================================== weight gradient
 // G[n][k] += sum_m dz[m][n] * relu(y4[m][k] * scale[c] + shift[c])      (dW of ConvStack.out, reference models.py:68; N = 256, K = 19200, M = B*T)
 // The reduction index is the ROW m, the slow dimension of both tensors.  Same skeleton as lin_fwd with the roles turned:

@@ -16,7 +16,7 @@
     /* ConvStack: bit 0 the row-streaming kernels of a2s_conv_rows.hip, bit 1 their second generation (conv3x3_rows16) where it exists              \
        (Cout 20, 40), bits 2 / 3 its form with two accumulator sets for the forward / data-gradient launches; 0 = the tiled kernels of a2s_conv.hip */ \
     X(conv_rows, 7, COUNT, "A2S_CONV_ROWS")                                                                                                          \
-    /* the weight gradient on the row-streaming kernels of a2s_conv_wrows.hip */                                                                     \
+    /* the weight gradient on the row-streaming kernels of a2s_conv_wrows.hip (0: the tiled ones of a2s_conv_wgrad.hip) */                           \
     X(wgrad_rows, 1, COUNT, "A2S_WGRAD_ROWS")                                                                                                        \
     /* the first layer's compile-time-shaped kernels (conv3x3_c1_fixed, conv3x3_wgrad_c1_stream); 0 = the generic ones (tests: bit-equal) */         \
     X(conv_c1_fast, 1, RAW, 0)                                                                                                                       \

@@ -14,7 +14,7 @@ from piano_a2s_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # trace-build-only symbols (tools/, -DRW_TRACE and the like): exported by measurement builds, not declared by the header, called untyped
-UNDECLARED_OK = {"a2s_rows_trace_read", "a2s_conv_trace_read", "a2s_gemm_trace_read", "a2s_staff_emb_save_floats"}
+UNDECLARED_OK = {"a2s_rows_trace_read", "a2s_conv_trace_read", "a2s_conv_wgrad_trace_read", "a2s_gemm_trace_read", "a2s_staff_emb_save_floats"}
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""The first ConvStack layer's compile-time-shaped kernels (csrc/a2s_conv.hip: conv3x3_c1_fixed, conv3x3_wgrad_c1_stream; round 6) against the
+"""The first ConvStack layer's compile-time-shaped kernels (csrc/a2s_conv.hip: conv3x3_c1_fixed, a2s_conv_wgrad.hip: conv3x3_wgrad_c1_stream; round 6) against the
 generic Cin = 1 kernels they replace at the model's shape (20 channels x 480 bins): the same order of operations per output, per statistic and
 per tap sum, so every result is BIT-identical -- output, batch-statistics partials, per-channel max |y|, weight gradient, the BatchNorm input
 gradient written out.  Sizes where workgroups walk several rows (the streaming weight gradient prefetches the next row while it sums the

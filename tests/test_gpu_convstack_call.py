@@ -14,7 +14,7 @@ the oracle; every other difference fails the test and names the element.  The fl
 
 How the kernels form the decision.  Every kernel that masks a gradient or stages an activation evaluates x * scale + shift as ONE fma: the
 row-streaming, Linear and GEMM staging kernels write fmaf(...) (csrc/a2s_conv_rows.hip, a2s_conv_wrows.hip, a2s_linear.hip, a2s_gemm.hip); the tiled
-convolutions, the BatchNorm backward kernels (csrc/a2s_conv.hip) and the GEMM statistics epilogue (a2s_gemm.hip) write the plain expression, which
+convolutions (csrc/a2s_conv.hip, a2s_conv_wgrad.hip), the BatchNorm backward kernels (a2s_bn.hip) and the GEMM statistics epilogue (a2s_gemm.hip) write the plain expression, which
 hipcc contracts (its default for device code is -ffp-contract=fast-honor-pragmas and piano_a2s_amd/build.py passes no other; a probe kernel with that
 expression compiles to a single v_fma_f32 for gfx950).  So double(y) * double(scale) + double(shift) > 0 is the decision of every kernel and no
 element is ambiguous; the number of elements at which a two-rounding evaluation would have decided otherwise is reported beside the flips.
@@ -60,7 +60,7 @@ CASES = [
     (2, 1, 128),         # T = 1: only the middle kernel row contributes
     (1, 2, 128),         # one clip of two frames
     (2, 129, 128),       # 258 rows: three Linear blocks, the last of two rows; more than four 64-row weight-gradient blocks
-    # added to the issue's list: the model's own F.  conv1's compile-time-shaped weight gradient (conv3x3_wgrad_c1_stream<20, 480>, csrc/a2s_conv.hip) is
+    # added to the issue's list: the model's own F.  conv1's compile-time-shaped weight gradient (conv3x3_wgrad_c1_stream<20, 480>, csrc/a2s_conv_wgrad.hip) is
     # launched at F == 480 only, so no case above reaches it; F tiles 4 x 120
     (2, 3, 480),
 ]

@@ -1,6 +1,7 @@
 """Phase timeline of the split-operand convolution kernel from in-kernel shader-clock stamps (library built with -DC4_TRACE):
 per stage of wave 0 of 8 mid-grid workgroups -- barrier waits, staging (commit), input issue, multiply, epilogue.
-usage: A2S_LIB=.../liba2s_hip_trace.so python tools/conv_trace.py [B] [Cin] [Cout]"""
+usage: A2S_LIB=.../liba2s_hip_trace.so python tools/conv_trace.py [B] [Cin] [Cout]
+  (build.build_variant('trace', ['-DC4_TRACE'], ['a2s_conv.hip', 'a2s_conv_wgrad.hip']); A2S_TRACE_WGRAD=1: the weight-gradient kernel)"""
 import ctypes as C
 import os
 import sys
@@ -40,7 +41,8 @@ def main():
         hip.check(L.a2s_conv3x3(hip.stream(), hip._p(x), hip._p(w), hip._p(y), hip._p(scale), hip._p(shift), hip._p(partial), B, T, F, ci, co, 0, hip._p(cws)), "conv")
     torch.cuda.synchronize()
     buf = np.zeros(8 * 24 * 8, dtype=np.uint64)
-    rc = L.a2s_conv_trace_read(buf.ctypes.data_as(C.c_void_p))
+    read = L.a2s_conv_wgrad_trace_read if wgrad else L.a2s_conv_trace_read     # each file stamps into a buffer of its own
+    rc = read(buf.ctypes.data_as(C.c_void_p))
     assert rc == 0, rc
     t = buf.reshape(8, 24, 8).astype(np.int64)
     names = ["barrier1 wait", "commit (+weight DMA issue)", "barrier2 wait", "issue next loads", "multiply (issue)", "epilogue"]
